@@ -19,6 +19,10 @@ The default N=1 run also carries every other leg the design claims, in the same 
 ranking; after the timed region 8 users of the last headline step are re-ranked by the CPU oracle and must match bit
 for bit (``verified_users``; a mismatch ends the run with a non-zero exit code).
 
+``--dump-outputs DIR`` writes what the last timed step computed -- the (users, k) scores and item ids a caller of the
+ranking receives -- as ``DIR/topk_scores.npy`` (float32) and ``DIR/topk_items.npy`` (float64, exact), after the timed
+region.  The inputs are seeded, so two builds run with the same flags can be compared output for output.
+
 Rank 0 prints ONE JSON line.  ``roofline`` is for the dominant kernel (score_topk_kernel):
 achieved = 2*d flop per (user,item) pair x pairs per launch / average kernel time measured with
 HIP events recorded around that kernel on its stream.  ``cpu_baseline`` is the reference path
@@ -97,6 +101,23 @@ def self_launch(n_gpus, argv):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, scores, ids):
+    """--dump-outputs: the last timed step's lists as DIR/topk_scores.npy (float32) and DIR/topk_items.npy (float64, exact
+    for any int32 id).  A block larger than 64 MB in that form is cut to a fixed sample of its rows (seed 0, ascending)."""
+    s = scores.float().cpu().numpy()
+    i = ids.cpu().numpy().astype(np.float64)
+    row_bytes = s.shape[1] * (s.itemsize + i.itemsize)
+    if s.shape[0] * row_bytes > DUMP_BYTES_MAX - 4096:                  # room for the two .npy headers
+        rows = np.sort(np.random.default_rng(0).choice(s.shape[0], (DUMP_BYTES_MAX - 4096) // row_bytes, replace=False))
+        s, i = s[rows], i[rows]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "topk_scores.npy"), s)
+    np.save(os.path.join(path, "topk_items.npy"), i)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -136,7 +157,11 @@ def main():
     ap.add_argument("--legs", default="eval_d64,eval_f16,mask_topk,train_xl,train_xl_lightgcn,train,eval_validation,eval_midsize,eval_e2e,torch_rocm",
                     help="N=1: secondary legs carried in the same JSON line (comma separated; 'none' = headline only)")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle self-check of the last timed step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's scores and item ids to DIR/topk_scores.npy, DIR/topk_items.npy")
     args = ap.parse_args()
+    if args.dump_outputs and (args.train_xl or args.train_xl_lightgcn or args.train_only):
+        ap.error("--dump-outputs writes the headline ranking; --train-xl / --train-xl-lightgcn / --train-only do not run it")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks ourselves.  Decided BEFORE anything touches the GPU
@@ -249,6 +274,8 @@ def main():
 
     import zlib
     result_crc = zlib.crc32(out[1].cpu().numpy().tobytes(), zlib.crc32(out[0].cpu().numpy().tobytes()))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out[0], out[1])
     # what THIS rank launches, as the library reports it: Bu users x its item shard (item shards), or its share of the user
     # block x the whole table (user shards)
     users_here = Bu if args.shard == "items" else (rank + 1) * Bu // world - rank * Bu // world

@@ -87,3 +87,27 @@ def test_gpus_n_without_a_launcher_starts_its_own_ranks():
                               env=env, capture_output=True, text=True, timeout=600)
         assert real.returncode != 0                              # relayed from the launcher (both ranks refuse a CPU box)
         assert "needs an MI355X" in real.stderr + real.stdout    # ... i.e. the ranks DID start and parse their flags
+
+
+def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
+    """--dump-outputs: scores as float32, ids as float64 (exact); a block over 64 MB in that form is cut to the same
+    seeded sample of rows on every call, never more than 64 MB in all."""
+    import numpy as np
+    import torch
+    import bench
+    rng = np.random.default_rng(1)
+    s = torch.from_numpy(rng.standard_normal((300, 20)).astype(np.float32))
+    i = torch.from_numpy(rng.integers(0, 2**31 - 1, (300, 20)).astype(np.int32))
+    bench.dump_outputs(str(tmp_path / "small"), s, i)
+    ds, di = np.load(tmp_path / "small" / "topk_scores.npy"), np.load(tmp_path / "small" / "topk_items.npy")
+    assert ds.dtype == np.float32 and di.dtype == np.float64
+    assert np.array_equal(ds, s.numpy()) and np.array_equal(di.astype(np.int32), i.numpy())
+    n = bench.DUMP_BYTES_MAX // (20 * 12) + 1000                  # just over the cap
+    big_s = torch.arange(n * 20, dtype=torch.float32).reshape(n, 20)
+    big_i = torch.arange(n * 20, dtype=torch.int32).reshape(n, 20)
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), big_s, big_i)
+        assert sum(os.path.getsize(tmp_path / tag / f) for f in os.listdir(tmp_path / tag)) <= bench.DUMP_BYTES_MAX
+    a, b = np.load(tmp_path / "a" / "topk_items.npy"), np.load(tmp_path / "b" / "topk_items.npy")
+    assert np.array_equal(a, b) and a.shape[0] < n and np.all(np.diff(a[:, 0]) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "topk_scores.npy"), a.astype(np.float32))   # rows of the two arrays agree

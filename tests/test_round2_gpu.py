@@ -282,9 +282,10 @@ _TWO_RANK_WORKER = r'''
 import os, sys
 sys.path.insert(0, os.environ["CR_ROOT"])
 import numpy as np, torch, torch.distributed as dist
-torch.cuda.set_device(0)
-dev = torch.device("cuda", 0)
-dist.init_process_group("gloo")                       # two processes share the one GPU; gloo stages through the host
+gpu = int(os.environ["LOCAL_RANK"]) if os.environ.get("CR_GPU_PER_RANK") == "1" else 0
+torch.cuda.set_device(gpu)
+dev = torch.device("cuda", gpu)
+dist.init_process_group("gloo")                       # ranks share GPU 0 unless CR_GPU_PER_RANK=1; gloo stages through the host
 rank, world = dist.get_rank(), dist.get_world_size()
 from coldrec_amd import ops
 from coldrec_amd.eval import ShardedTopK, UserShardedTopK, shard_bounds
@@ -415,14 +416,18 @@ def test_two_ranks_real_hip_kernels_on_one_gpu_over_gloo(tmp_path):
 
 
 def test_eight_ranks_real_hip_kernels_on_one_gpu_over_gloo(tmp_path):
-    """The node size the north_star names, with the HIP kernels in the loop: EIGHT ranks share the one GPU (gloo for the
+    """The node size the north_star names, with the HIP kernels in the loop: EIGHT ranks, one GPU each (gloo for the
     exchange).  4 096 users x 200 003 items: eight item shards whose sizes differ (200 003 = 8 x 25 000 + 3) + all-gather
     + the 160-candidate canonical merge == one rank, bit for bit; eight user slices likewise; the data-parallel slices of
     a 4 096-triple batch (MF, LightGCN, MF-SGD) and the row-sharded propagation (800 rows into 8 blocks) as in the
-    two-rank test."""
+    two-rank test.  Eight processes must not share one device, so the test needs eight GPUs."""
+    n_gpus = torch.cuda.device_count()
+    if n_gpus < 8:
+        pytest.skip(f"needs 8 GPUs (one per rank), found {n_gpus}")
     script = tmp_path / "eight_rank_worker.py"
     script.write_text(_TWO_RANK_WORKER)
-    env = dict(os.environ, CR_ROOT=ROOT, OMP_NUM_THREADS="2", CR_NUSERS="4096", CR_NITEMS="200003", CR_B="4096")
+    env = dict(os.environ, CR_ROOT=ROOT, OMP_NUM_THREADS="2", CR_NUSERS="4096", CR_NITEMS="200003", CR_B="4096",
+               CR_GPU_PER_RANK="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
                           "--master-addr", "127.0.0.1", "--master-port", "29648", str(script)],
                          env=env, capture_output=True, text=True, timeout=1500)
@@ -489,25 +494,38 @@ print("COMM_OK", rank, world)
 '''
 
 
-def test_comm_c_abi_two_ranks(tmp_path):
-    """crh_comm_unique_id / _init / _allgather_topk / _allreduce_f32 / _destroy driven by TWO processes with no
-    torch.distributed anywhere (what a non-Python caller of the C ABI does): item shards ranked per rank, the packed
-    top-k exchanged by the library's RCCL all-gather, crh_merge_topk == the one-rank ranking, bit for bit.  Needs two
-    GPUs: RCCL refuses two ranks on one device ("Duplicate GPU detected"), so on a one-GPU box the ranks report the
-    refusal (a named error from crh_comm_init, not a hang) and the test is skipped -- the documented limitation."""
+def _comm_two_ranks(tmp_path):
     script = tmp_path / "comm_worker.py"
     script.write_text(_COMM_WORKER)
     env = dict(os.environ, CR_ROOT=ROOT, OMP_NUM_THREADS="2")
     procs = [subprocess.Popen([sys.executable, str(script), str(r), "2", str(tmp_path / "uid.bin")], env=env,
                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(2)]
     outs = [p.communicate(timeout=600) for p in procs]
-    text = "".join(o[0] for o in outs)
-    if "COMM_INIT_REFUSED" in text:
-        assert torch.cuda.device_count() < 2, text
-        assert all(p.returncode == 0 for p in procs)
-        pytest.skip("one GPU: RCCL refuses two ranks on one device -- " + text.strip().splitlines()[0][:200])
+    return procs, outs, "".join(o[0] for o in outs)
+
+
+def test_comm_c_abi_two_ranks(tmp_path):
+    """crh_comm_unique_id / _init / _allgather_topk / _allreduce_f32 / _destroy driven by TWO processes with no
+    torch.distributed anywhere (what a non-Python caller of the C ABI does): item shards ranked per rank, the packed
+    top-k exchanged by the library's RCCL all-gather, crh_merge_topk == the one-rank ranking, bit for bit.  Needs two
+    GPUs: RCCL refuses two ranks on one device ("Duplicate GPU detected"); the next test pins that refusal down."""
+    n_gpus = torch.cuda.device_count()
+    if n_gpus < 2:
+        pytest.skip(f"needs 2 GPUs, found {n_gpus}")
+    procs, outs, text = _comm_two_ranks(tmp_path)
     assert all(p.returncode == 0 for p in procs), (text[-2000:], outs[0][1][-3000:], outs[1][1][-3000:])
     assert "COMM_OK 0 2" in text and "COMM_OK 1 2" in text
+
+
+def test_comm_c_abi_two_ranks_on_one_gpu_are_refused(tmp_path):
+    """The documented limitation of the two-rank C-ABI exchange on a one-GPU box: the ranks get a named error from
+    crh_comm_init (RCCL refuses two ranks on one device) and exit cleanly -- no hang, no crash."""
+    n_gpus = torch.cuda.device_count()
+    if n_gpus >= 2:
+        pytest.skip(f"{n_gpus} GPUs: the two ranks get one each (test_comm_c_abi_two_ranks)")
+    procs, outs, text = _comm_two_ranks(tmp_path)
+    assert all(p.returncode == 0 for p in procs), (text[-2000:], outs[0][1][-3000:], outs[1][1][-3000:])
+    assert "COMM_INIT_REFUSED" in text and "COMM_OK" not in text, text[-2000:]
 
 
 def test_comm_c_abi_one_rank_packed_allgather(tmp_path):
