@@ -8,9 +8,15 @@ Per case: random table sizes / widths / batch sizes / duplicate patterns, then
     bit-exact, heavy rows to rounding;
   * a few optimiser steps with the dense Adam and with the touched-rows replay -> identical bits after the flush;
   * whole epochs with the one-launch MF step (crh_mf_step_f32) against the three-kernel step -> same losses and tables
-    up to the summation order of the norms, and bit-identical when repeated.
+    up to the summation order of the norms, and bit-identical when repeated;
+  * SGD: the touched-rows update (crh_sgd_rows_f32) against the dense one, bitwise; whole epochs of the one-launch SGD step
+    against the three-kernel SGD step and an fp64 replay;
+  * the L2 norm / its backward (crh_l2_norm_f32, crh_l2_reg_bwd_f32) at random lengths, offsets (aligned and not) and
+    scales against fp64;
+  * the row-ownership split of the plan backward (crh_bpr_bwd_owned_f32, crh_rows_pack_f32 / _unpack_f32): the union over
+    the ranks is the plain plan backward, bit for bit.
 
-    python tests/fuzz/fuzz_train_ops.py --minutes 5 [--seed 0]
+    python tests/fuzz/fuzz_train_ops.py --minutes 5 [--seed 0] [--only owned,sgd]
 """
 import argparse
 import os
@@ -23,7 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from coldrec_amd import ops  # noqa: E402
-from coldrec_amd.train import MFEngine  # noqa: E402
+from coldrec_amd.train import EpochRunner, MFEngine  # noqa: E402
 from oracle import oracle_np as orc  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -341,11 +347,187 @@ def case_fused(rng):
                  err=float(np.abs(a - b).max()), scale=float(np.abs(b).max()), nbad=int(bad.sum()))
 
 
+def rand_widths(rng):
+    """widths of every lane-group size, idle lanes included (pick_group: next power of two >= d / 4, capped at 64)"""
+    return int(rng.choice([4, 8, 12, 16, 20, 36, 64, 68, 128, 132, 200, 252, 256]))
+
+
+def case_sgd(rng):
+    d = rand_widths(rng)
+    n_u, n_i = int(rng.integers(2, 900)), int(rng.integers(8, 1500))
+    B = int(rng.choice([64, 300, 1000, 4096]))
+    s = (2.0 * d) ** -0.25                                          # score differences O(1) at every width
+    U0 = (rng.standard_normal((n_u, d)) * s).astype(np.float32)
+    V0 = (rng.standard_normal((n_i, d)) * s).astype(np.float32)
+    hot_frac = float(rng.choice([0.0, 0.3, 0.95]))
+
+    def triples(n):
+        u = rng.integers(0, n_u, n).astype(np.int32)
+        i = np.where(rng.random(n) < hot_frac, rng.integers(0, min(3, n_i), n), rng.integers(0, n_i, n)).astype(np.int32)
+        j = rng.integers(0, n_i, n).astype(np.int32)
+        return u, i, np.where(j == i, (j + 1) % n_i, j).astype(np.int32)
+    lr = float(rng.choice([0.05, 0.5]))
+    # (1) one backward, then the touched-rows update == the dense update, bit for bit (a zero gradient moves nothing)
+    ui, pi, ni = triples(B)
+    tu, tp, tn = t(ui), t(pi), t(ni)
+    plan = ops.build_plans_device(tu, tp, tn, B)[0]
+    E = t(np.concatenate([U0, V0]))
+    G = torch.zeros_like(E)
+    ops.bpr_fwd_bwd(E[:n_u], E[n_u:], E[n_u:], tu, tp, tn, 1e-3, G[:n_u], G[n_u:], G[n_u:], plan=plan)
+    p1, g1, p2, g2 = E.clone(), G.clone(), E.clone(), G.clone()
+    ops.sgd_rows(p1, g1, plan, B, n_u, lr)
+    ops.sgd_dense(p2, g2, lr)
+    if not (torch.equal(p1.view(torch.int32), p2.view(torch.int32)) and not bool(g1.any())):
+        fail("sgd_rows != sgd_dense", d=d, B=B, n_u=n_u, n_i=n_i)
+    if not np.array_equal(p1.cpu().numpy().view(np.uint32), orc.sgd_dense(E.cpu().numpy(), G.cpu().numpy(), lr).view(np.uint32)):
+        fail("sgd_rows != oracle fma", d=d, B=B)
+    # (2) whole epochs: one-launch SGD step (twice: bit-identical) vs three-kernel SGD step vs an fp64 replay
+    n_rec = int(rng.integers(1, 3 * B + 2))
+    epochs = [triples(n_rec) for _ in range(int(rng.integers(1, 3)))]
+    res = []
+    for fused in (True, True, False):
+        eng = MFEngine(U0, V0, lr, 1e-3, DEV, optimizer="sgd")
+        runner = EpochRunner(eng, n_rec, B, fused=fused)
+        if d <= 256 and eng.fused != fused:
+            fail("sgd: one-launch step not taken", d=d, B=B, n_rec=n_rec)
+        losses = torch.cat([runner.run(*ep).clone() for ep in epochs])
+        torch.cuda.synchronize()
+        res.append((losses.cpu().numpy(), eng.E.cpu().numpy()))
+    for a, b in zip(res[0], res[1]):
+        if not np.array_equal(a.view(np.uint32), b.view(np.uint32)):
+            fail("sgd one-launch step not deterministic", d=d, B=B, n_rec=n_rec)
+    # losses: the two forms differ in the summation order of the norms only (test_fused_mf_step_matches_three_kernel_step)
+    if not np.allclose(res[0][0], res[2][0], rtol=2e-6, atol=1e-9):
+        fail("sgd one-launch vs three-kernel losses", d=d, B=B, n_rec=n_rec, err=float(np.abs(res[0][0] - res[2][0]).max()))
+    # fp64 replay: oracle gradients, p <- p - lr g.  Per step an fp32 gradient element is good to 5e-4 |g| + 1e-4 max|g|
+    # (case_bpr's bound), times lr, plus the fma's rounding (u |p|); x 2 for the drift those leave in the next gradients
+    E64 = np.concatenate([U0, V0]).astype(np.float64)
+    tol, want = np.zeros_like(E64), []
+    for (eu, ei, ej) in epochs:
+        for lo in range(0, n_rec, B):
+            sl = slice(lo, min(lo + B, n_rec))
+            bpr, l2, gU, gV, _ = orc.bpr_l2_fwd_bwd(E64[:n_u], E64[n_u:], eu[sl], ei[sl], ej[sl], 1e-3)
+            g = np.concatenate([gU, gV])
+            want.append((bpr, l2))
+            E64 = E64 - lr * g
+            tol += lr * (5e-4 * np.abs(g) + 1e-4 * np.abs(g).max()) + 2.0 ** -24 * np.abs(E64)
+    want = np.array(want)
+    sizes = np.array([min(lo + B, n_rec) - lo for _ in epochs for lo in range(0, n_rec, B)])
+    for tag, r in (("one-launch", res[0]), ("three-kernel", res[2])):
+        # -log(1e-5 + sigmoid) of one triple is ~6e-8 absolute in fp32: 1e-5 relative for a batch mean, 1e-4 for tiny batches
+        rt = np.where(sizes >= 64, 1e-5, 1e-4)[:, None]
+        if not (np.abs(r[0] - want) <= rt * np.abs(want) + 1e-12).all():
+            fail("sgd losses vs fp64 replay", form=tag, d=d, B=B, n_rec=n_rec, err=float(np.abs(r[0] - want).max()))
+        if not (np.abs(r[1] - E64) <= 2 * tol).all():
+            fail("sgd tables vs fp64 replay", form=tag, d=d, B=B, n_rec=n_rec, err=float(np.abs(r[1] - E64).max()))
+
+
+def case_l2(rng):
+    n = int(np.exp(rng.uniform(0, np.log(3e6))))
+    if rng.random() < 0.2:
+        n = int(rng.choice([1, 2, 3, 4, 5, (1 << 20) - 1, 1 << 20, (1 << 20) + 1, (1 << 20) + 5]))
+    off = int(rng.integers(0, 4))
+    scale = float(10.0 ** rng.uniform(-6, 6))
+    x = (rng.standard_normal(n) * scale * 10.0 ** rng.uniform(-2, 2, n)).astype(np.float32)
+    buf = torch.empty(n + 4, dtype=torch.float32, device=DEV)
+    xv = buf[off:off + n]
+    xv.copy_(t(x))
+    x64 = x.astype(np.float64)
+    want = float(np.sqrt(np.dot(x64, x64)))
+    nrm = ops.l2_norm(xv)
+    nrm2 = ops.l2_norm(xv)
+    # tests/test_train_edges_gpu.py::l2_norm_bound: roundings per term along the kernel's summation tree
+    blocks = min(max((n // 4 + 255) // 256, 1), 1024)
+    chain = (-(-(n // 4) // (blocks * 256)) + 3) if off == 0 else -(-n // (blocks * 256))
+    h = 1 + chain + 8 + -(-blocks // 256) + 8
+    u = 2.0 ** -24
+    bound = 0.5 * h * u / (1 - h * u) + u
+    got = float(nrm.item())
+    if not (abs(got - want) <= bound * want) or not torch.equal(nrm.view(torch.int32), nrm2.view(torch.int32)):
+        fail("l2 norm", n=n, off=off, scale=scale, got=got, want=want, bound=bound)
+    reg = float(rng.choice([1e-4, 0.05]))
+    go = None if rng.random() < 0.5 else float(rng.uniform(0.1, 3.0))
+    gx = ops.l2_reg_bwd(xv, reg, nrm, None if go is None else torch.tensor(go, dtype=torch.float32, device=DEV)).cpu().numpy()
+    wg = x64 * (np.float64(np.float32(reg)) * (1.0 if go is None else np.float64(np.float32(go))) / (n * want))
+    if want > 0 and not (np.abs(gx - wg) <= (6 * u + bound) * np.abs(wg)).all():
+        fail("l2 backward", n=n, off=off, scale=scale, err=float(np.abs(gx - wg).max()))
+
+
+def case_owned(rng):
+    d = int(rng.choice([4, 8, 12, 20, 36, 64, 68, 128, 132, 256]))
+    n_u, n_i = int(rng.integers(1, 600)), int(rng.integers(2, 900))
+    L = int(rng.choice([1, 7, 64, 513, 2000]))
+    n_rec = L + (int(rng.integers(1, L + 1)) if rng.random() < 0.5 else 0)     # a short last batch under stride L
+    s = (2.0 * d) ** -0.25
+    U = t((rng.standard_normal((n_u, d)) * s).astype(np.float32))
+    V = t((rng.standard_normal((n_i, d)) * s).astype(np.float32))
+    u = rng.integers(0, n_u, n_rec).astype(np.int32)
+    hot = rng.integers(0, n_i, 2)
+    i = np.where(rng.random(n_rec) < rng.choice([0.0, 0.5]), hot[rng.integers(0, 2, n_rec)], rng.integers(0, n_i, n_rec)).astype(np.int32)
+    j = rng.integers(0, n_i, n_rec).astype(np.int32)
+    plans = ops.build_plans_device(t(u), t(i), t(j), L)
+    bi = plans.shape[0] - 1                                        # the last batch (short when n_rec % L != 0)
+    lo = bi * L
+    B = n_rec - lo
+    plan = plans[bi].contiguous()
+    tu, ti, tj = t(u[lo:]), t(i[lo:]), t(j[lo:])
+    pl = plan.cpu().numpy()
+    nu_, ni_, Lp = int(pl[0]), int(pl[1]), int(pl[2])
+    rows = np.concatenate([pl[3:3 + nu_].astype(np.int64), n_u + pl[4 + 3 * Lp:4 + 3 * Lp + ni_].astype(np.int64)])
+    own_mod = int(rng.choice([2, 3, 5, 8, nu_ + ni_ + int(rng.integers(1, 4))]))
+    if own_mod > 64:
+        own_mod = int(rng.choice([2, 3, 5, 8]))                    # (one launch per rank: keep the case short)
+    E = torch.cat([U, V]).contiguous()
+    R = E.shape[0]
+    reg = float(rng.choice([0.0, 1e-3]))
+    G_want, loss_want = torch.zeros_like(E), torch.zeros(2, device=DEV)
+    ops.bpr_fwd_bwd(E[:n_u], E[n_u:], E[n_u:], tu, ti, tj, reg, G_want[:n_u], G_want[n_u:], G_want[n_u:], loss_want, plan=plan,
+                    workspace=ops.bpr_workspace(B, DEV))
+    ws, sums = ops.bpr_workspace(B, DEV), torch.zeros(4, device=DEV)
+    ops.bpr_fwd(E[:n_u], E[n_u:], E[n_u:], tu, ti, tj, sums, ws)
+    cap = ops.rows_pack_cap(B, own_mod)
+    ids_all, rows_all = [], []
+    sent = -777.25
+    for rem in range(own_mod):
+        G = torch.full_like(E, sent)
+        loss = torch.zeros(2, device=DEV)
+        ops.bpr_bwd_owned(E[:n_u], E[n_u:], tu, ti, tj, reg, sums, G[:n_u], G[n_u:], loss, ws, plan, own_mod, rem)
+        mine = rows[rem::own_mod]
+        om = np.zeros(R, bool)
+        om[mine] = True
+        om = t(om)
+        if not torch.equal(G[om].view(torch.int32), G_want[om].view(torch.int32)) or not bool((G[~om] == sent).all()):
+            fail("owned backward != plain backward on the owned rows / wrote other rows", d=d, B=B, L=L, own_mod=own_mod, rem=rem)
+        if not torch.equal(loss.view(torch.int32), loss_want.view(torch.int32)):
+            fail("owned loss", d=d, B=B, own_mod=own_mod, rem=rem)
+        ids = torch.full((cap,), -5, dtype=torch.int32, device=DEV)
+        packed = torch.full((cap, d), sent, device=DEV)
+        ops.rows_pack(G, plan, B, n_u, own_mod, rem, ids, packed)
+        want_ids = np.full(cap, -1, np.int64)
+        want_ids[:len(mine)] = mine
+        if not np.array_equal(ids.cpu().numpy(), want_ids):
+            fail("rows_pack ids", d=d, B=B, own_mod=own_mod, rem=rem)
+        k = len(mine)
+        if not torch.equal(packed[:k].view(torch.int32), G_want[t(mine)].view(torch.int32)) or not bool((packed[k:] == sent).all()):
+            fail("rows_pack rows", d=d, B=B, own_mod=own_mod, rem=rem)
+        ids_all.append(ids)
+        rows_all.append(packed)
+    G_got = torch.zeros_like(E)
+    ops.rows_unpack(G_got, torch.cat(ids_all).contiguous(), torch.cat(rows_all).contiguous())
+    torch.cuda.synchronize()
+    if not torch.equal(G_got.view(torch.int32), G_want.view(torch.int32)):
+        fail("owned union != plain plan backward", d=d, B=B, L=L, own_mod=own_mod)
+
+
+KINDS = {"bpr": case_bpr, "spmm": case_spmm, "adam": case_adam, "fused": case_fused, "sgd": case_sgd, "l2": case_l2,
+         "owned": case_owned}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=5.0)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--only", default="", help="run only this kind of case (bpr / spmm / adam / fused)")
+    ap.add_argument("--only", default="", help="run only these kinds of case, comma-separated (%s)" % " / ".join(KINDS))
     ap.add_argument("--force", default="", help="JSON: pin the shape of the fused case (d, n_u, n_i, B, n_rec, hot, epochs)")
     ap.add_argument("--stats", action="store_true",
                     help="fused cases: also replay every case in fp64 and report the error distributions of the one-launch "
@@ -359,10 +541,15 @@ def main():
         FORCE.update(json.loads(args.force))
     rng = np.random.default_rng(args.seed)
     t_end = time.time() + args.minutes * 60
-    counts = {"bpr": 0, "spmm": 0, "adam": 0, "fused": 0}
+    only = [k for k in args.only.split(",") if k]
+    for k in only:
+        if k not in KINDS:
+            ap.error("--only: unknown kind %r (kinds: %s)" % (k, ", ".join(KINDS)))
+    kinds = only or list(KINDS)
+    counts = {k: 0 for k in KINDS}
     while time.time() < t_end:
-        which = args.only or str(rng.choice(["bpr", "spmm", "adam", "fused"]))
-        {"bpr": case_bpr, "spmm": case_spmm, "adam": case_adam, "fused": case_fused}[which](rng)
+        which = kinds[0] if len(kinds) == 1 else str(rng.choice(kinds))
+        KINDS[which](rng)
         counts[which] += 1
     print(f"fuzz ok: {counts} random cases within parity, seed {args.seed}")
     if STATS:
