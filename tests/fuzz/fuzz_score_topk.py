@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Randomised parity fuzzing of the scoring kernels against the canonical oracle (tests-style tool: it imports
 oracle/).  Draws shapes, widths, k, mask densities, split counts, layouts and dtypes for --minutes, checks
-bit-exact scores + indices (fp32, and fp16 on exact-arithmetic tables) and prints a summary line.
+bit-exact scores + indices (fp32, and fp16 on exact-arithmetic tables) and prints a summary line.  A few cases (all of them
+with --shards) rank the catalogue as the ranks of the sharded evaluation do: 2 .. 8 shards (``shard_bounds`` or random cuts off
+the tile grid), one launch per shard with item_base = lo, merged, against the one-launch ranking bitwise and every shard against
+the oracle on sampled users.  A shard case is drawn from its own generator, seeded (seed, case): its failure line names it and
+``tools/fuzz_case_replay.py --score-shard SEED CASE`` replays it alone.
 
-    python tests/fuzz/fuzz_score_topk.py --minutes 5 [--seed 0]
+    python tests/fuzz/fuzz_score_topk.py --minutes 5 [--seed 0] [--shards]
 """
 import argparse
 import os
@@ -18,17 +22,136 @@ sys.path.insert(0, ROOT)
 from coldrec_amd import ops  # noqa: E402
 from oracle import oracle_np as orc  # noqa: E402
 
+SWITCHES = ("CRH_SCORE_WG", "CRH_SCORE_DMA", "CRH_SCORE_SEED")
+
+
+def shard_case(seed, case, dev, verbose=False):
+    """One sharded case drawn from default_rng([seed, case]).  Returns (ok, description)."""
+    from coldrec_amd.eval import ShardedTopK, shard_bounds
+    rng = np.random.default_rng([seed, case])
+    world = int(rng.integers(2, 9))
+    half = rng.random() < 0.35
+    d = int(rng.choice([16, 32, 64, 128, 256] if half else [8, 16, 32, 64, 128, 256, 24, 100]))
+    k = int(rng.choice([1, 5, 20, 20, 33, 64, 128]))
+    kind = rng.choice(["small", "big", "seeded"], p=[0.55, 0.3, 0.15])
+    if kind == "big":                                  # workgroup / DMA kernels (with CRH_SCORE_WG=2)
+        n_users, n_items = int(rng.integers(32768, 34000)), int(rng.integers(world * 40, 24000))
+        if d not in (64, 128, 256):
+            d = int(rng.choice([64, 128, 256] if half else [64, 128]))
+    elif kind == "seeded":                             # every shard >= 65 536 items, few users
+        n_users, n_items = int(rng.integers(1, 500)), world * int(rng.integers(65536, 70000))
+        d = 16 if half else int(rng.choice([8, 16]))
+    else:
+        n_users, n_items = int(rng.integers(1, 700)), int(rng.integers(world, 40000))
+    if rng.random() < 0.5:
+        cuts = [shard_bounds(n_items, world, r)[0] for r in range(world)] + [n_items]
+    else:                                              # random cuts, a third of them pushed off the grid by 1 or 31
+        inner = rng.choice(np.arange(1, n_items), world - 1, replace=False)
+        inner = np.where(rng.random(world - 1) < 0.33, (inner // 32) * 32 + rng.choice([1, 31], world - 1), inner)
+        cuts = [0] + sorted(set(int(c) for c in np.clip(inner, 1, n_items - 1))) + [n_items]
+    if any(hi <= lo for lo, hi in zip(cuts[:-1], cuts[1:])):
+        cuts = [shard_bounds(n_items, world, r)[0] for r in range(world)] + [n_items]
+    world = len(cuts) - 1
+    quant = half or rng.random() < 0.5
+    if quant:
+        q = int(rng.choice([2, 4, 8]))
+        U = (rng.integers(-q, q + 1, (n_users, d)) / q).astype(np.float32)
+        V = (rng.integers(-q, q + 1, (n_items, d)) / q).astype(np.float32)
+    else:
+        U = (rng.standard_normal((n_users, d)) * 0.3).astype(np.float32)
+        V = (rng.standard_normal((n_items, d)) * 0.3).astype(np.float32)
+    mean_r = int(rng.choice([0, 3, 30]))
+    lens = rng.poisson(mean_r, n_users) if mean_r else np.zeros(n_users, np.int64)
+    rated = [np.unique(x) for x in np.split(rng.integers(0, n_items, int(lens.sum())), np.cumsum(lens)[:-1])]
+    for c in cuts[1:-1]:                               # some users rated at the boundaries
+        u = int(rng.integers(0, n_users))
+        rated[u] = np.union1d(rated[u], [c - 1, c])
+    frac = float(rng.choice([0.0, 0.05, 0.2, 0.9]))
+    bm_ids = np.where(rng.random(n_items) < frac)[0] if frac else np.zeros(0, np.int64)
+    bm_ids = np.union1d(bm_ids, np.clip(np.array([c + o for c in cuts[1:-1] for o in (-1, 0, 31, 32)], np.int64), 0, n_items - 1))
+    use_idx = rng.random() < 0.4 and kind != "big"
+    users = rng.permutation(n_users)[: max(1, n_users // 2)].astype(np.int64) if use_idx else None
+    splits = int(rng.choice([0, 0, 1, 3]))
+    env = {}
+    if kind == "big" and rng.random() < 0.7:
+        env["CRH_SCORE_WG"] = "2"
+    env["CRH_SCORE_DMA"] = str(rng.choice(["1", "0", "2", "3"]))
+    env["CRH_SCORE_SEED"] = str(rng.choice(["1", "0", "2"]))
+    for v in SWITCHES:
+        os.environ.pop(v, None)
+    os.environ.update(env)
+    nq = n_users if users is None else len(users)
+    q_rated = rated if users is None else [rated[u] for u in users]
+    rp_u = np.concatenate([[0], np.cumsum([len(r) for r in q_rated])]).astype(np.int64)
+    col_u = np.concatenate(q_rated).astype(np.int64) if rp_u[-1] else np.zeros(0, np.int64)
+    tdt = torch.float16 if half else torch.float32
+    tU, tV = torch.from_numpy(U).to(dev).to(tdt), torch.from_numpy(V).to(dev).to(tdt)
+    rp_t = torch.from_numpy(rp_u).to(dev) if rp_u[-1] else None
+    rc_t = torch.from_numpy(col_u.astype(np.int32)).to(dev) if rp_u[-1] else None
+    bm_t = ops.make_bitmap(n_items, bm_ids, dev)
+    tu = None if users is None else torch.from_numpy(users.astype(np.int32)).to(dev)
+    S, I, routes = [], [], []
+    for r in range(world):
+        lo, hi = cuts[r], cuts[r + 1]
+        x = ops.score_topk_route(nq, hi - lo, d, k, half=half, has_bitmap=bm_t is not None, n_splits=splits)
+        routes.append("%s%s%s" % (x["route"], "+seeded" if x["seeded"] else "", "/" + x["dma_form"] if x["dma_form"] else ""))
+        if verbose:
+            print("shard %d [%d, %d) base %% 32 = %d: %s" % (r, lo, hi, lo % 32, routes[r]))
+        s, i = ShardedTopK(tV[lo:hi], lo, n_items, k).topk(tU, tu, rp_t, rc_t, bm_t, n_splits=splits)
+        S.append(s)
+        I.append(i)
+    ms, mi = ops.merge_topk(torch.stack(S), torch.stack(I), k)
+    us, ui = ops.score_topk(tU, tu, tV, k, rp_t, rc_t, bm_t)
+    torch.cuda.synchronize()
+    desc = dict(seed=seed, case=case, world=world, cuts=cuts, routes=routes, half=half, d=d, k=k, n_users=n_users,
+                n_items=n_items, quant=quant, mean_r=mean_r, frac=frac, use_idx=use_idx, splits=splits, env=env)
+    what = []
+    if not (torch.equal(mi, ui) and torch.equal(ms.view(torch.int32), us.view(torch.int32))):
+        bad = ((mi != ui).any(1) | (ms.view(torch.int32) != us.view(torch.int32)).any(1)).nonzero().flatten()[:8].tolist()
+        what.append("merged != unsharded for users %s" % bad)
+    if quant or not half:                              # every shard against the oracle, exact arithmetic
+        pick = np.arange(nq) if nq <= 48 else np.unique(np.concatenate([[0, 63, 64, 127, 128, nq - 1], rng.choice(nq, 24)]))
+        pick = pick[pick < nq]
+        q_users = pick if users is None else users[pick]
+        prp = np.concatenate([[0], np.cumsum([len(rated[u]) for u in q_users])]).astype(np.int64)
+        pcol = np.concatenate([rated[u] for u in q_users]).astype(np.int64) if prp[-1] else None
+        bm_o = orc.make_bitmap(n_items, bm_ids) if len(bm_ids) else None
+        for r in range(world):
+            lo, hi = cuts[r], cuts[r + 1]
+            ws, wi = orc.score_topk(U, q_users, V[lo:hi], k, prp if prp[-1] else None, pcol, bm_o, item_base=lo)
+            gs, gi = S[r].cpu().numpy()[pick], I[r].cpu().numpy()[pick]
+            if not (np.array_equal(gi, wi) and np.array_equal(gs.view(np.uint32), ws.view(np.uint32))):
+                rows = np.where((gi != wi).any(1) | (gs.view(np.uint32) != ws.view(np.uint32)).any(1))[0]
+                what.append("shard %d [%d, %d) (%s) != oracle for users %s" % (r, lo, hi, routes[r], pick[rows][:8].tolist()))
+    for v in SWITCHES:
+        os.environ.pop(v, None)
+    return not what, dict(desc, failures=what)
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=5.0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--shards", action="store_true", help="every case is a sharded case")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(args.seed)
     t_end = time.time() + args.minutes * 60
-    n_cases = n_big = n_seeded = n_many = 0
+    n_cases = n_big = n_seeded = n_many = n_shard = 0
+    pick_shard = np.random.default_rng([args.seed, 1 << 30])      # its own stream: the other cases draw as they always did
+    next_report = time.time() + 60
     while time.time() < t_end:
+        if time.time() > next_report:                              # a long run reports once a minute
+            print(f"... {n_cases} cases ({n_shard} sharded)", flush=True)
+            next_report += 60
+        if args.shards or pick_shard.random() < 0.03:
+            ok, desc = shard_case(args.seed, n_cases, dev)
+            if not ok:
+                print("MISMATCH shard", desc, flush=True)
+                sys.exit(1)
+            n_cases += 1
+            n_shard += 1
+            continue
         half = rng.random() < 0.35
         d = int(rng.choice([16, 32, 64, 128, 256] if half else [8, 16, 32, 64, 128, 256, 24, 100]))
         k = int(rng.choice([1, 5, 10, 20, 20, 20, 33, 64, 100, 128]))
@@ -113,7 +236,7 @@ def main():
         n_seeded += seeded
         n_many += many
     print(f"fuzz ok: {n_cases} random cases ({n_big} in workgroup-kernel territory, {n_seeded} in seeded-route territory of which "
-          f"{n_many} with users that fill the chip) bit-exact vs the oracle, seed {args.seed}")
+          f"{n_many} with users that fill the chip, {n_shard} sharded) bit-exact vs the oracle, seed {args.seed}")
 
 
 if __name__ == "__main__":

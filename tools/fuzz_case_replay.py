@@ -4,6 +4,11 @@ and the fp64 closed form (oracle gradients + oracle Adam) side by side, step by 
 largest table difference of each GPU form against the replay with the element it sits on.
 
     python tools/fuzz_case_replay.py tests/fuzz/cases/<case>.npz
+
+A sharded scoring case of tests/fuzz/fuzz_score_topk.py (its failure line gives seed and case) is replayed alone, with the route
+and the verdict of every shard:
+
+    python tools/fuzz_case_replay.py --score-shard SEED CASE
 """
 import os
 import sys
@@ -18,6 +23,12 @@ from coldrec_amd.train import EpochRunner, MFEngine  # noqa: E402
 from oracle import oracle_np as orc  # noqa: E402
 
 DEV = torch.device("cuda:0")
+if sys.argv[1] == "--score-shard":
+    sys.path.insert(0, os.path.join(ROOT, "tests", "fuzz"))
+    from fuzz_score_topk import shard_case
+    ok, desc = shard_case(int(sys.argv[2]), int(sys.argv[3]), DEV, verbose=True)
+    print("ok" if ok else "MISMATCH", desc)
+    sys.exit(0 if ok else 1)
 c = np.load(sys.argv[1])
 U0, V0, B, n_rec = c["U0"], c["V0"], int(c["B"]), int(c["n_rec"])
 n_u, n_i, d = U0.shape[0], V0.shape[0], U0.shape[1]
