@@ -12,12 +12,15 @@ at 8 GPUs").  Inputs are resident in HBM before the timed region.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 4 --warmup 1
 
-The default N=1 run also carries every other leg the design claims, in the same JSON line (each with its own
-``roofline``): ``eval_f16`` (configs[4] shape, fp16 MFMA), ``mask_topk`` (dense-block ranking, HBM-bound), ``train_xl``
-(S-TRAIN-XL dense Adam, HBM-bound), ``train_mf`` / ``train_mf_sgd`` / ``train_lightgcn`` (configs[1] / [2], with
-``value_end_to_end`` = triples per wall second over whole epochs WITH the sampler running) and the per-epoch validation
-ranking; after the timed region 8 users of the last headline step are re-ranked by the CPU oracle and must match bit
-for bit (``verified_users``; a mismatch ends the run with a non-zero exit code).
+A plain run does only what the headline figure needs: it builds the inputs, warms up, times the steps, writes
+``--dump-outputs`` if asked and prints the line.  Everything else the benchmark measures or checks runs with ``--full``,
+after the timed region.  With ``--full`` the N=1 run also carries every other leg the design claims, in the same JSON line
+(each with its own ``roofline``): ``eval_f16`` (configs[4] shape, fp16 MFMA), ``mask_topk`` (dense-block ranking,
+HBM-bound), ``train_xl`` (S-TRAIN-XL dense Adam, HBM-bound), ``train_mf`` / ``train_mf_sgd`` / ``train_lightgcn``
+(configs[1] / [2], with ``value_end_to_end`` = triples per wall second over whole epochs WITH the sampler running) and
+the per-epoch validation ranking, N > 1 adds the data-parallel training legs, and 64 users of the last headline step are
+re-ranked by the CPU oracle and must match bit for bit (``verified_users``; a mismatch ends the run with a non-zero exit
+code).
 
 ``--dump-outputs DIR`` writes what the last timed step computed -- the (users, k) scores and item ids a caller of the
 ranking receives -- as ``DIR/topk_scores.npy`` (float32) and ``DIR/topk_items.npy`` (float64, exact), after the timed
@@ -25,8 +28,8 @@ region.  The inputs are seeded, so two builds run with the same flags can be com
 
 Rank 0 prints ONE JSON line.  ``roofline`` is for the dominant kernel (score_topk_kernel):
 achieved = 2*d flop per (user,item) pair x pairs per launch / average kernel time measured with
-HIP events recorded around that kernel on its stream.  ``cpu_baseline`` is the reference path
-restated with the same library calls (oracle/ref_port.py: torch.matmul -> masks -> torch.topk),
+HIP events recorded around that kernel on its stream.  ``cpu_baseline`` (``--full``) is the reference
+path restated with the same library calls (oracle/ref_port.py: torch.matmul -> masks -> torch.topk),
 timed on the host cores on a bounded sample (rank 0, N=1 only).
 """
 import argparse
@@ -102,6 +105,7 @@ def self_launch(n_gpus, argv):
 
 
 DUMP_BYTES_MAX = 64 << 20
+ALL_LEGS = "eval_d64,eval_f16,mask_topk,train_xl,train_xl_lightgcn,train,eval_validation,eval_midsize,eval_e2e,torch_rocm"
 
 
 def dump_outputs(path, scores, ids):
@@ -142,8 +146,12 @@ def main():
     ap.add_argument("--n-splits", type=int, default=0)
     ap.add_argument("--masks", choices=["warm", "none"], default="warm",
                     help="'warm' = rated CSR + 20%% cold-item bitmap (default); 'none' = diagnostic run without masks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the secondary train legs (N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the oracle self-check of the last step, the secondary legs "
+                         "(--legs), the CPU baseline and, for N > 1, the data-parallel train legs; a plain run does none")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full / --train-only: skip the CPU baselines")
+    ap.add_argument("--no-train", action="store_true",
+                    help="with --full: skip the secondary legs (N=1) or the data-parallel train legs (N > 1)")
     ap.add_argument("--lazy-adam", action="store_true", help="with --train-xl: touched-rows replay of dense Adam")
     ap.add_argument("--train-only", action="store_true", help="only the two secondary train legs (profiling aid)")
     ap.add_argument("--train-xl", action="store_true",
@@ -154,14 +162,17 @@ def main():
     ap.add_argument("--cpu-sample-users", type=int, default=2048,
                     help="users of the CPU baseline (blocks of 256 against the WHOLE item table, SURVEY.md 8(d))")
     ap.add_argument("--cpu-budget-s", type=float, default=30.0, help="the CPU baseline stops after this many seconds")
-    ap.add_argument("--legs", default="eval_d64,eval_f16,mask_topk,train_xl,train_xl_lightgcn,train,eval_validation,eval_midsize,eval_e2e,torch_rocm",
-                    help="N=1: secondary legs carried in the same JSON line (comma separated; 'none' = headline only)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle self-check of the last timed step")
+    ap.add_argument("--legs", default=None,
+                    help="with --full, N=1: secondary legs carried in the same JSON line (comma separated; 'none' = headline "
+                         "only; default: " + ALL_LEGS + ")")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the oracle self-check of the last timed step")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's scores and item ids to DIR/topk_scores.npy, DIR/topk_items.npy")
     args = ap.parse_args()
     if args.dump_outputs and (args.train_xl or args.train_xl_lightgcn or args.train_only):
         ap.error("--dump-outputs writes the headline ranking; --train-xl / --train-xl-lightgcn / --train-only do not run it")
+    if args.legs not in (None, "none") and not args.full:
+        ap.error("--legs picks the secondary legs of a --full run; a plain run carries none")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks ourselves.  Decided BEFORE anything touches the GPU
@@ -326,9 +337,9 @@ def main():
 
     if gen_leg is not None and rank == 0:
         result["dropoutnet_generator"] = gen_leg
-    # ---- self-check of the LAST timed step + CPU baseline: both need the tables on the host (rank 0)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
-    want_verify = rank == 0 and not args.no_verify and args.shard == "items" and not args.generator
+    # ---- self-check of the LAST timed step + CPU baseline (--full): both need the tables on the host (rank 0)
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_verify = args.full and rank == 0 and not args.no_verify and args.shard == "items" and not args.generator
     U_cpu = V_cpu = None
     want_verify = want_verify and args.dtype == "f32"          # the fp16 table is checked on the device by the eval_f16 leg
     if (want_cpu or want_verify) and float(I) * d * 4 > 24e9:
@@ -357,9 +368,9 @@ def main():
     # (the CPU baseline itself runs AFTER the legs, below: half a minute of every host core at full tilt leaves worker threads
     # spinning and clocks ramped, and the legs that time host-side work beside the GPU -- the trainers' end-to-end epochs --
     # must not run in its wake)
-    legs = [] if args.legs == "none" else [x.strip() for x in args.legs.split(",") if x.strip()]
+    legs = [] if not args.full or args.legs == "none" else [x.strip() for x in (args.legs or ALL_LEGS).split(",") if x.strip()]
     wall = {"headline_incl_setup_and_checks": round(time.perf_counter() - t_main, 1)}   # where the run's minutes go
-    if world > 1 and not args.no_train and args.dtype == "f32":
+    if args.full and world > 1 and not args.no_train and args.dtype == "f32":
         # Secondary leg.  The headline line must survive it: an exception is caught below, and if a rank gets stuck
         # in a collective (the others would wait for ever) a watchdog on every rank prints what it has (rank 0) and
         # ends the process with a NON-ZERO code, so a stuck RCCL run is never reported as a success.

@@ -89,6 +89,18 @@ def test_gpus_n_without_a_launcher_starts_its_own_ranks():
         assert "needs an MI355X" in real.stderr + real.stdout    # ... i.e. the ranks DID start and parse their flags
 
 
+def test_legs_without_full_is_refused():
+    """The secondary legs run only in a --full run: naming one without --full is an argument error (exit code 2, before
+    anything touches the GPU), not a plain run that silently leaves it out."""
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "eval_f16"], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 2 and "--full" in out.stderr, (out.returncode, out.stderr[-2000:])
+    helptext = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                              timeout=300).stdout
+    assert "--full" in helptext
+
+
 def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
     """--dump-outputs: scores as float32, ids as float64 (exact); a block over 64 MB in that form is cut to the same
     seeded sample of rows on every call, never more than 64 MB in all."""

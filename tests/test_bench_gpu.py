@@ -12,8 +12,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--items", "200003", "--users", "4096", "--users-per-step", "2048", "--steps", "2", "--warmup", "1",
-         "--no-cpu-baseline", "--no-train", "--legs", "none"]
+PLAIN = ["--items", "200003", "--users", "4096", "--users-per-step", "2048", "--steps", "2", "--warmup", "1"]
+SMALL = PLAIN + ["--full", "--no-cpu-baseline", "--no-train", "--legs", "none"]       # + the oracle self-check
 
 
 def _bench(flags, **env_extra):
@@ -36,6 +36,25 @@ def test_gpus_2_self_launched_equals_gpus_1():
     assert list(two)[-1] == "legs_summary" and "headline" in two["legs_summary"]
 
 
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the run times the same steps and returns the same last-step lists as a --full run (crc32 and dumped
+    arrays equal), and carries none of the --full work: no oracle self-check, no CPU baseline, no secondary leg."""
+    import numpy as np
+    plain = _bench(["--gpus", "1"] + PLAIN + ["--dump-outputs", str(tmp_path / "plain")])
+    full = _bench(["--gpus", "1"] + SMALL + ["--dump-outputs", str(tmp_path / "full")])
+    assert full["verified_users"] == 64
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert plain[key] is not None and type(plain[key]) is type(full[key]), key
+    assert (plain["metric"], plain["unit"], plain["higher_is_better"], plain["dtype"]) == (
+        full["metric"], full["unit"], full["higher_is_better"], full["dtype"])
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["frac"] > 0
+    assert plain["result_crc32"] == full["result_crc32"]
+    for f in ("topk_scores.npy", "topk_items.npy"):
+        assert np.array_equal(np.load(tmp_path / "plain" / f).view(np.uint8), np.load(tmp_path / "full" / f).view(np.uint8)), f
+    assert not {"verified_users", "cpu_baseline", "host_legs_skipped", "predicted_scaling_8gpu"} & set(plain)
+    assert set(plain["legs_summary"]) == {"headline"} and set(plain["wall_s"]) == {"headline_incl_setup_and_checks", "total"}
+
+
 def test_gpus_4_user_shards_self_launched_equals_gpus_1():
     one = _bench(["--gpus", "1"] + SMALL)
     four = _bench(["--gpus", "4", "--shard", "users"] + SMALL, CRH_BENCH_BACKEND="gloo")
@@ -52,7 +71,7 @@ def test_gpus_8_full_headline_size_self_launched_equals_gpus_1():
     n_gpus = torch.cuda.device_count()
     if n_gpus < 8:
         pytest.skip(f"needs 8 GPUs (one per rank), found {n_gpus}")
-    full = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--legs", "none"]
+    full = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--legs", "none"]
     one = _bench(["--gpus", "1"] + full)
     eight = _bench(["--gpus", "8"] + full, CRH_BENCH_BACKEND="gloo")
     assert eight["n_gpus"] == 8 and eight["config"]["items"] == 10_000_000 and eight["config"]["users_per_step"] == 131072

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One round's profile (on the GPU box, from the repo root): bash tools/profile_round.sh <tag> [parts]      e.g. r05_z "eval f16"
 #   parts: any of  eval f16 train xl mx  (default: all)
-#   eval   rocprofv3 kernel stats of the DEFAULT bench command (every leg) + separate PMC passes of the headline kernel
+#   eval   rocprofv3 kernel stats of the --full bench command (every leg) + separate PMC passes of the headline kernel
 #   f16    the ceiling record of the fp16 scoring kernel (configs[4]): the bare MFMA(+LDS) loops on THIS box, the shipped
 #          kernel and the SAME kernel with the selection ablated (-DCRH_PROFILE build), each with
 #          SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE (matrix-pipe occupancy and effective clock); + the feature-ladder
@@ -22,8 +22,8 @@ has() { [[ " $PARTS " == *" $1 "* ]]; }
 [ -x tools/probes/dma_stream_probe ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++20 -mllvm -amdgpu-mfma-vgpr-form -o tools/probes/dma_stream_probe tools/probes/dma_stream_probe.hip
 
 if has eval; then
-$T rocprofv3 --kernel-trace --stats -d "$OUT/stats" -- python3 bench.py --no-cpu-baseline > "$OUT/bench_under_stats.json" 2> "$OUT/stats.err"
-EV="--no-cpu-baseline --no-verify --legs eval_d64 --steps 2 --warmup 1"      # the headline's launches + the d=64 leg's (its own kernel rows)
+$T rocprofv3 --kernel-trace --stats -d "$OUT/stats" -- python3 bench.py --full --no-cpu-baseline > "$OUT/bench_under_stats.json" 2> "$OUT/stats.err"
+EV="--full --no-cpu-baseline --no-verify --legs eval_d64 --steps 2 --warmup 1"      # the headline's launches + the d=64 leg's (its own kernel rows)
 $T rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d "$OUT/pmc_sq" -- python3 bench.py $EV > /dev/null 2> "$OUT/pmc_sq.err"
 $T rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -- python3 bench.py $EV > /dev/null 2> "$OUT/pmc_fetch.err"
 $T rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -- python3 bench.py $EV > /dev/null 2> "$OUT/pmc_write.err"
@@ -38,7 +38,7 @@ if has f16; then
 $T ./tools/probes/mfma_energy_probe > "$OUT/f16_bare_loops.log" 2>&1
 $T ./tools/probes/dma_stream_probe > "$OUT/f16_stream_ladder.log" 2>&1
 # (b) the leg as shipped and with the selection ablated, un-profiled (wall numbers must not come from a profiled pass)
-F16="--no-cpu-baseline --no-verify --steps 1 --warmup 0 --legs eval_f16"
+F16="--full --no-cpu-baseline --no-verify --steps 1 --warmup 0 --legs eval_f16"
 PLIB=$PWD/coldrec_amd/lib/libcoldrec_hip_profile.so
 [ -f "$PLIB" ] || make -s -C coldrec_amd/csrc profile
 $T python3 bench.py $F16 > "$OUT/f16_shipped.json" 2> "$OUT/f16_shipped.err"

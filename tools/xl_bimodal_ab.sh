@@ -6,7 +6,7 @@
 TAG=${1:-r06}
 cd "$(dirname "$0")/.." || exit 1
 OUT=gpurun_out/xl_ab_$TAG; mkdir -p "$OUT"
-C="--no-cpu-baseline --no-verify --steps 1 --warmup 0"
+C="--full --no-cpu-baseline --no-verify --steps 1 --warmup 0"
 pick() { python3 - "$1" <<'PY'
 import json, sys
 for ln in open(sys.argv[1]):
