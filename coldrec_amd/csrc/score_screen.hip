@@ -1,0 +1,392 @@
+// Screened ranking of fp32 d=128 catalogues (the headline shape): the catalogue is walked once in fp16 by the
+// LDS-DMA kernel (16x the fp32 MFMA rate) keeping K' = SCREEN_KP > k candidates per user, the candidates are rescored with the
+// canonical fmaf chain, and a per-user certificate proves that no item outside them can enter the exact top-k.  Users without
+// the proof are ranked exactly by the fallback below.  This file holds the kernels of stages 0 (fp16 copies and their error
+// norms), 2 (rescoring + certificate) and 3 (exact fallback); score_topk.hip runs stage 1 and the orchestration.
+//
+// The bound.  u, v: fp32 rows; u^, v^: their fp16 copies scaled back (one power of two per table, so scaling is exact);
+// a: the approximate score the fp16 kernel ranked by (its fp32 accumulator, scaled back); s: the exact fmaf chain.
+//   |s - u.v|     <= g_d |u| |v|               (d-term fma chain, g_d = d 2^-24 / (1 - d 2^-24))
+//   |u.v - u^.v^| <= |u| |v - v^| + |u - u^| |v^|
+//   |u^.v^ - a|   <= g' |u^| |v^|              (f16 x f16 products are exact in fp32; g' = 2^-12 covers any fp32 accumulation order)
+// so |s - a| <= B_u = |u| R + |u - u^| N^ + g_d |u| N + g' |u^| N^ with R = max |v - v^|, N = max |v|, N^ = max |v^| over the
+// unmasked rows of the shard.  The fp16 copies carry no subnormals (flushed to zero here, which lands in the residuals), so
+// every partial sum of the MFMA is a multiple of 2^-48 of the scaled operands and never underflows; the exact chain's own
+// subnormal roundings are covered by an absolute term.  Norms are evaluated in fp64 and rounded up; a non-finite input makes
+// its norm +inf (or NaN), and then no comparison with the bound can pass.
+#include <math.h>
+
+#include "score_topk_common.h"
+
+namespace crh_score {
+namespace {
+
+constexpr int SD = 128;            // row width of the screened route
+constexpr int FB_SLICES_MAX = 64;  // item slices per uncertified user in the fallback
+
+// a float that is >= x (x >= 0 or NaN); +inf when x is NaN or beyond the float range
+__device__ __forceinline__ float up_float(double x) {
+    if (!(x <= 3.0e38)) return __builtin_inff();
+    float f = (float)x;
+    if ((double)f < x) f = __uint_as_float(__float_as_uint(f) + 1u);
+    return f;
+}
+
+// exponent e of the table's power-of-two scale: max|x| * 2^e < 2^15 (0 for an all-zero table)
+__device__ __forceinline__ int scale_exp(const unsigned* stats, int word) {
+    const float m = __uint_as_float(stats[word]);
+    if (!(m > 0.0f) || !(m <= 3.4e38f)) return 0;
+    int E;
+    frexpf(m, &E);          // m < 2^E
+    return 15 - E;
+}
+
+// fp16 copy of x * 2^e without subnormals (they are flushed to zero: the residual carries them)
+__device__ __forceinline__ _Float16 to_f16(float x, int e) {
+    const float y = ldexpf(x, e);
+    _Float16 hv = (_Float16)y;
+    if (fabsf((float)hv) < 6.103515625e-05f) hv = (_Float16)0.0f;     // 2^-14: the smallest fp16 normal
+    return hv;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// max |x| over the finite entries of rows (rows ? rows[r] : r) of a [*][SD] table -> atomicMax on the float bits of stats[word]
+__global__ __launch_bounds__(256) void screen_maxabs_kernel(const float* __restrict__ tab, const int32_t* __restrict__ rows,
+                                                            int64_t n_rows, unsigned* __restrict__ stats, int word) {
+    const int64_t n4 = n_rows * (SD / 4);
+    float m = 0.0f;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) {
+        const int64_t r = e / (SD / 4);
+        const int64_t row = rows ? (int64_t)rows[r] : r;
+        const f32x4 x = *reinterpret_cast<const f32x4*>(tab + row * SD + 4 * (e % (SD / 4)));
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float ax = fabsf(x[c]);
+            if (ax <= 3.4028235e38f) m = fmaxf(m, ax);     // NaN and inf fail the test: they reach the residuals instead
+        }
+    }
+    __shared__ float red[4];
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float b = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        if (b > 0.0f) atomicMax(stats + word, __float_as_uint(b));
+    }
+}
+
+// Sums over one row of 16 consecutive lanes (8 elements each): x^2, (x - x^)^2, x^^2 in fp64.
+__device__ __forceinline__ void row_sums(const f32x4& x0, const f32x4& x1, _Float16 (&hv)[8], int e, double& sxx, double& sdd,
+                                         double& shh) {
+    const double inv = ldexp(1.0, -e);
+    sxx = 0.0; sdd = 0.0; shh = 0.0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const float x = c < 4 ? x0[c & 3] : x1[c & 3];
+        hv[c] = to_f16(x, e);
+        const double xh = (double)(float)hv[c] * inv;        // exact
+        const double dx = (double)x - xh;
+        sxx += (double)x * (double)x;
+        sdd += dx * dx;
+        shh += xh * xh;
+    }
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+        sxx += __shfl_xor(sxx, o);
+        sdd += __shfl_xor(sdd, o);
+        shh += __shfl_xor(shh, o);
+    }
+}
+
+// an upper bound of sqrt(s) for an fp64 sum of squares (its own rounding error is far below the 2^-30 margin)
+__device__ __forceinline__ float up_norm(double s) { return up_float(sqrt(s) * (1.0 + 0x1p-30)); }
+
+// Item shard -> fp16 in the fragment-ordered packed layout of pack_items_f16_kernel<128> (tile t, unit c = 8 elements of row r at
+// ((t * 8 + c / 2) * 64 + (c & 1) * 32 + r)), bitmap-masked rows zero; the maxima of |v - v^|, |v|, |v^| over the unmasked rows
+// go to stats[2..4].  Grid-stride over tiles; 16 lanes per row.
+__global__ __launch_bounds__(256) void screen_items_kernel(const float* __restrict__ v, int64_t n_items, const uint32_t* __restrict__ bitmap,
+                                                           int64_t item_base, _Float16* __restrict__ packed, unsigned* __restrict__ stats) {
+    const int e = scale_exp(stats, 0);
+    const int64_t T = (n_items + 31) >> 5;
+    float mr = 0.0f, mn = 0.0f, mh = 0.0f;
+    u32x4* dst = reinterpret_cast<u32x4*>(packed);
+    for (int64_t t = blockIdx.x; t < T; t += gridDim.x) {
+        for (int p = 0; p < 2; ++p) {
+            const int u = threadIdx.x + 256 * p, r = u >> 4, c = u & 15;
+            int64_t row = (t << 5) + r;
+            if (row >= n_items) row = n_items - 1;        // the tail tile repeats the last row (as the pack kernels do)
+            const bool masked = bitmap != nullptr && ((bitmap[(item_base + row) >> 5] >> ((item_base + row) & 31)) & 1u);
+            const float* src = v + row * SD + 8 * c;
+            const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
+            _Float16 hv[8];
+            double sxx, sdd, shh;
+            row_sums(x0, x1, hv, e, sxx, sdd, shh);
+            u32x4 o = u32x4{0u, 0u, 0u, 0u};
+            if (!masked) {
+                o = __builtin_bit_cast(u32x4, f16x8{hv[0], hv[1], hv[2], hv[3], hv[4], hv[5], hv[6], hv[7]});
+                mr = fmaxf(mr, up_norm(sdd));
+                mn = fmaxf(mn, up_norm(sxx));
+                mh = fmaxf(mh, up_norm(shh));
+                if (sdd != sdd || sxx != sxx) mr = __builtin_inff();     // NaN input: fmaxf would drop it
+            }
+            dst[(t * 8 + (c >> 1)) * 64 + (c & 1) * 32 + r] = o;
+        }
+    }
+    __shared__ float red[3][4];
+    mr = wave_max(mr);
+    mn = wave_max(mn);
+    mh = wave_max(mh);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = mr;
+        red[1][threadIdx.x >> 6] = mn;
+        red[2][threadIdx.x >> 6] = mh;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const float b = fmaxf(fmaxf(red[threadIdx.x][0], red[threadIdx.x][1]), fmaxf(red[threadIdx.x][2], red[threadIdx.x][3]));
+        if (b > 0.0f) atomicMax(stats + 2 + threadIdx.x, __float_as_uint(b));
+    }
+}
+
+// User block (in `users` order) -> fp16 row-major [n_users][128]; per user |u|, |u^|, |u - u^| (upper bounds) into ustat[3 j ..].
+__global__ __launch_bounds__(256) void screen_users_kernel(const float* __restrict__ uemb, const int32_t* __restrict__ users,
+                                                           int64_t n_users, _Float16* __restrict__ uh, float* __restrict__ ustat,
+                                                           const unsigned* __restrict__ stats) {
+    const int e = scale_exp(stats, 1);
+    const int64_t n_units = n_users * 16;
+    for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < ((n_units + 255) & ~(int64_t)255); w += (int64_t)gridDim.x * 256) {
+        const int64_t j = (w < n_units ? w : n_units - 1) >> 4;      // (the shuffles need every lane of the row group)
+        const int c = (int)(w & 15);
+        const int64_t row = users ? (int64_t)users[j] : j;
+        const float* src = uemb + row * SD + 8 * c;
+        const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
+        _Float16 hv[8];
+        double sxx, sdd, shh;
+        row_sums(x0, x1, hv, e, sxx, sdd, shh);
+        if (w < n_units) {
+            reinterpret_cast<u32x4*>(uh)[j * 16 + c] = __builtin_bit_cast(u32x4, f16x8{hv[0], hv[1], hv[2], hv[3], hv[4], hv[5], hv[6], hv[7]});
+            if (c == 0) {
+                const bool bad = sxx != sxx || sdd != sdd;
+                ustat[3 * j + 0] = bad ? __builtin_inff() : up_norm(sxx);
+                ustat[3 * j + 1] = bad ? __builtin_inff() : up_norm(shh);
+                ustat[3 * j + 2] = bad ? __builtin_inff() : up_norm(sdd);
+            }
+        }
+    }
+}
+
+// the canonical score: fmaf chain over k ascending from +0 (oracle/topk_oracle.c)
+__device__ __forceinline__ float exact_chain(const float* __restrict__ u, const float* __restrict__ v) {
+    float s = 0.0f;
+#pragma unroll 8
+    for (int q = 0; q < SD; q += 4) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(u + q), b = *reinterpret_cast<const f32x4*>(v + q);
+        s = __builtin_fmaf(a.x, b.x, s);
+        s = __builtin_fmaf(a.y, b.y, s);
+        s = __builtin_fmaf(a.z, b.z, s);
+        s = __builtin_fmaf(a.w, b.w, s);
+    }
+    return s;
+}
+
+// is gi in the ascending list col[lo, hi)?  (one lane, binary search)
+__device__ __forceinline__ bool lane_in_list(const int32_t* __restrict__ col, int64_t lo, int64_t hi, int gi) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        const int x = col[mid];
+        if (x == gi) return true;
+        if (x < gi) lo = mid + 1;
+        else hi = mid;
+    }
+    return false;
+}
+
+// Stage 2: one wave per user, one lane per candidate.  A certified user's k best candidates by (exact score desc, id asc) are its
+// answer; every other user is appended to fail_list (count in stats[5]).
+__global__ __launch_bounds__(256) void screen_certify_kernel(ScreenArgs s) {
+    const int lane = threadIdx.x & 63;
+    const int64_t slot = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (slot >= s.n_users) return;                       // wave-uniform
+    const int KP = s.kp, K = s.k;
+    const bool mine = lane < KP;
+    int gi = CRH_PAD_IDX;
+    float a = CRH_NEG_INF;
+    if (mine) {
+        gi = s.cand_idx[slot * KP + lane];
+        a = s.cand_score[slot * KP + lane];
+    }
+    const bool real = mine && gi != CRH_PAD_IDX && (int64_t)gi >= s.item_base && (int64_t)gi < s.item_base + s.n_items;
+    bool masked = false;
+    if (real && s.bitmap) masked = (s.bitmap[gi >> 5] >> (gi & 31)) & 1u;
+    if (real && !masked && s.rated_rowptr) masked = lane_in_list(s.rated_col, s.rated_rowptr[slot], s.rated_rowptr[slot + 1], gi);
+    const int64_t urow = s.users ? (int64_t)s.users[slot] : slot;
+    float sc = CRH_NEG_INF;
+    if (real) sc = exact_chain(s.user_emb + urow * SD, s.item_emb + ((int64_t)gi - s.item_base) * SD);
+    const bool ok = !mine || (real && !masked && __builtin_isfinite(a) && __builtin_isfinite(sc));
+    // rank of this lane's candidate among the KP by the canonical key (ids are distinct)
+    int rank = 0;
+    for (int j = 0; j < KP; ++j) {
+        const float sj = __shfl(sc, j);
+        const int ij = __shfl(gi, j);
+        rank += (j != lane && crh_better(sj, ij, sc, gi)) ? 1 : 0;
+    }
+    const unsigned long long kth = __ballot(mine && rank == K - 1);
+    const float ek = __shfl(sc, kth ? __builtin_ctzll(kth) : 0);
+    const float a_last = __shfl(a, KP - 1);
+    bool cert = s.mode != 3 && __ballot(!ok) == 0ull && kth != 0ull;
+    if (cert) {
+        const float* us = s.ustat + 3 * slot;
+        const float R = __uint_as_float(s.stats[2]), N = __uint_as_float(s.stats[3]), Nh = __uint_as_float(s.stats[4]);
+        const double gd = SD * 0x1p-24 / (1.0 - SD * 0x1p-24), gp = 0x1p-12;
+        double B = (double)us[0] * R + (double)us[2] * Nh + gd * (double)us[0] * N + gp * (double)us[1] * Nh + 0x1p-126;
+        B *= 1.0 + 0x1p-20;
+        const double A = (double)a_last * ldexp(1.0, -(scale_exp(s.stats, 0) + scale_exp(s.stats, 1)));   // exact
+        double thr = A + B;
+        thr += fabs(thr) * 0x1p-50;                        // the rounding of that sum, upward
+        cert = (double)ek > thr && ek > CRH_MASKED_SCORE;  // NaN anywhere fails both
+    }
+    if (cert) {
+        if (mine && rank < K) {
+            s.out_score[slot * K + rank] = sc;
+            s.out_idx[slot * K + rank] = gi;
+        }
+    } else if (lane == 0) {
+        const unsigned f = atomicAdd(s.stats + 5, 1u);
+        s.fail_list[f] = (int32_t)slot;
+    }
+}
+
+// Stage 3a: exact per-(uncertified user, item slice) lists, grid-stride over count x n_slices work items (the count is read
+// here, on the device).  Semantics of the fused selection's slow path: an item is a candidate when its raw score (a bitmap-masked
+// item scores against a zero row, as in the packed copies) is above the list's threshold; masked candidates enter at -1e9.
+__global__ __launch_bounds__(256) void screen_fallback_kernel(ScreenArgs s) {
+    __shared__ float ush[4][SD];
+    __shared__ float lsh[4][32];
+    __shared__ int lih[4][32];
+    __shared__ int cnth[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int K = s.k, S = s.n_slices;
+    const int64_t n_work = (int64_t)s.stats[5] * S;
+    float* ls = lsh[wv];
+    int* li = lih[wv];
+    int* cnt = &cnth[wv];
+    for (int64_t w = (int64_t)blockIdx.x * 4 + wv; w < n_work; w += (int64_t)gridDim.x * 4) {
+        const int64_t f = w / S;
+        const int z = (int)(w % S);
+        const int64_t slot = s.fail_list[f];
+        const int64_t urow = s.users ? (int64_t)s.users[slot] : slot;
+        ush[wv][lane] = s.user_emb[urow * SD + lane];
+        ush[wv][lane + 64] = s.user_emb[urow * SD + lane + 64];
+        if (lane == 0) *cnt = 0;
+        const int64_t lo = s.n_items * z / S, hi = s.n_items * (z + 1) / S;
+        float tau = CRH_NEG_INF;
+        for (int64_t base = lo; base < hi; base += 64) {
+            const int64_t i = base + lane;
+            const bool valid = i < hi;
+            const int gl = (int)(s.item_base + (valid ? i : lo));
+            const bool bm = valid && s.bitmap && ((s.bitmap[gl >> 5] >> (gl & 31)) & 1u);
+            float raw = CRH_NEG_INF;
+            if (valid) {
+                if (bm) {
+                    raw = 0.0f;
+#pragma unroll 8
+                    for (int q = 0; q < SD; ++q) raw = __builtin_fmaf(ush[wv][q], 0.0f, raw);
+                } else {
+                    raw = exact_chain(ush[wv], s.item_emb + i * SD);
+                }
+            }
+            unsigned long long cand = __ballot(valid && raw > tau);
+            const unsigned long long bms = __ballot(bm);
+            while (cand) {
+                const int L = __builtin_ctzll(cand);
+                cand &= cand - 1;
+                float sc = __shfl(raw, L);
+                const int g = (int)(s.item_base + base + L);
+                const int n = __builtin_amdgcn_readfirstlane(*cnt);
+                if (wave_list_rejects(ls, li, n, K, sc, g)) continue;
+                bool masked = (bms >> L) & 1ull;
+                if (!masked && s.rated_rowptr) masked = wave_is_masked(g, slot, s.rated_rowptr, s.rated_col, nullptr, lane);
+                if (masked) sc = CRH_MASKED_SCORE;
+                wave_list_insert(ls, li, cnt, K, sc, g, lane);
+                tau = wave_list_tau(ls, __builtin_amdgcn_readfirstlane(*cnt), K);
+            }
+        }
+        const int n = __builtin_amdgcn_readfirstlane(*cnt);
+        const int64_t o = (f * S + z) * K;
+        wave_list_store(ls, li, n, K, s.part_score + o, s.part_idx + o, lane);
+    }
+}
+
+// Stage 3b: canonical merge of an uncertified user's slice lists into its output row.
+__global__ __launch_bounds__(256) void screen_fallback_merge_kernel(ScreenArgs s) {
+    __shared__ float lsh[4][32];
+    __shared__ int lih[4][32];
+    __shared__ int cnth[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int K = s.k, S = s.n_slices;
+    const int64_t count = s.stats[5];
+    float* ls = lsh[wv];
+    int* li = lih[wv];
+    int* cnt = &cnth[wv];
+    for (int64_t f = (int64_t)blockIdx.x * 4 + wv; f < count; f += (int64_t)gridDim.x * 4) {
+        if (lane == 0) *cnt = 0;
+        for (int z = 0; z < S; ++z) {
+            const int64_t o = (f * S + z) * K;
+            const float es = lane < K ? s.part_score[o + lane] : CRH_NEG_INF;
+            const int ei = lane < K ? s.part_idx[o + lane] : CRH_PAD_IDX;
+            unsigned long long m = __ballot(lane < K && ei != CRH_PAD_IDX);
+            while (m) {
+                const int L = __builtin_ctzll(m);
+                m &= m - 1;
+                const float sc = __shfl(es, L);
+                const int g = __shfl(ei, L);
+                const int n = __builtin_amdgcn_readfirstlane(*cnt);
+                if (n >= K && !crh_better(sc, g, ls[K - 1], li[K - 1])) break;   // the slice list is sorted: the rest cannot enter
+                wave_list_insert(ls, li, cnt, K, sc, g, lane);
+            }
+        }
+        const int64_t slot = s.fail_list[f];
+        wave_list_store(ls, li, __builtin_amdgcn_readfirstlane(*cnt), K, s.out_score + slot * K, s.out_idx + slot * K, lane);
+    }
+}
+
+}  // namespace
+
+int screen_fallback_slices(int64_t n_items) {
+    const int64_t s = n_items / 4096;
+    return (int)(s < 1 ? 1 : (s > FB_SLICES_MAX ? FB_SLICES_MAX : s));
+}
+
+int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, hipStream_t st) {
+    const int64_t T = (s.n_items + 31) / 32;
+    hipLaunchKernelGGL(screen_maxabs_kernel, dim3(2048), dim3(256), 0, st, s.item_emb, nullptr, s.n_items, s.stats, 0);
+    CRH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(screen_maxabs_kernel, dim3(256), dim3(256), 0, st, s.user_emb, s.users, s.n_users, s.stats, 1);
+    CRH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(screen_items_kernel, dim3((unsigned)(T < 4096 ? T : 4096)), dim3(256), 0, st, s.item_emb, s.n_items, s.bitmap,
+                       s.item_base, packed, s.stats);
+    CRH_HIP(hipGetLastError());
+    const int64_t ub = (s.n_users * 16 + 255) / 256;
+    hipLaunchKernelGGL(screen_users_kernel, dim3((unsigned)(ub < 2048 ? ub : 2048)), dim3(256), 0, st, s.user_emb, s.users, s.n_users,
+                       uh, s.ustat, s.stats);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int launch_screen_certify(const ScreenArgs& s, hipStream_t st) {
+    hipLaunchKernelGGL(screen_certify_kernel, dim3((unsigned)((s.n_users + 3) / 4)), dim3(256), 0, st, s);
+    CRH_HIP(hipGetLastError());
+    // the fallback's grid does not depend on the count (it is on the device): one resident round of the chip
+    hipLaunchKernelGGL(screen_fallback_kernel, dim3(2048), dim3(256), 0, st, s);
+    CRH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(screen_fallback_merge_kernel, dim3(512), dim3(256), 0, st, s);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+}  // namespace crh_score

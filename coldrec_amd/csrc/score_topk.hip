@@ -978,8 +978,81 @@ int64_t seed_route(int esz, int64_t n_users, int64_t n_items, int d) {
     return P;
 }
 
+// The screened route (score_screen.hip): fp16 screen of K' candidates per user by the LDS-DMA kernel, exact
+// rescoring, a per-user certificate, exact fallback for the users without one.  Its workspace, front to back.
+constexpr int SCREEN_KP = 28;                   // K': k <= 28 lists fit beside the DMA kernel's four slots of 256-byte rows
+constexpr int64_t SCREEN_SEED_ITEMS = 8192;     // fp16 prefix ranked first (as the exact headline route seeds its lists)
+int64_t screen_prefix(int64_t n_items) { return n_items >= 8 * SCREEN_SEED_ITEMS ? SCREEN_SEED_ITEMS : 0; }
+// item-range cuts of the stage-1 DMA launch (as plan_splits for a DMA route of 128-user waves, four to a workgroup)
+int screen_splits(int64_t n_users, int64_t n_main, bool seeded) {
+    const int64_t n_wg = ((n_users + 127) / 128 + 3) / 4, T = (n_main + 31) / 32;
+    int s = seeded ? pick_splits_seeded(n_wg, n_main, 256.0) : pick_splits_wg(n_wg, n_main, SCREEN_KP, 256, 18750.0);
+    if (s > T) s = (int)T;
+    return s;
+}
+struct ScreenLayout {
+    size_t stats, ustat, fail, uh, seed, cand, packed, tbits, sync, scratch, need;
+};
+ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P) {
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    ScreenLayout L;
+    L.stats = 0;
+    L.ustat = 256;
+    L.fail = L.ustat + al((size_t)n_users * 3 * sizeof(float));
+    L.uh = L.fail + al((size_t)n_users * sizeof(int32_t));
+    L.seed = L.uh + al((size_t)n_users * 128 * 2);
+    L.cand = L.seed + al((size_t)n_users * SCREEN_KP * 8);
+    L.packed = L.cand + al((size_t)n_users * SCREEN_KP * 8);
+    L.tbits = L.packed + packed_bytes(n_items, 128, 2);
+    L.sync = L.tbits + tbits_bytes(n_items);
+    L.scratch = L.sync + sync_bytes(n_items);
+    // scratch: the stage-1 split lists, the prefix's score block (one 64-user group at the least) and the fallback's slice lists
+    const int S = screen_splits(n_users, n_items - P, P > 0);
+    const size_t lists = S > 1 ? (size_t)S * n_users * SCREEN_KP * 8 : 0;
+    const size_t dense = P > 0 ? (size_t)64 * (size_t)P * sizeof(float) : 0;
+    const size_t part = (size_t)n_users * screen_fallback_slices(n_items) * 20 * 8;
+    L.need = L.scratch + std::max(lists, std::max(dense, part));
+    return L;
+}
+
+// Does a call take the screened route?  ONE predicate for the dispatcher (score_topk_any) and crh_score_topk_screened.
+// CRH_SCORE_SCREEN (read per call): 0 never; 1 (default) fp32 d=128, k <= 20 calls of >= FP32_DMA_FLAG_MAX_ITEMS items that take the
+// DMA kernel in its barrier form today; 2 every fp32 d=128, k <= 20 call (tests); 3 as 2, but no user is certified (every user goes
+// through the exact fallback: a test switch).  Always: n_splits == 0 and a workspace that holds the route's (screen_layout).
+int screen_mode() {
+    const char* e = getenv("CRH_SCORE_SCREEN");
+    return e ? atoi(e) : 1;
+}
+bool screen_route(int esz, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes, bool has_bitmap, int n_splits) {
+    const int mode = screen_mode();
+    if (mode <= 0 || mode > 3 || esz != 4 || d != 128 || k < 1 || k > 20 || n_splits != 0 || n_users <= 0 || n_items <= 0 ||
+        workspace_bytes == 0)
+        return false;
+    if (workspace_bytes < screen_layout(n_users, n_items, screen_prefix(n_items)).need) return false;
+    if (mode >= 2) return true;
+    if (n_items < FP32_DMA_FLAG_MAX_ITEMS) return false;
+    // today's route of the shape (crh_score_topk_route's evaluation): the DMA kernel in its barrier form
+    int64_t P = seed_route(esz, n_users, n_items, d);
+    size_t ws = workspace_bytes;
+    if (P > 0) {
+        const size_t sb = seed_bytes(n_users, k);
+        const size_t stage1 = dense_block_bytes(n_users, P) + packed_bytes(P, d, esz);
+        const size_t stage2 = lists_bytes(n_users, k) + packed_bytes(n_items - P, d, esz);
+        if (workspace_bytes >= sb + std::max(stage1, stage2)) ws = workspace_bytes - sb;
+        else P = 0;
+    }
+    const RoutePlan r = plan_route(esz, n_users, n_items - P, d, k, true, ws, has_bitmap, 0, P > 0);
+    return !r.dense && r.use_dma && r.dma_mode == 3;
+}
+
+int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_users, const float* item_emb, int64_t n_items,
+                        const int64_t* rated_rowptr, const int32_t* rated_col, const uint32_t* cand_bitmap, int k, int64_t item_base,
+                        float* out_score, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream,
+                        void* ev_kernel_start, void* ev_kernel_stop, const char* who);
+
 // esz = 4: fp32 tables, exact fp32 MFMA (canonical fma chain).  esz = 2: fp16 tables, fp32 accumulate.
 // Route of a call (n_splits == 0; a caller that names a split count gets the plain fused selection):
+//   screened: fp32 d=128 catalogues of >= 6 M items (screen_route): fp16 screen + exact rescoring + certificate + exact fallback;
 //   seeded  : a catalogue of >= 65 536 items and either users that do not fill the chip on their own (the unseeded picker
 //             would cut the item range; prefix 1/16 of the catalogue, 4 096 .. 16 384 items) or, fp32, fewer than 2 M items
 //             (prefix 4 096 items): rank the prefix by the dense route, then the fused selection over the rest, lists seeded;
@@ -990,6 +1063,11 @@ int score_topk_any(int esz, const void* user_emb, const int32_t* users, int64_t 
                    const uint32_t* cand_bitmap, int k, int64_t item_base, float* out_score, int32_t* out_idx,
                    void* workspace, size_t workspace_bytes, void* stream, int n_splits, void* ev_kernel_start,
                    void* ev_kernel_stop, const char* who) {
+    if (user_emb && item_emb && out_score && out_idx && workspace &&
+        screen_route(esz, n_users, n_items, d, k, workspace_bytes, cand_bitmap != nullptr, n_splits))
+        return score_topk_screened(reinterpret_cast<const float*>(user_emb), users, n_users, reinterpret_cast<const float*>(item_emb),
+                                   n_items, rated_rowptr, rated_col, cand_bitmap, k, item_base, out_score, out_idx, workspace,
+                                   workspace_bytes, stream, ev_kernel_start, ev_kernel_stop, who);
     // the seeded route's own predicate and prefix (shared with the workspace query: seed_route)
     const int64_t P = n_splits == 0 ? seed_route(esz, n_users, n_items, d) : 0;
     if (P > 0 && user_emb && item_emb && out_score && out_idx && n_users > 0 && k >= 1 && k <= CRH_MAX_K && workspace) {
@@ -1285,6 +1363,159 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
         return crh_merge_topk(a.out_score, a.out_idx, a.n_splits, n_users, k, k, out_score, out_idx, stream);
     return CRH_OK;
 }
+
+// The screened route (see screen_route and score_screen.hip).  No host synchronisation: the fallback reads the count of uncertified
+// users from the device.
+int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_users, const float* item_emb, int64_t n_items,
+                        const int64_t* rated_rowptr, const int32_t* rated_col, const uint32_t* cand_bitmap, int k, int64_t item_base,
+                        float* out_score, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream,
+                        void* ev_kernel_start, void* ev_kernel_stop, const char* who) {
+    CRH_CHECK_ARG(((uintptr_t)user_emb & 15) == 0 && ((uintptr_t)item_emb & 15) == 0, "%s: tables must be 16-byte aligned", who);
+    CRH_CHECK_ARG(rated_rowptr != nullptr || rated_col == nullptr, "%s: rated_col given without rated_rowptr", who);
+    CRH_CHECK_ARG(item_base >= 0 && item_base + n_items < (int64_t)CRH_PAD_IDX, "%s: item ids exceed int32", who);
+    constexpr int KP = SCREEN_KP, D = 128;
+    const int64_t P = screen_prefix(n_items);
+    const ScreenLayout L = screen_layout(n_users, n_items, P);
+    CRH_CHECK_ARG(workspace_bytes >= L.need, "%s: workspace %zu < %zu bytes (screened route)", who, workspace_bytes, L.need);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* ws = reinterpret_cast<char*>(workspace);
+    _Float16* pk = reinterpret_cast<_Float16*>(ws + L.packed);
+    _Float16* uh = reinterpret_cast<_Float16*>(ws + L.uh);
+    float* seed_s = reinterpret_cast<float*>(ws + L.seed);
+    int32_t* seed_i = reinterpret_cast<int32_t*>(seed_s + (size_t)n_users * KP);
+    float* cand_s = reinterpret_cast<float*>(ws + L.cand);
+    int32_t* cand_i = reinterpret_cast<int32_t*>(cand_s + (size_t)n_users * KP);
+    char* scratch = ws + L.scratch;
+    const size_t scratch_b = workspace_bytes - L.scratch;
+
+    ScreenArgs s;
+    s.user_emb = user_emb;
+    s.users = users;
+    s.n_users = n_users;
+    s.item_emb = item_emb;
+    s.n_items = n_items;
+    s.item_base = item_base;
+    s.rated_rowptr = rated_rowptr;
+    s.rated_col = rated_col;
+    s.bitmap = cand_bitmap;
+    s.k = k;
+    s.kp = KP;
+    s.mode = screen_mode();
+    s.cand_score = cand_s;
+    s.cand_idx = cand_i;
+    s.stats = reinterpret_cast<unsigned*>(ws + L.stats);
+    s.ustat = reinterpret_cast<float*>(ws + L.ustat);
+    s.fail_list = reinterpret_cast<int32_t*>(ws + L.fail);
+    s.n_slices = screen_fallback_slices(n_items);
+    s.part_score = reinterpret_cast<float*>(scratch);
+    s.part_idx = reinterpret_cast<int32_t*>(s.part_score + (size_t)n_users * s.n_slices * k);
+    s.out_score = out_score;
+    s.out_idx = out_idx;
+
+    // ---- stage 0: fp16 copies (items packed, users in `users` order) and the norms of the bound
+    CRH_HIP(hipMemsetAsync(s.stats, 0, 256, st));
+    int rc = launch_screen_prep(s, pk, uh, st);
+    if (rc != CRH_OK) return rc;
+    if (ev_kernel_start) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_start), st));
+
+    // ---- stage 1: approximate top-K' on the fp16 copies -- the prefix ranked into seed lists (score block + crh_mask_topk_f32, as
+    // the seeded route does), then the LDS-DMA kernel over the rest
+    ScoreArgs a;
+    a.user_emb = uh;
+    a.users = nullptr;
+    a.n_users = n_users;
+    a.item_emb = nullptr;       // both kernels read the packed copy only
+    a.rated_rowptr = rated_rowptr;
+    a.rated_col = rated_col;
+    a.bitmap = cand_bitmap;
+    a.k = KP;
+    a.ablate = 0;
+    a.wave_clock = nullptr;
+    a.xcd_sync = nullptr;
+    a.sync_window = 0;
+    a.sync_stride = 0;
+    a.dense = nullptr;
+    a.dense_stride = 0;
+    a.user_base = 0;
+    a.seed_score = nullptr;
+    a.seed_idx = nullptr;
+    a.tile_bits = reinterpret_cast<const uint32_t*>(pk);
+    if (P > 0) {
+        const int64_t stride = P;                       // P is a multiple of 32
+        const int upw_pw = users_per_wave(2, D);
+        int64_t chunk = (int64_t)(scratch_b / ((size_t)stride * sizeof(float))) & ~(int64_t)63;
+        if (chunk > n_users) chunk = n_users;
+        a.packed = pk;
+        a.n_items = P;
+        a.item_base = item_base;
+        a.dense = reinterpret_cast<float*>(scratch);
+        a.dense_stride = stride;
+        for (int64_t u0 = 0; u0 < n_users; u0 += chunk) {
+            const int64_t cu = std::min(chunk, n_users - u0);
+            a.user_base = u0;
+            a.n_users = cu;
+            a.n_ugroups = (cu + upw_pw - 1) / upw_pw;
+            a.n_splits = (int)std::max<int64_t>(1, std::min<int64_t>(P / 32, 2048 / a.n_ugroups));
+            a.rated_rowptr = rated_rowptr ? rated_rowptr + u0 : nullptr;
+            rc = launch_score_per_wave(2, D, 2, a, st);
+            if (rc != CRH_OK) return rc;
+            rc = crh_mask_topk_f32(a.dense, cu, P, stride, a.rated_rowptr, rated_col, cand_bitmap, KP, item_base, 0,
+                                   seed_s + u0 * KP, seed_i + u0 * KP, stream);
+            if (rc != CRH_OK) return rc;
+        }
+        a.dense = nullptr;
+        a.dense_stride = 0;
+        a.user_base = 0;
+        a.n_users = n_users;
+        a.rated_rowptr = rated_rowptr;
+        a.seed_score = seed_s;
+        a.seed_idx = seed_i;
+    }
+    const int64_t n_main = n_items - P, T = (n_main + 31) / 32;
+    a.packed = reinterpret_cast<const char*>(pk) + (size_t)(P / 32) * 32 * D * 2;
+    a.n_items = n_main;
+    a.item_base = item_base + P;
+    a.n_ugroups = (n_users + 127) / 128;
+    const int64_t n_wg = (a.n_ugroups + 3) / 4;
+    a.n_splits = screen_splits(n_users, n_main, P > 0);
+    if (a.n_splits == 1) {
+        a.out_score = cand_s;
+        a.out_idx = cand_i;
+    } else {
+        a.out_score = reinterpret_cast<float*>(scratch);
+        a.out_idx = reinterpret_cast<int32_t*>(a.out_score + (size_t)a.n_splits * n_users * KP);
+    }
+    // XCD lockstep of the workgroups (one resident round, no cuts), as score_topk_impl
+    static const int sync_win_raw = CRH_TUNE_ENV("CRH_SCORE_SYNC_WINDOW") ? atoi(CRH_TUNE_ENV("CRH_SCORE_SYNC_WINDOW")) : 128;
+    static const int sync_win = sync_win_raw <= 0 ? 0 : std::max(2, sync_win_raw & ~1);
+    if (sync_win > 0 && a.n_splits == 1 && n_wg <= 256 && n_wg > 8) {
+        const int64_t n_win = (T + 1 + sync_win - 1) / sync_win + 1;
+        if ((size_t)(n_win + 1) * 8 * sizeof(unsigned) <= sync_bytes(n_items)) {
+            a.sync_window = sync_win;
+            a.sync_stride = n_win + 1;
+            a.xcd_sync = reinterpret_cast<unsigned*>(ws + L.sync);
+            CRH_HIP(hipMemsetAsync(a.xcd_sync, 0, (size_t)a.sync_stride * 8 * sizeof(unsigned), st));
+        }
+    }
+    if (cand_bitmap) {
+        uint32_t* tb = reinterpret_cast<uint32_t*>(ws + L.tbits);
+        hipLaunchKernelGGL(tile_bits_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, cand_bitmap, a.item_base, n_main, T, tb);
+        CRH_HIP(hipGetLastError());
+        a.tile_bits = tb;
+    }
+    rc = launch_score_dma(2, D, 3, a, st);
+    if (rc != CRH_OK) return rc;
+    if (a.n_splits > 1) {
+        rc = crh_merge_topk(a.out_score, a.out_idx, a.n_splits, n_users, KP, KP, cand_s, cand_i, stream);
+        if (rc != CRH_OK) return rc;
+    }
+
+    // ---- stages 2 and 3: exact rescoring + certificate, exact fallback of the uncertified users
+    rc = launch_screen_certify(s, st);
+    if (rc != CRH_OK) return rc;
+    if (ev_kernel_stop) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_stop), st));
+    return CRH_OK;
+}
 }  // namespace
 
 // Partial lists of the item-range splits + the fragment-ordered copy of the item shard.  A caller that can
@@ -1346,6 +1577,23 @@ extern "C" int crh_score_topk_route(int elem_bytes, int64_t n_users, int64_t n_i
     if (prefix_items) *prefix_items = P;
     if (picked_splits) *picked_splits = r.dense ? 1 : plan_splits(r, elem_bytes, n_users, n_main, k, n_splits, P > 0);
     return route;
+}
+
+// Does a crh_score_topk_f32[_ex] call of this shape take the screened route?  The dispatcher's own predicate (screen_route); the
+// route code above stays that of the exact stage the shape would take without it.
+extern "C" int crh_score_topk_screened(int elem_bytes, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes,
+                                       int has_bitmap, int n_splits) {
+    return screen_route(elem_bytes, n_users, n_items, d, k, workspace_bytes, has_bitmap != 0, n_splits) ? 1 : 0;
+}
+
+// Uncertified users of the last screened call that used this workspace (a workspace word; waits for `stream`).
+extern "C" int64_t crh_score_topk_uncertified(const void* workspace, void* stream) {
+    CRH_CHECK_ARG(workspace != nullptr, "crh_score_topk_uncertified: NULL workspace");
+    unsigned n = 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    CRH_HIP(hipMemcpyAsync(&n, reinterpret_cast<const unsigned*>(workspace) + 5, sizeof(n), hipMemcpyDeviceToHost, st));
+    CRH_HIP(hipStreamSynchronize(st));
+    return (int64_t)n;
 }
 
 // the scoring kernel of a route as rocprofv3 prints it (prefix of the demangled name)

@@ -385,4 +385,33 @@ __attribute__((visibility("hidden"))) int launch_score_dma(int esz, int d, int m
 __attribute__((visibility("hidden"))) size_t score_dma_lds_bytes(int row_bytes, int k, int ring_slots, bool flags);
 __attribute__((visibility("hidden"))) int score_dma_ring_slots(int esz, int d, int k, int mode);
 
+// score_screen.hip: stages 0, 2 and 3 of the screened route (fp16 screen + exact rescoring + certificate; see that file)
+struct ScreenArgs {
+    const float* user_emb;        // fp32 tables as the caller passed them
+    const int32_t* users;
+    int64_t n_users;
+    const float* item_emb;        // rows [item_base, item_base + n_items)
+    int64_t n_items;
+    int64_t item_base;
+    const int64_t* rated_rowptr;
+    const int32_t* rated_col;
+    const uint32_t* bitmap;
+    int k;
+    int kp;                       // candidates per user (K')
+    int mode;                     // CRH_SCORE_SCREEN: 3 = certify no user
+    const float* cand_score;      // [n_users][kp] the fp16 kernel's lists (scaled scores, canonical order)
+    const int32_t* cand_idx;
+    unsigned* stats;              // [0] max|v| [1] max|u| (float bits) [2] R [3] N [4] N^ [5] uncertified users
+    float* ustat;                 // [n_users][3] |u|, |u^|, |u - u^|
+    int32_t* fail_list;           // [n_users] slots of the uncertified users (stats[5] of them)
+    float* part_score;            // [n_users][n_slices][k] the fallback's slice lists
+    int32_t* part_idx;
+    int n_slices;
+    float* out_score;             // [n_users][k]
+    int32_t* out_idx;
+};
+__attribute__((visibility("hidden"))) int screen_fallback_slices(int64_t n_items);
+__attribute__((visibility("hidden"))) int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, hipStream_t st);
+__attribute__((visibility("hidden"))) int launch_screen_certify(const ScreenArgs& s, hipStream_t st);
+
 }  // namespace crh_score

@@ -688,10 +688,10 @@ int score_dma_ring_slots(int esz, int d, int k, int mode) {
 }
 
 // 512-byte rows (fp32 d=128: the headline; fp16 d=256: configs[4]) and 256-byte rows (fp32 d=64: the reference's default
-// width, main.py:97 --emb_size 64 = configs[0]): half the tile, half the B registers, the same loop.  mode: 2 = the flag form
-// (fp32 d=128 only), anything else the barrier form.
+// width, main.py:97 --emb_size 64 = configs[0]; fp16 d=128: the screen of the screened route, score_screen.hip): half the tile,
+// half the B registers, the same loop.  mode: 2 = the flag form (fp32 d=128 only), anything else the barrier form.
 int launch_score_dma(int esz, int d, int mode, const ScoreArgs& a, hipStream_t stream) {
-    if (esz == 2) return launch_score_dma_t<_Float16, 256, 4, false>(a, stream);
+    if (esz == 2) return d == 128 ? launch_score_dma_t<_Float16, 128, 4, false>(a, stream) : launch_score_dma_t<_Float16, 256, 4, false>(a, stream);
     if (d == 64) return launch_score_dma_t<float, 64, 4, false>(a, stream);
     return mode == 2 ? launch_score_dma_t<float, 128, 4, true>(a, stream) : launch_score_dma_t<float, 128, 4, false>(a, stream);
 }

@@ -130,8 +130,9 @@ def score_topk_route(n_users: int, n_items: int, d: int, k: int, half: bool = Fa
                      n_splits: int = 0, pack: bool = True) -> dict:
     """Which kernels ``score_topk`` runs for a block of this shape: the library's own answer (crh_score_topk_route evaluates
     the dispatcher's predicates under the current environment switches; no GPU needed), with the workspace ``score_topk``
-    would pass.  ``{"route", "seeded", "dma_form", "prefix_items", "n_splits", "kernel", "code"}``; ``kernel`` is the scoring kernel's
-    name as rocprofv3 prints it."""
+    would pass.  ``{"route", "seeded", "dma_form", "prefix_items", "n_splits", "kernel", "code", "screened"}``; ``kernel`` is the scoring
+    kernel's name as rocprofv3 prints it; ``screened``: the call takes the screened route (fp16 screen, exact rescoring and
+    certificate, exact fallback; crh_score_topk_screened), and route / kernel / code describe the exact route it replaces."""
     import ctypes
     L = _lib.lib()
     d = d if d % 8 == 0 and (L.crh_score_topk_f16_supports_dim(d) if half else L.crh_score_topk_supports_dim(d)) else \
@@ -142,9 +143,24 @@ def score_topk_route(n_users: int, n_items: int, d: int, k: int, half: bool = Fa
     code = L.crh_score_topk_route(2 if half else 4, n_users, n_items, d, k, ws_bytes, 1 if has_bitmap else 0, n_splits,
                                   ctypes.byref(prefix), ctypes.byref(splits))
     _lib.check(code if code < 0 else 0, "crh_score_topk_route")
+    screened = bool(L.crh_score_topk_screened(2 if half else 4, n_users, n_items, d, k, ws_bytes, 1 if has_bitmap else 0, n_splits))
     return {"route": ROUTE_NAMES[code & 15], "seeded": bool(code & 16), "dma_form": ("flags" if code & 32 else "barrier") if (code & 15) == 4 else None,
             "prefix_items": int(prefix.value),
-            "n_splits": int(splits.value), "kernel": L.crh_score_topk_route_kernel(code).decode(), "code": int(code)}
+            "n_splits": int(splits.value), "kernel": L.crh_score_topk_route_kernel(code).decode(), "code": int(code),
+            "screened": screened}
+
+
+def score_topk_uncertified(device=None) -> int:
+    """Users the last screened ``score_topk`` call on this device and stream could not certify (they took the exact fallback).
+    Synchronises the stream; only meaningful right after a call that ``score_topk_route(...)["screened"]`` reports."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    key = (dev.type, dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    buf = _ws_cache.get(key)
+    if buf is None:
+        raise RuntimeError("score_topk_uncertified: no scoring workspace on this stream")
+    n = _lib.lib().crh_score_topk_uncertified(_lib.ptr(buf), _lib.current_stream())
+    _lib.check(n if n < 0 else 0, "crh_score_topk_uncertified")
+    return int(n)
 
 
 def mask_topk(scores: torch.Tensor, k: int, rated_rowptr=None, rated_col=None, cand_bitmap=None,

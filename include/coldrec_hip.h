@@ -89,6 +89,19 @@ int crh_score_topk_route(int elem_bytes, int64_t n_users, int64_t n_items, int d
                          int has_bitmap, int n_splits, int64_t* prefix_items, int* picked_splits);
 /* kernel-name prefix of a route's scoring kernel as rocprofv3 prints it ("score_topk_dma_kernel", ...) */
 const char* crh_score_topk_route_kernel(int route);
+/* The SCREENED route of fp32 d=128 calls with k <= 20 (the headline shape): the catalogue is ranked in fp16 by the LDS-DMA kernel
+ * into 28 candidates per user, the candidates are rescored with the canonical fmaf chain, and a per-user error bound proves that
+ * no other item can enter the top-k; users without that proof are ranked by an exact fallback.  Results are identical to the
+ * exact route's.  CRH_SCORE_SCREEN (read per call): 0 never, 1 (default) calls of >= 6 M items that the DMA kernel's barrier form
+ * would rank, 2 every fp32 d=128 call with k <= 20, 3 as 2 with no user certified (test switch); n_splits must be 0 and the
+ * workspace must hold the route's buffers (the full workspace of these shapes does).
+ * crh_score_topk_screened: 1 if a call of this shape (arguments as crh_score_topk_route) takes the screened route, else 0;
+ * crh_score_topk_route still reports the exact route the shape takes without it.
+ * crh_score_topk_uncertified: the uncertified-user count of the last screened call on this workspace (synchronises `stream`;
+ * for tests and measurements). */
+int crh_score_topk_screened(int elem_bytes, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes,
+                            int has_bitmap, int n_splits);
+int64_t crh_score_topk_uncertified(const void* workspace, void* stream);
 int crh_score_topk_f32(const float* user_emb, const int32_t* users, int64_t n_users,
                        const float* item_emb, int64_t n_items, int d,
                        const int64_t* rated_rowptr, const int32_t* rated_col,
