@@ -87,6 +87,9 @@ SIGNATURES = {
     "crh_l2_workspace_bytes": (_sz, []),
     "crh_l2_norm_f32": (_i32, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "crh_l2_reg_bwd_f32": (_i32, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _i32, _vp]),
+    "crh_infonce_workspace_bytes": (_sz, [_i64, _i32]),
+    "crh_infonce_splits": (_i32, [_i64]),
+    "crh_infonce_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "crh_comm_unique_id": (_i32, [_vp]),
     "crh_comm_init": (_vp, [_i32, _i32, _vp]),
     "crh_comm_destroy": (_i32, [_vp]),

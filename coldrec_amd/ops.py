@@ -756,3 +756,72 @@ def spmm_csr(rowptr, col, val, x, y=None, acc_in=None, s_in: float = 1.0, acc_ou
                                      _lib.ptr(ws), ws.numel() * 4 if ws is not None else 0,
                                      _lib.current_stream())
     _lib.check(rc, "crh_spmm_csr_f32")
+
+
+# ---- contrastive learning (infonce.hip) ------------------------------------------------------------------------------
+
+def infonce_workspace_bytes(n_max: int, d: int) -> int:
+    return int(_lib.lib().crh_infonce_workspace_bytes(int(n_max), int(d)))
+
+
+def infonce_workspace(n_max: int, d: int, device) -> torch.Tensor:
+    """Private scratch of one crh_infonce_f32 shape (the caching allocator hands out 512-byte aligned blocks)."""
+    return torch.empty(max(infonce_workspace_bytes(n_max, d), 1), dtype=torch.uint8, device=device)
+
+
+def infonce(view1: torch.Tensor, view2: torch.Tensor, tau: float, b_cos: bool = True, rows1=None, rows2=None, n_dev=None,
+            n_max: Optional[int] = None, scale: float = 1.0, accumulate: bool = False, grad1=None, grad2=None, loss=None,
+            workspace=None, want_grad1: bool = True, want_grad2: bool = True):
+    """InfoNCE loss and both input gradients in one call (crh_infonce_f32).  view1 / view2: fp32 contiguous (rows, d),
+    d % 4 == 0 <= 256 (``util.utils.InfoNCE`` pads other widths); rows1 / rows2: optional unique int32 row ids (the batch is
+    view[rows[:N]]), n_dev: optional device int32 N.  Returns (loss, grad1, grad2); grad* = d loss / d view * scale,
+    written (or added, ``accumulate``) at the batch's rows only.  A gradient that is neither given nor wanted is not
+    computed (None is returned for it; without grad2 the column pass is skipped)."""
+    _need_cuda(view1, view2, rows1, rows2, n_dev, grad1, grad2, loss, workspace)
+    dev = view1.device
+    for v in (view1, view2):
+        if v.dtype != torch.float32 or not v.is_contiguous() or v.dim() != 2:
+            raise RuntimeError("infonce: views must be contiguous 2-D float32 tensors")
+    if view1.shape[1] != view2.shape[1]:
+        raise RuntimeError("infonce: views differ in width")
+    for t in (view2, rows1, rows2, n_dev, grad1, grad2, loss, workspace):
+        if t is not None and t.device != dev:
+            raise RuntimeError("infonce: every tensor must be on the views' device")
+    for r in (rows1, rows2):
+        if r is not None and (r.dtype != torch.int32 or not r.is_contiguous() or r.dim() != 1):
+            raise RuntimeError("infonce: row ids must be contiguous 1-D int32")
+    if n_dev is not None and (n_dev.dtype != torch.int32 or n_dev.numel() < 1):
+        raise RuntimeError("infonce: n_dev must be a device int32 scalar")
+    if loss is not None and (loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 1):
+        raise RuntimeError("infonce: loss must be a contiguous float32 buffer of at least one element")
+    d = view1.shape[1]
+    if n_max is None:
+        n_max = rows1.shape[0] if rows1 is not None else view1.shape[0]
+    if rows1 is None and view1.shape[0] < n_max or rows2 is None and view2.shape[0] < n_max \
+            or rows1 is not None and rows1.shape[0] < n_max or rows2 is not None and rows2.shape[0] < n_max:
+        raise RuntimeError("infonce: fewer rows than n_max")
+
+    def grad_buffer(g, v, rows, want):
+        if g is None:
+            if not want:
+                return None
+            # every row is overwritten only when the batch is the whole view; otherwise untouched rows must read zero
+            whole = rows is None and n_dev is None and not accumulate and v.shape[0] == n_max
+            return torch.empty_like(v) if whole else torch.zeros_like(v)
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != v.shape:
+            raise RuntimeError("infonce: gradient buffers must be contiguous float32 tensors of the views' shapes")
+        return g
+
+    grad1 = grad_buffer(grad1, view1, rows1, want_grad1)
+    grad2 = grad_buffer(grad2, view2, rows2, want_grad2)
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    if workspace is None:
+        workspace = infonce_workspace(n_max, d, dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise RuntimeError("infonce: workspace must be a contiguous uint8 tensor")
+    _lib.check(_lib.lib().crh_infonce_f32(_lib.ptr(view1), _lib.ptr(rows1), _lib.ptr(view2), _lib.ptr(rows2), _lib.ptr(n_dev),
+                                          int(n_max), int(d), float(tau), int(bool(b_cos)), float(scale), int(bool(accumulate)),
+                                          _lib.ptr(grad1), _lib.ptr(grad2), _lib.ptr(loss), _lib.ptr(workspace),
+                                          workspace.numel(), _lib.current_stream()), "crh_infonce_f32")
+    return loss, grad1, grad2

@@ -6,6 +6,8 @@
   (util/utils.py:160-336), same generator contracts, CPython ``random`` / NumPy streams restated in C++.
 * ``bpr_loss(u, p, n)`` / ``l2_reg_loss(reg, *embs)`` -- differentiable scalars
   (util/utils.py:25-29, 44-48) whose forward and backward run in crh_bpr_fwd_bwd_f32.
+* ``InfoNCE(view1, view2, temperature, b_cos=True)`` -- differentiable scalar (util/utils.py:61-76) whose forward and
+  backward run together in crh_infonce_f32, without the N x N logit matrix.
 * ``set_seed(seed, cuda)`` -- seeds the same three generators (util/utils.py:339-348).
 
 Tensors must live on the GPU: there is no CPU implementation behind these functions.
@@ -176,3 +178,39 @@ def l2_reg_loss(reg, *args):
     for emb in args:
         emb_loss = emb_loss + _L2Fn.apply(emb.reshape(emb.shape[0], -1) if emb.dim() != 2 else emb, 1.0)
     return emb_loss * reg
+
+
+class _InfoNCEFn(torch.autograd.Function):
+    """-mean(diag(log_softmax(normalize(v1) normalize(v2)^T / t))) (util/utils.py:61-76).  crh_infonce_f32 computes the loss
+    and the gradients of the inputs that need one in the forward; the backward scales them by grad_out."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, temperature, b_cos, need1, need2):
+        d = v1.shape[1]
+        a, b = _pad4(v1), _pad4(v2)
+        loss, g1, g2 = ops.infonce(a, b, float(temperature), bool(b_cos), want_grad1=need1, want_grad2=need2)
+        ctx.g = (g1, g2)          # kernel outputs, not inputs: kept as attributes (no version check needed)
+        ctx.d = d
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        d = ctx.d
+        g1, g2 = ctx.g
+        return (None if g1 is None else g1[:, :d] * grad_out, None if g2 is None else g2[:, :d] * grad_out,
+                None, None, None, None)
+
+
+def InfoNCE(view1, view2, temperature: float, b_cos: bool = True):
+    """Average InfoNCE loss of two (N, D) views; gathered, non-contiguous or any-width CUDA tensors.  Gradients are computed
+    only for the views that need one (none under torch.no_grad)."""
+    _check_gpu(view1, view2)
+    if view1.dim() != 2 or view1.shape != view2.shape:
+        raise RuntimeError("InfoNCE: views must be two (N, D) tensors of the same shape")
+    if view1.shape[0] == 0:
+        return (view1.sum() + view2.sum()) * float('nan')               # the reference's mean over no rows
+    if view1.shape[1] > 256:
+        raise RuntimeError("InfoNCE: embedding width %d > 256 is not supported" % view1.shape[1])
+    grad = torch.is_grad_enabled()
+    return _InfoNCEFn.apply(view1, view2, float(temperature), bool(b_cos), grad and view1.requires_grad,
+                            grad and view2.requires_grad)

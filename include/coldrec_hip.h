@@ -461,6 +461,31 @@ int crh_comm_allgather_topk(crh_comm* c, const float* score, const int32_t* idx,
                             void* stream);
 
 /*
+ * InfoNCE of the graph-contrastive models, forward and backward in one call (reference util/utils.py:61-76, called twice
+ * per batch by model/SimGCL.py:58-59 and model/XSimGCL.py:61-62, and by model/NCL.py:61,64):
+ *     Z1, Z2 = F.normalize(view1), F.normalize(view2)   (b_cos != 0; b_cos = 0 keeps the raw rows)
+ *     S = Z1 Z2^T / tau;  loss = -mean(diag(log_softmax(S, 1)))
+ * without the N x N matrix: two streaming passes over 32 x 32 tiles on v_mfma_f32_32x32x2_f32 (exact fp32), the row
+ * pass with an online max / sum; every reduction in a fixed order (two identical calls give identical bits).
+ *   view1 / view2  fp32 row-major, width d (d % 4 == 0, 4 <= d <= 256); rows1 / rows2 = int32 row ids into them (the batch
+ *                  is view[rows[0..N)]; ids must be unique: gradient rows are scattered back to them), NULL = rows 0..N-1
+ *   n_dev          device int32 N (clamped to [0, n_max]), NULL = n_max; grids are sized from n_max, so a step that
+ *                  computes N on the device needs no host sync
+ *   grad1 / grad2  d loss/d view * scale, at the rows of rows1 / rows2 (or rows 0..N-1); accumulate != 0 adds into them,
+ *                  else those rows are overwritten; no other row is touched.  The normalize backward clamps the norm at
+ *                  1e-12 as torch does (a zero row gets grad / 1e-12).  Either may be NULL (not computed: a NULL grad2
+ *                  skips the column pass); at least one of grad1, grad2, loss_out must be given
+ *   loss_out       device scalar (the unscaled mean), NULL = not written; N = 0 gives 0 and touches no gradient row
+ *   workspace      crh_infonce_workspace_bytes(n_max, d) bytes, 256-byte aligned: zero-padded normalised copies of both
+ *                  views (ceil32(n_max) x ceil32(d) each) plus crh_infonce_splits(n_max) partial tiles of the same size
+ */
+size_t crh_infonce_workspace_bytes(int64_t n_max, int d);
+int crh_infonce_splits(int64_t n_max);
+int crh_infonce_f32(const float* view1, const int32_t* rows1, const float* view2, const int32_t* rows2,
+                    const int32_t* n_dev, int64_t n_max, int d, float tau, int b_cos, float scale, int accumulate,
+                    float* grad1, float* grad2, float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * HOST-side negative sampler reproducing util/utils.py:123-157 (next_batch_pairwise) and NumPy's
  * legacy MT19937 stream bit for bit (np.random.seed / shuffle / choice), on internal ids.
  * All pointers are HOST pointers.  rec_* are the training records in file order; n_items_seen =
