@@ -22,7 +22,7 @@ namespace crh_score {
 namespace {
 
 constexpr int SD = 128;            // row width of the screened route
-constexpr int FB_SLICES_MAX = 64;  // item slices per uncertified user in the fallback
+constexpr int FB_SCRATCH_SLICES = 64;  // slice lists per user the workspace holds for the fallback (screen_fallback_slices)
 
 // a float that is >= x (x >= 0 or NaN); +inf when x is NaN or beyond the float range
 __device__ __forceinline__ float up_float(double x) {
@@ -261,7 +261,27 @@ __global__ __launch_bounds__(256) void screen_certify_kernel(ScreenArgs s) {
     }
 }
 
-// Stage 3a: exact per-(uncertified user, item slice) lists, grid-stride over count x n_slices work items (the count is read
+// Item slices per uncertified user in the fallback, from the count (read on the device by every stage-3 kernel, so they all agree):
+// enough (user x slice) work items to fill one resident round of the chip (FB_WAVES), at least FB_MIN_ITEMS items per slice, at most
+// FB_SLICES_MAX (two merge levels of FB_FANIN), and never more lists than the scratch holds (s.n_slices per user of the call: since
+// count <= n_users, that leaves at least s.n_slices each).  One uncertified user of the headline: 4 096 slices of 2 441 items
+// instead of 64 of 156 250 -- the fallback was a handful of latency-bound waves walking the table.
+constexpr int64_t FB_WAVES = 2048 * 4;   // the fallback's grid: 2 048 workgroups of four waves
+constexpr int64_t FB_MIN_ITEMS = 1024;
+constexpr int FB_FANIN = 64;             // lists merged by one wave per merge level
+constexpr int FB_SLICES_MAX = FB_FANIN * FB_FANIN;
+__device__ __forceinline__ int fb_slices(const ScreenArgs& s, int64_t count) {
+    if (count <= 0) return 1;
+    int64_t S = (FB_WAVES + count - 1) / count;
+    const int64_t by_items = (s.n_items + FB_MIN_ITEMS - 1) / FB_MIN_ITEMS;
+    const int64_t by_scratch = s.n_users * s.n_slices / count;
+    if (S > by_items) S = by_items;
+    if (S > by_scratch) S = by_scratch;
+    if (S > FB_SLICES_MAX) S = FB_SLICES_MAX;
+    return S < 1 ? 1 : (int)S;
+}
+
+// Stage 3a: exact per-(uncertified user, item slice) lists, grid-stride over count x fb_slices work items (the count is read
 // here, on the device).  Semantics of the fused selection's slow path: an item is a candidate when its raw score (a bitmap-masked
 // item scores against a zero row, as in the packed copies) is above the list's threshold; masked candidates enter at -1e9.
 __global__ __launch_bounds__(256) void screen_fallback_kernel(ScreenArgs s) {
@@ -270,8 +290,10 @@ __global__ __launch_bounds__(256) void screen_fallback_kernel(ScreenArgs s) {
     __shared__ int lih[4][32];
     __shared__ int cnth[4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int K = s.k, S = s.n_slices;
-    const int64_t n_work = (int64_t)s.stats[5] * S;
+    const int K = s.k;
+    const int64_t count = s.stats[5];
+    const int S = fb_slices(s, count);
+    const int64_t n_work = count * S;
     float* ls = lsh[wv];
     int* li = lih[wv];
     int* cnt = &cnth[wv];
@@ -322,20 +344,31 @@ __global__ __launch_bounds__(256) void screen_fallback_kernel(ScreenArgs s) {
     }
 }
 
-// Stage 3b: canonical merge of an uncertified user's slice lists into its output row.
-__global__ __launch_bounds__(256) void screen_fallback_merge_kernel(ScreenArgs s) {
+// Stage 3b: canonical merge of an uncertified user's slice lists, FB_FANIN lists per wave and level.  Level 0 merges slices
+// [64 g, 64 g + 64) into the list of slice 64 g; level 1 merges those (slices 0, 64, 128, ...) into the output row.  Whichever
+// level sees every slice of a user in one group (level 0 when fb_slices <= 64) writes the output row; a later level has nothing
+// left to do.  A group's first list is read before its merged list overwrites it, by the same wave: merging in place is safe.
+__global__ __launch_bounds__(256) void screen_fallback_merge_kernel(ScreenArgs s, int level) {
     __shared__ float lsh[4][32];
     __shared__ int lih[4][32];
     __shared__ int cnth[4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int K = s.k, S = s.n_slices;
+    const int K = s.k;
     const int64_t count = s.stats[5];
+    const int S = fb_slices(s, count);
+    const int last = S <= FB_FANIN ? 0 : 1;
+    if (level > last) return;                              // uniform over the grid
+    const int stride = level == 0 ? 1 : FB_FANIN;          // slice distance of the lists merged at this level
+    const int span = stride * FB_FANIN;                     // slices covered by one group
+    const int G = (S + span - 1) / span;                    // groups per user
     float* ls = lsh[wv];
     int* li = lih[wv];
     int* cnt = &cnth[wv];
-    for (int64_t f = (int64_t)blockIdx.x * 4 + wv; f < count; f += (int64_t)gridDim.x * 4) {
+    for (int64_t w = (int64_t)blockIdx.x * 4 + wv; w < count * G; w += (int64_t)gridDim.x * 4) {
+        const int64_t f = w / G;
+        const int z0 = (int)(w % G) * span;
         if (lane == 0) *cnt = 0;
-        for (int z = 0; z < S; ++z) {
+        for (int z = z0; z < z0 + span && z < S; z += stride) {
             const int64_t o = (f * S + z) * K;
             const float es = lane < K ? s.part_score[o + lane] : CRH_NEG_INF;
             const int ei = lane < K ? s.part_idx[o + lane] : CRH_PAD_IDX;
@@ -350,16 +383,23 @@ __global__ __launch_bounds__(256) void screen_fallback_merge_kernel(ScreenArgs s
                 wave_list_insert(ls, li, cnt, K, sc, g, lane);
             }
         }
-        const int64_t slot = s.fail_list[f];
-        wave_list_store(ls, li, __builtin_amdgcn_readfirstlane(*cnt), K, s.out_score + slot * K, s.out_idx + slot * K, lane);
+        const int n = __builtin_amdgcn_readfirstlane(*cnt);
+        if (level == last) {
+            const int64_t slot = s.fail_list[f];
+            wave_list_store(ls, li, n, K, s.out_score + slot * K, s.out_idx + slot * K, lane);
+        } else {
+            const int64_t o = (f * S + z0) * K;
+            wave_list_store(ls, li, n, K, s.part_score + o, s.part_idx + o, lane);
+        }
     }
 }
 
 }  // namespace
 
+// slice lists per user the workspace holds for the fallback (screen_layout; the kernels pick their own count inside it)
 int screen_fallback_slices(int64_t n_items) {
     const int64_t s = n_items / 4096;
-    return (int)(s < 1 ? 1 : (s > FB_SLICES_MAX ? FB_SLICES_MAX : s));
+    return (int)(s < 1 ? 1 : (s > FB_SCRATCH_SLICES ? FB_SCRATCH_SLICES : s));
 }
 
 int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, hipStream_t st) {
@@ -381,11 +421,13 @@ int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, hipS
 int launch_screen_certify(const ScreenArgs& s, hipStream_t st) {
     hipLaunchKernelGGL(screen_certify_kernel, dim3((unsigned)((s.n_users + 3) / 4)), dim3(256), 0, st, s);
     CRH_HIP(hipGetLastError());
-    // the fallback's grid does not depend on the count (it is on the device): one resident round of the chip
-    hipLaunchKernelGGL(screen_fallback_kernel, dim3(2048), dim3(256), 0, st, s);
+    // the fallback's grid does not depend on the count (it is on the device): one resident round of the chip (fb_slices)
+    hipLaunchKernelGGL(screen_fallback_kernel, dim3((unsigned)(FB_WAVES / 4)), dim3(256), 0, st, s);
     CRH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(screen_fallback_merge_kernel, dim3(512), dim3(256), 0, st, s);
-    CRH_HIP(hipGetLastError());
+    for (int level = 0; level < 2; ++level) {
+        hipLaunchKernelGGL(screen_fallback_merge_kernel, dim3(512), dim3(256), 0, st, s, level);
+        CRH_HIP(hipGetLastError());
+    }
     return CRH_OK;
 }
 
