@@ -106,21 +106,105 @@ __device__ __forceinline__ void row_sums(const f32x4& x0, const f32x4& x1, _Floa
 // an upper bound of sqrt(s) for an fp64 sum of squares (its own rounding error is far below the 2^-30 margin)
 __device__ __forceinline__ float up_norm(double s) { return up_float(sqrt(s) * (1.0 + 0x1p-30)); }
 
+// The live-row map of a shard's main range (the global ids [g0, g1), any alignment) under a candidate bitmap: idmap[q] = id of
+// the q-th unmasked item, ascending, so the order of the compacted rows is the order of their ids.  Three small kernels, one
+// bitmap word per thread: per-block counts, their exclusive scan (one block; it also leaves the total in *n_live), the ids.
+constexpr int LIVE_WPB = 256;      // bitmap words per block of the count and id kernels
+
+// unmasked bits of the w-th bitmap word of [g0, g1) (the first and the last word may be partial)
+__device__ __forceinline__ unsigned live_word(const uint32_t* __restrict__ bitmap, int64_t w, int64_t g0, int64_t g1) {
+    const int64_t w0 = g0 >> 5, n_words = ((g1 - 1) >> 5) - w0 + 1;
+    if (w >= n_words) return 0u;
+    unsigned m = ~bitmap[w0 + w];
+    const int64_t lo = (w0 + w) << 5;
+    if (lo < g0) m &= ~0u << (int)(g0 - lo);               // 1 .. 31 bits below the range
+    if (lo + 32 > g1) m &= ~0u >> (int)(lo + 32 - g1);     // 1 .. 31 bits above it
+    return m;
+}
+
+// exclusive sum of v over the block's 256 threads (their order); *total = the block's sum
+__device__ __forceinline__ unsigned block_excl_sum(unsigned v, unsigned* total) {
+    __shared__ unsigned wsum[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();
+    unsigned before = 0;
+    for (int q = 0; q < wv; ++q) before += wsum[q];
+    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(256) void screen_live_count_kernel(const uint32_t* __restrict__ bitmap, int64_t g0, int64_t g1,
+                                                                unsigned* __restrict__ blocksum) {
+    const unsigned c = __popc(live_word(bitmap, (int64_t)blockIdx.x * LIVE_WPB + threadIdx.x, g0, g1));
+    unsigned total;
+    block_excl_sum(c, &total);
+    if (threadIdx.x == 0) blocksum[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void screen_live_scan_kernel(unsigned* __restrict__ blocksum, int64_t n_blocks,
+                                                               unsigned* __restrict__ n_live) {
+    const int64_t per = (n_blocks + 255) / 256;
+    const int64_t lo = threadIdx.x * per < n_blocks ? threadIdx.x * per : n_blocks, hi = lo + per < n_blocks ? lo + per : n_blocks;
+    unsigned sum = 0;
+    for (int64_t q = lo; q < hi; ++q) sum += blocksum[q];
+    unsigned total;
+    unsigned run = block_excl_sum(sum, &total);
+    for (int64_t q = lo; q < hi; ++q) {
+        const unsigned c = blocksum[q];
+        blocksum[q] = run;
+        run += c;
+    }
+    if (threadIdx.x == 0) *n_live = total;
+}
+
+__global__ __launch_bounds__(256) void screen_idmap_kernel(const uint32_t* __restrict__ bitmap, int64_t g0, int64_t g1,
+                                                           const unsigned* __restrict__ blocksum, int32_t* __restrict__ idmap) {
+    const int64_t w = (int64_t)blockIdx.x * LIVE_WPB + threadIdx.x;
+    unsigned m = live_word(bitmap, w, g0, g1);
+    unsigned total;
+    int64_t pos = (int64_t)blocksum[blockIdx.x] + block_excl_sum(__popc(m), &total);
+    const int id0 = (int)(((g0 >> 5) + w) << 5);
+    while (m) {
+        idmap[pos++] = id0 + __builtin_ctz(m);
+        m &= m - 1;
+    }
+}
+
 // Item shard -> fp16 in the fragment-ordered packed layout of pack_items_f16_kernel<128> (tile t, unit c = 8 elements of row r at
 // ((t * 8 + c / 2) * 64 + (c & 1) * 32 + r)), bitmap-masked rows zero; the maxima of |v - v^|, |v|, |v^| over the unmasked rows
 // go to stats[2..4].  Grid-stride over tiles; 16 lanes per row.
+// idmap != NULL (the compacted copy): the first `prefix` rows (a multiple of 32) as above; behind them destination row q is the
+// q-th unmasked item of the main range, shard row idmap[q] - item_base -- still one contiguous 512-byte read per row.  The masked
+// rows are neither read nor written, the rows behind the last live one in its tile are zeros (nobody selects them), and the
+// maxima cover exactly the rows they cover without the compaction.
 __global__ __launch_bounds__(256) void screen_items_kernel(const float* __restrict__ v, int64_t n_items, const uint32_t* __restrict__ bitmap,
-                                                           int64_t item_base, _Float16* __restrict__ packed, unsigned* __restrict__ stats) {
+                                                           int64_t item_base, _Float16* __restrict__ packed, unsigned* __restrict__ stats,
+                                                           int64_t prefix, const int32_t* __restrict__ idmap) {
     const int e = scale_exp(stats, 0);
-    const int64_t T = (n_items + 31) >> 5;
+    const int64_t TP = prefix >> 5, n_live = idmap ? (int64_t)stats[SCREEN_STAT_LIVE] : 0;
+    const int64_t T = idmap ? TP + ((n_live + 31) >> 5) : (n_items + 31) >> 5;
     float mr = 0.0f, mn = 0.0f, mh = 0.0f;
     u32x4* dst = reinterpret_cast<u32x4*>(packed);
     for (int64_t t = blockIdx.x; t < T; t += gridDim.x) {
         for (int p = 0; p < 2; ++p) {
             const int u = threadIdx.x + 256 * p, r = u >> 4, c = u & 15;
             int64_t row = (t << 5) + r;
-            if (row >= n_items) row = n_items - 1;        // the tail tile repeats the last row (as the pack kernels do)
-            const bool masked = bitmap != nullptr && ((bitmap[(item_base + row) >> 5] >> ((item_base + row) & 31)) & 1u);
+            bool masked;
+            if (idmap != nullptr && t >= TP) {
+                const int64_t q = row - prefix;
+                masked = q >= n_live;                     // (n_live >= 1 here)
+                row = (int64_t)idmap[masked ? n_live - 1 : q] - item_base;
+            } else {
+                if (row >= n_items) row = n_items - 1;        // the tail tile repeats the last row (as the pack kernels do)
+                masked = bitmap != nullptr && ((bitmap[(item_base + row) >> 5] >> ((item_base + row) & 31)) & 1u);
+            }
             const float* src = v + row * SD + 8 * c;
             const f32x4 x0 = *reinterpret_cast<const f32x4*>(src), x1 = *reinterpret_cast<const f32x4*>(src + 4);
             _Float16 hv[8];
@@ -402,14 +486,28 @@ int screen_fallback_slices(int64_t n_items) {
     return (int)(s < 1 ? 1 : (s > FB_SCRATCH_SLICES ? FB_SCRATCH_SLICES : s));
 }
 
-int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, hipStream_t st) {
-    const int64_t T = (s.n_items + 31) / 32;
+// block sums of the live-row scan (screen_live_*_kernel): one word per LIVE_WPB bitmap words of the main range
+size_t screen_scan_bytes(int64_t n_main) { return (size_t)((n_main + 31) / 32 / LIVE_WPB + 2) * sizeof(unsigned); }
+
+int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, int64_t prefix, int32_t* idmap, unsigned* scan,
+                       hipStream_t st) {
+    const int64_t T = (s.n_items + 31) / 32;     // (compacted: the upper bound; the kernel walks the live tiles)
     hipLaunchKernelGGL(screen_maxabs_kernel, dim3(2048), dim3(256), 0, st, s.item_emb, nullptr, s.n_items, s.stats, 0);
     CRH_HIP(hipGetLastError());
     hipLaunchKernelGGL(screen_maxabs_kernel, dim3(256), dim3(256), 0, st, s.user_emb, s.users, s.n_users, s.stats, 1);
     CRH_HIP(hipGetLastError());
+    if (idmap != nullptr) {
+        const int64_t g0 = s.item_base + prefix, g1 = s.item_base + s.n_items;
+        const int64_t n_words = ((g1 - 1) >> 5) - (g0 >> 5) + 1, nb = (n_words + LIVE_WPB - 1) / LIVE_WPB;
+        hipLaunchKernelGGL(screen_live_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, s.bitmap, g0, g1, scan);
+        CRH_HIP(hipGetLastError());
+        hipLaunchKernelGGL(screen_live_scan_kernel, dim3(1), dim3(256), 0, st, scan, nb, s.stats + SCREEN_STAT_LIVE);
+        CRH_HIP(hipGetLastError());
+        hipLaunchKernelGGL(screen_idmap_kernel, dim3((unsigned)nb), dim3(256), 0, st, s.bitmap, g0, g1, scan, idmap);
+        CRH_HIP(hipGetLastError());
+    }
     hipLaunchKernelGGL(screen_items_kernel, dim3((unsigned)(T < 4096 ? T : 4096)), dim3(256), 0, st, s.item_emb, s.n_items, s.bitmap,
-                       s.item_base, packed, s.stats);
+                       s.item_base, packed, s.stats, prefix, idmap);
     CRH_HIP(hipGetLastError());
     const int64_t ub = (s.n_users * 16 + 255) / 256;
     hipLaunchKernelGGL(screen_users_kernel, dim3((unsigned)(ub < 2048 ? ub : 2048)), dim3(256), 0, st, s.user_emb, s.users, s.n_users,

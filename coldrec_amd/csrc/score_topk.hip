@@ -991,9 +991,11 @@ int screen_splits(int64_t n_users, int64_t n_main, bool seeded) {
     return s;
 }
 struct ScreenLayout {
-    size_t stats, ustat, fail, uh, seed, cand, packed, tbits, sync, scratch, need;
+    size_t stats, ustat, fail, uh, seed, cand, packed, tbits, sync, idmap, scan, scratch, need;
 };
-ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P) {
+// compact: with the live-row map of the main range (one id per item, rounded up to whole tiles plus the one the id DMA of the
+// last tile may touch) and the block sums of its scan
+ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool compact = false) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     ScreenLayout L;
     L.stats = 0;
@@ -1005,7 +1007,9 @@ ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P) {
     L.packed = L.cand + al((size_t)n_users * SCREEN_KP * 8);
     L.tbits = L.packed + packed_bytes(n_items, 128, 2);
     L.sync = L.tbits + tbits_bytes(n_items);
-    L.scratch = L.sync + sync_bytes(n_items);
+    L.idmap = L.sync + sync_bytes(n_items);
+    L.scan = L.idmap + (compact ? al((size_t)(((n_items - P + 31) / 32 + 1) * 32) * sizeof(int32_t)) : 0);
+    L.scratch = L.scan + (compact ? al(screen_scan_bytes(n_items - P)) : 0);
     // scratch: the stage-1 split lists, the prefix's score block (one 64-user group at the least) and the fallback's slice lists
     const int S = screen_splits(n_users, n_items - P, P > 0);
     const size_t lists = S > 1 ? (size_t)S * n_users * SCREEN_KP * 8 : 0;
@@ -1022,6 +1026,14 @@ ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P) {
 int screen_mode() {
     const char* e = getenv("CRH_SCORE_SCREEN");
     return e ? atoi(e) : 1;
+}
+// CRH_SCORE_SCREEN_COMPACT (read per call): 1 (default) a call with a candidate bitmap streams only the unmasked rows through the
+// fp16 pass (when the workspace holds the map: the route itself is decided without it, so the switch never changes the route);
+// 0 keeps the masked rows in the stream as rows of zeros.
+bool screen_compact(int64_t n_users, int64_t n_items, size_t workspace_bytes, bool has_bitmap) {
+    const char* e = getenv("CRH_SCORE_SCREEN_COMPACT");
+    if (!has_bitmap || (e && atoi(e) == 0)) return false;
+    return workspace_bytes >= screen_layout(n_users, n_items, screen_prefix(n_items), true).need;
 }
 bool screen_route(int esz, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes, bool has_bitmap, int n_splits) {
     const int mode = screen_mode();
@@ -1139,6 +1151,39 @@ int print_wave_timing(unsigned long long* dev, int64_t n_waves, int timing, hipS
                         "%.0f ticks each = %.3f of the loop\n",
                 in_[n_waves / 2], lp_[n_waves / 2], so_[n_waves / 2], ev / (double)n_waves, ev > 0 ? ev_ticks / ev : 0.0,
                 lp_sum > 0 ? ev_ticks / lp_sum : 0.0);
+    return CRH_OK;
+}
+// CRH_SCORE_TIMING of a DMA-kernel launch (score_topk_impl and the screened route's stage 1): per-tile duration histograms of the
+// first 16 workgroups' waves (64 buckets) + [wave][cycles in events, events], printed to stderr after the launch
+int dma_timing_begin(ScoreArgs& a, hipStream_t st) {
+    CRH_HIP(hipMalloc(&a.wave_clock, (size_t)16 * 4 * 66 * 8));
+    CRH_HIP(hipMemsetAsync(a.wave_clock, 0, (size_t)16 * 4 * 66 * 8, st));
+    return CRH_OK;
+}
+int dma_timing_report(ScoreArgs& a, int esz, int d, hipStream_t st) {
+    CRH_HIP(hipStreamSynchronize(st));
+    std::vector<unsigned long long> h((size_t)16 * 4 * 66);
+    CRH_HIP(hipMemcpy(h.data(), a.wave_clock, h.size() * 8, hipMemcpyDeviceToHost));
+    CRH_HIP(hipFree(a.wave_clock));
+    {
+        unsigned long long tk = 0, ne = 0;
+        for (int q = 0; q < 64; ++q) { tk += h[(size_t)16 * 4 * 64 + 2 * q]; ne += h[(size_t)16 * 4 * 64 + 2 * q + 1]; }
+        fprintf(stderr, "[crh dma timing] events: %.0f per wave, %.0f cycles each (tiles with at least one candidate; 64 waves)\n",
+                (double)ne / 64.0, ne ? (double)tk / (double)ne : 0.0);
+    }
+    for (int wv = 0; wv < 4; ++wv) {
+        unsigned long long tot = 0, wsum = 0;
+        std::vector<unsigned long long> b(64, 0);
+        for (int blk = 0; blk < 16; ++blk)
+            for (int q = 0; q < 64; ++q) b[q] += h[((size_t)blk * 4 + wv) * 64 + q];
+        const unsigned long long bw = (esz == 4 ? 512 : 128) >> (d * esz == 256 ? 1 : 0);     // bucket width in cycles per tile
+        for (int q = 0; q < 64; ++q) { tot += b[q]; wsum += b[q] * (q * bw + bw / 2); }
+        fprintf(stderr, "[crh dma timing] wave %d: %llu tiles, mean %.0f cycles; histogram (%llu-cycle buckets from 0):", wv, tot,
+                tot ? (double)wsum / (double)tot : 0.0, bw);
+        for (int q = 0; q < 64; ++q) fprintf(stderr, " %llu", b[q]);
+        fprintf(stderr, "\n");
+    }
+    a.wave_clock = nullptr;
     return CRH_OK;
 }
 #endif
@@ -1297,6 +1342,8 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
         }
     }
     a.tile_bits = reinterpret_cast<const uint32_t*>(a.packed);      // readable filler when there is no candidate bitmap
+    a.idmap = nullptr;
+    a.n_live = nullptr;
     if (use_dma && cand_bitmap) {
         uint32_t* tb = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + tb_off);
         hipLaunchKernelGGL(tile_bits_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, cand_bitmap, item_base, n_items, T, tb);
@@ -1308,9 +1355,9 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
     static const int timing = CRH_PROFILE_ENV("CRH_SCORE_TIMING");
     const int64_t n_waves = a.n_ugroups * a.n_splits;
     if (timing && !use_wg) CRH_HIP(hipMalloc(&a.wave_clock, (size_t)n_waves * 48));   // profile build only: [wave][start,end], [wave][loop start,end], [wave][event ticks,events]
-    if (timing && use_dma) {   // DMA kernel: per-tile duration histograms of the first 16 workgroups' waves (64 buckets of 128 cycles)
-        CRH_HIP(hipMalloc(&a.wave_clock, (size_t)16 * 4 * 66 * 8));    // + [wave][cycles in events, events]
-        CRH_HIP(hipMemsetAsync(a.wave_clock, 0, (size_t)16 * 4 * 66 * 8, st));
+    if (timing && use_dma) {
+        rc = dma_timing_begin(a, st);
+        if (rc != CRH_OK) return rc;
     }
 #endif
     if (ev_kernel_start) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_start), st));
@@ -1331,28 +1378,8 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
     if (ev_kernel_stop) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_stop), st));
 #ifdef CRH_PROFILE
     if (timing && use_dma) {
-        CRH_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> h((size_t)16 * 4 * 66);
-        CRH_HIP(hipMemcpy(h.data(), a.wave_clock, h.size() * 8, hipMemcpyDeviceToHost));
-        CRH_HIP(hipFree(a.wave_clock));
-        {
-            unsigned long long tk = 0, ne = 0;
-            for (int q = 0; q < 64; ++q) { tk += h[(size_t)16 * 4 * 64 + 2 * q]; ne += h[(size_t)16 * 4 * 64 + 2 * q + 1]; }
-            fprintf(stderr, "[crh dma timing] events: %.0f per wave, %.0f cycles each (tiles with at least one candidate; 64 waves)\n",
-                    (double)ne / 64.0, ne ? (double)tk / (double)ne : 0.0);
-        }
-        for (int wv = 0; wv < 4; ++wv) {
-            unsigned long long tot = 0, wsum = 0;
-            std::vector<unsigned long long> b(64, 0);
-            for (int blk = 0; blk < 16; ++blk)
-                for (int q = 0; q < 64; ++q) b[q] += h[((size_t)blk * 4 + wv) * 64 + q];
-            const unsigned long long bw = (esz == 4 ? 512 : 128) >> (d * esz == 256 ? 1 : 0);     // bucket width in cycles per tile
-            for (int q = 0; q < 64; ++q) { tot += b[q]; wsum += b[q] * (q * bw + bw / 2); }
-            fprintf(stderr, "[crh dma timing] wave %d: %llu tiles, mean %.0f cycles; histogram (%llu-cycle buckets from 0):", wv, tot,
-                    tot ? (double)wsum / (double)tot : 0.0, bw);
-            for (int q = 0; q < 64; ++q) fprintf(stderr, " %llu", b[q]);
-            fprintf(stderr, "\n");
-        }
+        rc = dma_timing_report(a, esz, d, st);
+        if (rc != CRH_OK) return rc;
     }
     if (timing && !use_wg) {
         const int trc = print_wave_timing(a.wave_clock, n_waves, timing, st);
@@ -1375,8 +1402,10 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     CRH_CHECK_ARG(item_base >= 0 && item_base + n_items < (int64_t)CRH_PAD_IDX, "%s: item ids exceed int32", who);
     constexpr int KP = SCREEN_KP, D = 128;
     const int64_t P = screen_prefix(n_items);
-    const ScreenLayout L = screen_layout(n_users, n_items, P);
+    const bool compact = screen_compact(n_users, n_items, workspace_bytes, cand_bitmap != nullptr);
+    const ScreenLayout L = screen_layout(n_users, n_items, P, compact);
     CRH_CHECK_ARG(workspace_bytes >= L.need, "%s: workspace %zu < %zu bytes (screened route)", who, workspace_bytes, L.need);
+    int32_t* idmap = compact ? reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + L.idmap) : nullptr;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(workspace);
     _Float16* pk = reinterpret_cast<_Float16*>(ws + L.packed);
@@ -1414,7 +1443,7 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
 
     // ---- stage 0: fp16 copies (items packed, users in `users` order) and the norms of the bound
     CRH_HIP(hipMemsetAsync(s.stats, 0, 256, st));
-    int rc = launch_screen_prep(s, pk, uh, st);
+    int rc = launch_screen_prep(s, pk, uh, P, idmap, reinterpret_cast<unsigned*>(ws + L.scan), st);
     if (rc != CRH_OK) return rc;
     if (ev_kernel_start) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_start), st));
 
@@ -1440,6 +1469,8 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     a.seed_score = nullptr;
     a.seed_idx = nullptr;
     a.tile_bits = reinterpret_cast<const uint32_t*>(pk);
+    a.idmap = nullptr;          // (the prefix is not compacted)
+    a.n_live = nullptr;
     if (P > 0) {
         const int64_t stride = P;                       // P is a multiple of 32
         const int upw_pw = users_per_wave(2, D);
@@ -1497,14 +1528,30 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
             CRH_HIP(hipMemsetAsync(a.xcd_sync, 0, (size_t)a.sync_stride * 8 * sizeof(unsigned), st));
         }
     }
-    if (cand_bitmap) {
+    if (compact) {               // the stream holds the unmasked rows only: no tile bits, the rows' ids instead
+        a.idmap = idmap;
+        a.n_live = s.stats + SCREEN_STAT_LIVE;
+    } else if (cand_bitmap) {
         uint32_t* tb = reinterpret_cast<uint32_t*>(ws + L.tbits);
         hipLaunchKernelGGL(tile_bits_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, cand_bitmap, a.item_base, n_main, T, tb);
         CRH_HIP(hipGetLastError());
         a.tile_bits = tb;
     }
+#ifdef CRH_PROFILE
+    static const int timing = CRH_PROFILE_ENV("CRH_SCORE_TIMING");
+    if (timing) {
+        rc = dma_timing_begin(a, st);
+        if (rc != CRH_OK) return rc;
+    }
+#endif
     rc = launch_score_dma(2, D, 3, a, st);
     if (rc != CRH_OK) return rc;
+#ifdef CRH_PROFILE
+    if (timing) {
+        rc = dma_timing_report(a, 2, D, st);
+        if (rc != CRH_OK) return rc;
+    }
+#endif
     if (a.n_splits > 1) {
         rc = crh_merge_topk(a.out_score, a.out_idx, a.n_splits, n_users, KP, KP, cand_s, cand_i, stream);
         if (rc != CRH_OK) return rc;
@@ -1584,6 +1631,17 @@ extern "C" int crh_score_topk_route(int elem_bytes, int64_t n_users, int64_t n_i
 extern "C" int crh_score_topk_screened(int elem_bytes, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes,
                                        int has_bitmap, int n_splits) {
     return screen_route(elem_bytes, n_users, n_items, d, k, workspace_bytes, has_bitmap != 0, n_splits) ? 1 : 0;
+}
+
+// The screened route's plan for a shape it takes (crh_score_topk_screened): item-range cuts of its fp16 pass, and whether the pass
+// streams only the unmasked rows (CRH_SCORE_SCREEN_COMPACT, a candidate bitmap, a workspace that holds the live-row map).
+extern "C" int crh_score_topk_screen_plan(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap, int* cuts,
+                                          int* compact) {
+    CRH_CHECK_ARG(n_users > 0 && n_items > 0, "crh_score_topk_screen_plan: empty block");
+    const int64_t P = screen_prefix(n_items);
+    if (cuts) *cuts = screen_splits(n_users, n_items - P, P > 0);
+    if (compact) *compact = screen_compact(n_users, n_items, workspace_bytes, has_bitmap != 0) ? 1 : 0;
+    return CRH_OK;
 }
 
 // Uncertified users of the last screened call that used this workspace (a workspace word; waits for `stream`).

@@ -42,6 +42,11 @@ struct ScoreArgs {
     // DMA kernel: per 32-item tile of THIS launch's shard the candidate-bitmap bits of its items (tile_bits_kernel), or --
     // without a bitmap -- any readable memory of at least 4 bytes per tile (never looked at)
     const uint32_t* tile_bits;
+    // DMA kernel over a COMPACTED stream (the screened route's fp16 pass under a candidate bitmap, score_screen.hip): row q of
+    // the packed copy is the q-th unmasked item of the shard, idmap[q] its global id (ascending), *n_live the number of such
+    // rows (on the device; n_items is its upper bound, which the host sized the launch by).  NULL: rows are items.
+    const int32_t* idmap;
+    const unsigned* n_live;
 };
 
 // in : lane (i,0) holds k = 8q+0..3 of row i, lane (i,1) holds k = 8q+4..7
@@ -382,7 +387,7 @@ constexpr int WG_RING = 3;   // item-tile slots in LDS (workgroup kernels)
 // score_topk_dma.hip (built with -mllvm -amdgpu-mfma-vgpr-form): the LDS-DMA workgroup kernel for 512- and 256-byte rows
 // (mode = CRH_SCORE_DMA: 1 default, 3 = barrier form for fp32 too)
 __attribute__((visibility("hidden"))) int launch_score_dma(int esz, int d, int mode, const ScoreArgs& a, hipStream_t stream);
-__attribute__((visibility("hidden"))) size_t score_dma_lds_bytes(int row_bytes, int k, int ring_slots, bool flags);
+__attribute__((visibility("hidden"))) size_t score_dma_lds_bytes(int row_bytes, int k, int ring_slots, bool flags, bool compact = false);
 __attribute__((visibility("hidden"))) int score_dma_ring_slots(int esz, int d, int k, int mode);
 
 // score_screen.hip: stages 0, 2 and 3 of the screened route (fp16 screen + exact rescoring + certificate; see that file)
@@ -401,7 +406,7 @@ struct ScreenArgs {
     int mode;                     // CRH_SCORE_SCREEN: 3 = certify no user
     const float* cand_score;      // [n_users][kp] the fp16 kernel's lists (scaled scores, canonical order)
     const int32_t* cand_idx;
-    unsigned* stats;              // [0] max|v| [1] max|u| (float bits) [2] R [3] N [4] N^ [5] uncertified users
+    unsigned* stats;              // [0] max|v| [1] max|u| (float bits) [2] R [3] N [4] N^ [5] uncertified users [6] live rows (compacted)
     float* ustat;                 // [n_users][3] |u|, |u^|, |u - u^|
     int32_t* fail_list;           // [n_users] slots of the uncertified users (stats[5] of them)
     float* part_score;            // [n_users][n_slices][k] the fallback's slice lists
@@ -411,7 +416,12 @@ struct ScreenArgs {
     int32_t* out_idx;
 };
 __attribute__((visibility("hidden"))) int screen_fallback_slices(int64_t n_items);
-__attribute__((visibility("hidden"))) int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, hipStream_t st);
+// idmap != NULL: the rows behind the first `prefix` items are compacted to the unmasked ones (idmap[q] = global id of the q-th,
+// their number in s.stats[SCREEN_STAT_LIVE]; scan = screen_scan_bytes of scratch words)
+constexpr int SCREEN_STAT_LIVE = 6;
+__attribute__((visibility("hidden"))) size_t screen_scan_bytes(int64_t n_main);
+__attribute__((visibility("hidden"))) int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, int64_t prefix,
+                                                             int32_t* idmap, unsigned* scan, hipStream_t st);
 __attribute__((visibility("hidden"))) int launch_screen_certify(const ScreenArgs& s, hipStream_t st);
 
 }  // namespace crh_score

@@ -14,6 +14,11 @@ constexpr int DMA_NW = 4;           // waves per workgroup (one per SIMD)
 constexpr int DMA_UPW = 128;        // users per wave
 constexpr int TBITS_B = 2 * 64 * 4; // two blocks of 64 tiles' candidate bits
 constexpr int FLAGS_B = 64;         // flag form: ready[<= 8] and done[<= 8] counters of the ring slots
+// compacted stream (CM): the ids of a tile's 32 rows ride the DMA stream in the place of the tile bits.  One 256-byte piece per
+// body carries the ids of tiles j+3 and j+4 into slots (j+3) & 7 and the one behind it (slot 8 only ever takes that second half).
+// When body j issues it every wave has selected tile j-2, and tile j+4 shares a slot with tile j-4: eight slots are enough.
+constexpr int IDS_SLOTS = 8;
+constexpr int IDS_B = (IDS_SLOTS + 1) * 32 * 4;
 
 // per-wave LDS of the DMA kernel: the lists (scores, ids, fill) and a 192-bit membership filter of each user's rated list.
 // The rated-list bounds are read from memory when a candidate's filter says "maybe rated" (rare).  k = 20: 188 bytes per user,
@@ -63,10 +68,12 @@ constexpr bool DMA_ONE_TRIP_F32 = false;
 #else
 constexpr bool DMA_ONE_TRIP_F32 = true;
 #endif
-template <bool ONE_TRIP>
+// CM (compacted stream): row q of the stream is the q-th unmasked item; idv = the ids of this tile's rows (lane l: row l & 31),
+// read from LDS once per event by the caller.  item0 and split_end stay row numbers; there are no masked rows (tb = 0).
+template <bool ONE_TRIP, bool CM>
 __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau_reg, float* ls, int* li, int* cnt, int K,
                                                    int ucol0, int64_t slot0, const ScoreArgs& a, int64_t item0,
-                                                   int64_t split_end, int lane, unsigned tb, const unsigned* rfilter) {
+                                                   int64_t split_end, int lane, unsigned tb, const unsigned* rfilter, int idv) {
     unsigned cm = gt_mask16(acc, tau_reg);
     // bits of this lane's 16 rows: rows (r&3) + 8*(r>>2) + 4*hh <-> bit r.  Masked rows are packed as zeros: with no negative
     // threshold in the group none of them is a candidate, and the bit shuffling (a dozen VALU instructions) is skipped
@@ -96,7 +103,9 @@ __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau
             const int64_t il = item0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
             if (il >= split_end) continue;   // clamped duplicate rows of the tail tile
             float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pick16u(acc, r)), L));
-            const int gi = (int)(a.item_base + il);
+            int gi;
+            if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, (r & 3) + 8 * (r >> 2) + 4 * hh);
+            else gi = (int)(a.item_base + il);
             // one batch of LDS reads: fill, tail entry, filter word
             const unsigned hsh = rated_hash192(gi);
             const int n_raw = cnt[ul];
@@ -202,13 +211,20 @@ __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau
 // R = 4 slots and a prefetch distance of 2 tiles a wave may run (NG - 2) / NG of a tile ahead of the slowest reader and a
 // whole tile ahead of the slowest refiller: several events' worth at fp32 tile times (3.4 / 6.8 us).  fp16 tiles last
 // 0.85 us -- less than a DMA round trip -- so the fp16 kernel keeps the barrier form.
-template <typename T, int D, int R, bool FL>
+//
+// CM = the COMPACTED stream (fp16 d=128: the screened route's pass under a candidate bitmap).  The packed copy holds the unmasked
+// rows only (ScoreArgs::idmap, n_live).  The tile count, the cuts' bounds and the DMA clamp come from *n_live; the host sized the
+// grid, the cuts and the lockstep windows by its upper bound n_items, and every workgroup of a cut walks the same tiles.  A
+// candidate's id comes out of the id slots in LDS (IDS_B, in the place of the tile bits: there is no masked row to tell apart);
+// lists, filters, seeds and the cuts' merge stay in id space.
+template <typename T, int D, int R, bool FL, bool CM = false>
 __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     constexpr int NW = DMA_NW, UW = 4, UPW = DMA_UPW;
     // body j issues the DMA of tile j + PF; in the flag form it publishes its pieces of tile j + PF - 1 (issued one body ago) first:
     // a wave may lead the slowest reader by (NG - 2) / NG of a tile and the slowest refiller by one tile
     constexpr int PF = FL ? 2 : 3;
-    static_assert(R == 4 && (!FL || sizeof(T) == 4), "ring shape");
+    static_assert(R == 4 && (!FL || sizeof(T) == 4) && !(CM && FL), "ring shape");
+    constexpr int SIDE_B = CM ? IDS_B : TBITS_B;        // the tile bits' or the ids' area behind the ring
     constexpr int ROWB = D * (int)sizeof(T);
     constexpr int NCH = ROWB / 32;
     constexpr int TILE_B = NCH * 1024;
@@ -229,20 +245,34 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     const int i = lane & 31, h = lane >> 5;
 
     char* ring = smem;                                  // [R][TILE_B]
-    unsigned* tbits = reinterpret_cast<unsigned*>(smem + R * TILE_B);   // [2][64]
-    unsigned* flags = tbits + TBITS_B / 4;             // FL: ready[R] at 0, done[R] at 8; slots of the prologue's tiles start ready
+    unsigned* tbits = reinterpret_cast<unsigned*>(smem + R * TILE_B);   // [2][64]; CM: [IDS_SLOTS + 1][32] ids
+    unsigned* flags = tbits + SIDE_B / 4;             // FL: ready[R] at 0, done[R] at 8; slots of the prologue's tiles start ready
     if constexpr (FL) {
         // (published by the prologue's barrier.  Tiles 0 .. PF-2 of the prologue start complete; tile PF-1 is bumped by body 0 like
         // every tile after it: the prologue waited for all of them)
         if (threadIdx.x < 16) flags[threadIdx.x] = threadIdx.x < PF - 1 ? (unsigned)NW : 0u;
     }
-    const int64_t NT = (a.n_items + 31) >> 5;
+    int64_t n_rows = a.n_items;                          // rows of the stream
+    if constexpr (CM) n_rows = (int64_t)__builtin_amdgcn_readfirstlane((int)*a.n_live);
+    const int64_t NT = (n_rows + 31) >> 5;
     const int64_t t0 = NT * split / S, t1 = NT * (split + 1) / S;
-    const int64_t split_end = (t1 << 5) < a.n_items ? (t1 << 5) : a.n_items;
+    const int64_t split_end = (t1 << 5) < n_rows ? (t1 << 5) : n_rows;
     const int64_t slot0w = ug * UPW;
+    // ids [lo, hi) of this cut's rows, worked out where they are used (CM: out of the map, which ascends; an empty cut gets an
+    // empty range)
+    auto cut_ids = [&](int& lo, int& hi) __attribute__((always_inline)) {
+        if constexpr (CM) {
+            const int id_end = (int)(a.item_base + a.n_items);
+            lo = (t0 << 5) < n_rows ? a.idmap[t0 << 5] : id_end;
+            hi = (t1 << 5) < n_rows ? a.idmap[t1 << 5] : id_end;
+        } else {
+            lo = (int)(a.item_base + (t0 << 5));
+            hi = (int)(a.item_base + split_end);
+        }
+    };
 
     // ---- this wave's lists
-    char* wl = smem + R * TILE_B + TBITS_B + (FL ? FLAGS_B : 0) + (size_t)wave * dma_wave_lds_bytes(K);
+    char* wl = smem + R * TILE_B + SIDE_B + (FL ? FLAGS_B : 0) + (size_t)wave * dma_wave_lds_bytes(K);
     float* ls = reinterpret_cast<float*>(wl);           // [UPW][K]
     int* li = reinterpret_cast<int*>(ls + UPW * K);      // [UPW][K]
     int* cnt = li + UPW * K;                            // [UPW]
@@ -270,7 +300,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     unsigned* rfilter = reinterpret_cast<unsigned*>(cnt + UPW);      // [UPW][DMA_FW]
     for (int j = lane; j < UPW * DMA_FW; j += 64) rfilter[j] = 0u;
     if (live && a.rated_rowptr) {
-        const int id0 = (int)(a.item_base + (t0 << 5)), id1 = (int)(a.item_base + split_end);
+        int id0, id1;
+        cut_ids(id0, id1);
         const int64_t s1 = slot0w + UPW < a.n_users ? slot0w + UPW : a.n_users;
         const int64_t e0 = a.rated_rowptr[slot0w], e1 = a.rated_rowptr[s1];
         int64_t nxt = a.rated_rowptr[slot0w + 1];   // end of the list of this lane's current user
@@ -351,7 +382,18 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.tile_bits + (unsigned)t),
                                          (__attribute__((address_space(3))) void*)(tbits + (blk & 1) * 64), 4, 0, 0);
     };
-    const bool has_bits = a.bitmap != nullptr;          // without a candidate bitmap tile_bits points at readable filler
+    // CM: the ids of tiles t0 + j and t0 + j + 1 -> slots j & 7 and the next one, one id per lane (clamped like the tiles: valid
+    // addresses, ids nobody reads).  Issued by every wave with every tile, as the tile bits are
+    auto dma_ids = [&](int j) __attribute__((always_inline)) {
+        int t = (int)t0 + j;
+        t = t < n_tiles32 ? t : n_tiles32 - 1;
+        unsigned e = ((unsigned)t << 5) + (unsigned)lane;
+        const unsigned e_max = ((unsigned)n_tiles32 << 5) - 1u;
+        e = e < e_max ? e : e_max;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.idmap + e),
+                                         (__attribute__((address_space(3))) void*)(tbits + (j & (IDS_SLOTS - 1)) * 32), 4, 0, 0);
+    };
+    const bool has_bits = !CM && a.bitmap != nullptr;   // without a candidate bitmap tile_bits points at readable filler
     auto dma_wait_all = [&]() __attribute__((always_inline)) {
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -470,7 +512,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
             // its second half -- into the buffer of the block before, whose last tile was selected at the head of body
             // 64 b, before every wave's barrier of that body (flag form: 32 tiles behind every wave, which are at most R apart)
             if constexpr (!FL && g == BG) {
-                dma_tbits((t0 + j + 32) >> 6);
+                if constexpr (CM) dma_ids(j + 3);
+                else dma_tbits((t0 + j + 32) >> 6);
                 dma_tile(j + 3, s_fill);
                 // one DMA instruction and a few of its address instructions per MFMA gap instead of all of them in one gap
                 // (+0.9 % on the same box: a single wave per SIMD hides about five issue slots per MFMA, not twenty)
@@ -553,11 +596,13 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 #endif
                     const int64_t ts = t0 + j - 1;                                      // the tile being selected
                     const unsigned tb = has_bits ? tbits[((ts >> 6) & 1) * 64 + (ts & 63)] : 0u;
+                    int idv = 0;                     // CM: the selected tile's ids, one LDS read per event (where tb's was)
+                    if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
 #pragma unroll
                     for (int u = 0; u < UW; ++u)
                         if (__ballot(m[u] > tau[u]) != 0ull)
-                            tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a, ts << 5,
-                                               split_end, lane, tb, rfilter);
+                            tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32, CM>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a,
+                                                                                        ts << 5, split_end, lane, tb, rfilter, idv);
                     // the list stores of the inserts are drained HERE: left pending, the compiler parks an lgkmcnt(0) at a
                     // later point of the common path, right behind the fragment reads of the barrier group
                     __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -576,8 +621,13 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     };
 
     if (n_steps > 0) {
-        dma_tbits(t0 >> 6);
-        dma_tbits((t0 >> 6) + 1);
+        if constexpr (CM) {
+            dma_ids(0);                                   // tiles 0 .. 3; body j brings tile j + 3 (and j + 4)
+            dma_ids(2);
+        } else {
+            dma_tbits(t0 >> 6);
+            dma_tbits((t0 >> 6) + 1);
+        }
 #pragma unroll
         for (int p = 0; p < PF; ++p) dma_tile(p, p);
         dma_wait_all();
@@ -647,6 +697,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     }
 #endif
     if (live) {
+        int id_lo, id_hi;
+        cut_ids(id_lo, id_hi);
         for (int j = 0; j < UPW; ++j) {
             const int64_t slot = slot0w + j;
             if (slot >= a.n_users) break;
@@ -654,17 +706,17 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
             const int64_t o = ((int64_t)split * a.n_users + slot) * K;
             if (a.seed_score && S > 1)
                 wave_list_store_range(ls + j * K, li + j * K, n, K, a.out_score + o, a.out_idx + o, lane,
-                                      split == 0 ? INT32_MIN : (int)(a.item_base + (t0 << 5)), (int)(a.item_base + split_end));
+                                      split == 0 ? INT32_MIN : id_lo, id_hi);
             else
                 wave_list_store(ls + j * K, li + j * K, n, K, a.out_score + o, a.out_idx + o, lane);
         }
     }
 }
 
-template <typename T, int D, int R, bool FL>
+template <typename T, int D, int R, bool FL, bool CM = false>
 int launch_score_dma_t(const ScoreArgs& a, hipStream_t stream) {
-    const size_t lds = score_dma_lds_bytes(D * (int)sizeof(T), a.k, R, FL);
-    auto kern = score_topk_dma_kernel<T, D, R, FL>;
+    const size_t lds = score_dma_lds_bytes(D * (int)sizeof(T), a.k, R, FL, CM);
+    auto kern = score_topk_dma_kernel<T, D, R, FL, CM>;
     CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds));
     const int64_t blocks = ((a.n_ugroups + DMA_NW - 1) / DMA_NW) * a.n_splits;
@@ -675,8 +727,8 @@ int launch_score_dma_t(const ScoreArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-size_t score_dma_lds_bytes(int row_bytes, int k, int ring_slots, bool flags) {
-    return (size_t)ring_slots * (row_bytes / 32) * 1024 + TBITS_B + (flags ? FLAGS_B : 0) + DMA_NW * dma_wave_lds_bytes(k);
+size_t score_dma_lds_bytes(int row_bytes, int k, int ring_slots, bool flags, bool compact) {
+    return (size_t)ring_slots * (row_bytes / 32) * 1024 + (compact ? IDS_B : TBITS_B) + (flags ? FLAGS_B : 0) + DMA_NW * dma_wave_lds_bytes(k);
 }
 
 // Ring slots of a launch, 0 = the lists do not fit beside the ring.  (A flag form with EIGHT slots for 256-byte rows -- prefetch
@@ -691,6 +743,10 @@ int score_dma_ring_slots(int esz, int d, int k, int mode) {
 // width, main.py:97 --emb_size 64 = configs[0]; fp16 d=128: the screen of the screened route, score_screen.hip): half the tile,
 // half the B registers, the same loop.  mode: 2 = the flag form (fp32 d=128 only), anything else the barrier form.
 int launch_score_dma(int esz, int d, int mode, const ScoreArgs& a, hipStream_t stream) {
+    if (esz == 2 && d == 128 && a.idmap != nullptr) {     // the compacted stream of the screened route
+        if (score_dma_lds_bytes(d * esz, a.k, 4, false, true) > 160 * 1024) return CRH_ERR_ARG;
+        return launch_score_dma_t<_Float16, 128, 4, false, true>(a, stream);
+    }
     if (esz == 2) return d == 128 ? launch_score_dma_t<_Float16, 128, 4, false>(a, stream) : launch_score_dma_t<_Float16, 256, 4, false>(a, stream);
     if (d == 64) return launch_score_dma_t<float, 64, 4, false>(a, stream);
     return mode == 2 ? launch_score_dma_t<float, 128, 4, true>(a, stream) : launch_score_dma_t<float, 128, 4, false>(a, stream);

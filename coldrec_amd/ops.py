@@ -150,6 +150,18 @@ def score_topk_route(n_users: int, n_items: int, d: int, k: int, half: bool = Fa
             "screened": screened}
 
 
+def score_topk_screen_plan(n_users: int, n_items: int, d: int, k: int, has_bitmap: bool = True) -> dict:
+    """The screened route's plan for a call ``score_topk_route`` reports as screened: ``{"cuts", "compact"}`` -- the item-range
+    cuts of its fp16 pass, and whether that pass streams only the rows the candidate bitmap leaves (CRH_SCORE_SCREEN_COMPACT)."""
+    import ctypes
+    L = _lib.lib()
+    ws_bytes = L.crh_score_topk_workspace_bytes(n_users, n_items, d, k)
+    cuts, compact = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(L.crh_score_topk_screen_plan(n_users, n_items, ws_bytes, 1 if has_bitmap else 0, ctypes.byref(cuts),
+                                            ctypes.byref(compact)), "crh_score_topk_screen_plan")
+    return {"cuts": int(cuts.value), "compact": bool(compact.value)}
+
+
 def score_topk_uncertified(device=None) -> int:
     """Users the last screened ``score_topk`` call on this device and stream could not certify (they took the exact fallback).
     Synchronises the stream; only meaningful right after a call that ``score_topk_route(...)["screened"]`` reports."""

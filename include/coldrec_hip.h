@@ -98,7 +98,11 @@ const char* crh_score_topk_route_kernel(int route);
  * crh_score_topk_screened: 1 if a call of this shape (arguments as crh_score_topk_route) takes the screened route, else 0;
  * crh_score_topk_route still reports the exact route the shape takes without it.
  * crh_score_topk_uncertified: the uncertified-user count of the last screened call on this workspace (synchronises `stream`;
- * for tests and measurements). */
+ * for tests and measurements).
+ * crh_score_topk_screen_plan: for a shape that takes the screened route, the item-range cuts of its fp16 pass and whether that
+ * pass streams only the rows the candidate bitmap leaves (CRH_SCORE_SCREEN_COMPACT, read per call: 1 default, 0 keeps the masked
+ * rows in the stream as zeros; results are identical either way). */
+int crh_score_topk_screen_plan(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap, int* cuts, int* compact);
 int crh_score_topk_screened(int elem_bytes, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes,
                             int has_bitmap, int n_splits);
 int64_t crh_score_topk_uncertified(const void* workspace, void* stream);
