@@ -91,6 +91,8 @@ SIGNATURES = {
     "crh_infonce_workspace_bytes": (_sz, [_i64, _i32]),
     "crh_infonce_splits": (_i32, [_i64]),
     "crh_infonce_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "crh_noise_uniform_f32": (_i32, [_vp, _i64, _i32, ctypes.c_uint64, _vp, _i64, _vp]),
+    "crh_perturb_rows_f32": (_i32, [_vp, _i64, _i32, _f32, _vp, ctypes.c_uint64, _vp, _i64, _vp, _f32, _vp, _f32, _vp]),
     "crh_comm_unique_id": (_i32, [_vp]),
     "crh_comm_init": (_vp, [_i32, _i32, _vp]),
     "crh_comm_destroy": (_i32, [_vp]),

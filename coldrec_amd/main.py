@@ -50,7 +50,7 @@ class Config:
 def model_factory(config):
     cls = AVAILABLE_MODELS.get(config.args.model)
     if cls is None:
-        raise ValueError(f"Invalid model name: {config.args.model}. Available models: {list(AVAILABLE_MODELS.keys())}")
+        raise ValueError(f"Invalid model name: {config.args.model}. Available models: {list(AVAILABLE_MODELS.names())}")
     return cls(config)
 
 

@@ -3,14 +3,25 @@
 Only the hot-path trainers are built in; they are imported lazily so that a missing optional
 dependency of some other plugin can never break ``--model MF``.  A stock ColdRec model file that
 subclasses ``BaseColdStartTrainer`` can be registered with ``register(name, cls)``.
+
+``keys()`` lists the core trainers plus whatever ``register()`` added.  The contrastive trainers (SimGCL, XSimGCL)
+resolve by name through ``[]``, ``.get()`` and ``in`` as well, from a cache of their own: resolving one never changes
+what ``keys()`` reports.  ``names()`` is everything a ``--model`` flag can name.
 """
 import importlib
 
 _BUILTIN = {'MF': ('.MF', 'MF'), 'LightGCN': ('.LightGCN', 'LightGCN'), 'DropoutNet': ('.DropoutNet', 'DropoutNet')}
+_CONTRASTIVE = {'SimGCL': ('.SimGCL', 'SimGCL'), 'XSimGCL': ('.XSimGCL', 'XSimGCL')}
+_contrastive_cache = {}
 
 
 class _Registry(dict):
     def __missing__(self, name):
+        if name in _CONTRASTIVE:                      # kept out of the dict's own storage (see the module docstring)
+            if name not in _contrastive_cache:
+                mod, cls = _CONTRASTIVE[name]
+                _contrastive_cache[name] = getattr(importlib.import_module(mod, __name__), cls)
+            return _contrastive_cache[name]
         if name not in _BUILTIN:
             raise KeyError(name)
         mod, cls = _BUILTIN[name]
@@ -23,8 +34,15 @@ class _Registry(dict):
         except KeyError:
             return default
 
+    def __contains__(self, name):
+        return name in _BUILTIN or name in _CONTRASTIVE or dict.__contains__(self, name)
+
     def keys(self):
         return sorted(set(_BUILTIN) | set(dict.keys(self)))
+
+    def names(self):
+        """Every model name that resolves: core + contrastive + registered."""
+        return sorted(set(_BUILTIN) | set(_CONTRASTIVE) | set(dict.keys(self)))
 
 
 AVAILABLE_MODELS = _Registry()

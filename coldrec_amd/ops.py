@@ -837,3 +837,52 @@ def infonce(view1: torch.Tensor, view2: torch.Tensor, tau: float, b_cos: bool = 
                                           _lib.ptr(grad1), _lib.ptr(grad2), _lib.ptr(loss), _lib.ptr(workspace),
                                           workspace.numel(), _lib.current_stream()), "crh_infonce_f32")
     return loss, grad1, grad2
+
+
+# ---- SimGCL / XSimGCL layer perturbation (perturb.hip) ---------------------------------------------------------------
+
+def _perturb_checks(what: str, y: torch.Tensor, *others) -> None:
+    _need_cuda(y, *others)
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.dim() != 2:
+        raise RuntimeError(f"{what}: the rows must be a contiguous 2-D float32 tensor")
+    for t in others:
+        if t is None:
+            continue
+        if t.device != y.device:
+            raise RuntimeError(f"{what}: every tensor must be on the rows' device")
+        if t.dtype == torch.int64:
+            if t.numel() < 1:
+                raise RuntimeError(f"{what}: draw_dev must be a device int64 scalar")
+        elif t.dtype != torch.float32 or not t.is_contiguous() or t.shape != y.shape:
+            raise RuntimeError(f"{what}: noise and accumulators must be contiguous float32 tensors of the rows' shape")
+
+
+def noise_uniform(n_rows: int, d: int, seed: int, draw: int = 0, draw_dev: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """The (n_rows, d) uniforms in [0, 1) that ``perturb_rows(noise=None)`` generates in registers for the same
+    (seed, draw): Philox4x32-10, see crh_noise_uniform_f32.  ``draw_dev``: optional device int64 added to ``draw``."""
+    if out is None:
+        out = torch.empty((int(n_rows), int(d)), dtype=torch.float32, device=device if device is not None else
+                          (draw_dev.device if draw_dev is not None else 'cuda'))
+    _perturb_checks("noise_uniform", out, draw_dev)
+    if draw_dev is not None and draw_dev.dtype != torch.int64:
+        raise RuntimeError("noise_uniform: draw_dev must be a device int64 scalar")
+    _lib.check(_lib.lib().crh_noise_uniform_f32(_lib.ptr(out), out.shape[0], out.shape[1], int(seed) & (2 ** 64 - 1),
+                                                _lib.ptr(draw_dev), int(draw), _lib.current_stream()),
+               "crh_noise_uniform_f32")
+    return out
+
+
+def perturb_rows(y: torch.Tensor, eps: float, noise: Optional[torch.Tensor] = None, seed: int = 0, draw: int = 0,
+                 draw_dev: Optional[torch.Tensor] = None, acc_in: Optional[torch.Tensor] = None, s_in: float = 1.0,
+                 acc_out: Optional[torch.Tensor] = None, s_out: float = 1.0) -> torch.Tensor:
+    """y += sign(y) * normalize(r, dim=-1) * eps in place (model/SimGCL.py:106-108); acc_out = (acc_in*s_in + y)*s_out.
+    r = ``noise`` (an (n_rows, d) buffer of uniforms) or, without it, the Philox stream of (seed, draw [+ *draw_dev])."""
+    _perturb_checks("perturb_rows", y, noise, acc_in, acc_out, draw_dev)
+    if draw_dev is not None and draw_dev.dtype != torch.int64:
+        raise RuntimeError("perturb_rows: draw_dev must be a device int64 scalar")
+    _lib.check(_lib.lib().crh_perturb_rows_f32(_lib.ptr(y), y.shape[0], y.shape[1], float(eps), _lib.ptr(noise),
+                                               int(seed) & (2 ** 64 - 1), _lib.ptr(draw_dev), int(draw), _lib.ptr(acc_in),
+                                               float(s_in), _lib.ptr(acc_out), float(s_out), _lib.current_stream()),
+               "crh_perturb_rows_f32")
+    return y

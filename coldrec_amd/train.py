@@ -10,6 +10,7 @@ nothing is copied to the host unless the caller asks for the loss.
 from __future__ import annotations
 
 import os
+import zlib
 
 from typing import Optional
 
@@ -560,6 +561,185 @@ class LGCNEngine(_TableState):
             return
         self.k.adam_dense(self.E, self.G, self.M, self.V, self.step_count, lr=self.lr, zero_grad=False,
                           step_scalars=step_scalars)
+
+
+class CLEngine(LGCNEngine):
+    """model/SimGCL.py:16-60,101-113 and model/XSimGCL.py:21-63,106-124 on the LightGCN engine's kernels: the encoder is
+    x_k = A x_{k-1} (+ sign(x_k) * normalize(noise) * eps when perturbed, and the perturbed x_k feeds the next layer), its
+    output mean(x_1..x_L) -- layer 0 is NOT in the mean, the scale is 1/L.
+
+    ``mode='simgcl'``: one clean pass (BPR + the two-term L2 on its rows) and two perturbed passes V1, V2 with
+    cl_rate * (InfoNCE(V1[uu], V2[uu]) + InfoNCE(V1[ii], V2[ii])).  sign() has no gradient and the noise is constant, so all
+    three passes share the backward operator M = (1/L) sum_{k=1..L} A^k (A symmetric): every gradient is accumulated into
+    one table g and ONE Horner chain of L SpMMs gives dE0 = M g -- 3L + L SpMMs per step where autograd runs 6L.
+    ``mode='xsimgcl'``: one perturbed pass; OUT = its mean, CL = its layer ``l_cl`` (1-based); BPR + L2 on OUT,
+    cl_rate * (InfoNCE(OUT[uu], CL[uu]) + InfoNCE(OUT[ii], CL[ii])); with g_f at OUT and g_c at CL,
+    D_L = g_f/L + [L == l_cl] g_c, D_k = g_f/L + [k == l_cl] g_c + A D_{k+1}, dE0 = A D_1.
+
+    ``noise='device'``: the uniforms are generated in registers (Philox4x32-10 keyed by ``seed``, one draw number per
+    perturbed layer); ``noise='host'``: torch.rand((N, d), float32) from the CPU's global generator, once per perturbed
+    layer in the reference's order, uploaded -- the reference's own stream (tests/golden/g19_*).
+    Evaluation (``forward()``) is the clean pass.  ``self.loss`` = [bpr, l2, cl_user, cl_item] (the InfoNCE terms unscaled).
+    The step is launched eagerly (torch.unique sizes the contrastive batches on the host); data parallelism and row
+    sharding are not built for it."""
+
+    def __init__(self, user0, item0, rowptr, col, val, n_layers: int, lr: float, reg: float, device,
+                 optimizer: str = 'adam', mode: str = 'simgcl', eps: float = 0.1, tau: float = 0.2, cl_rate: float = 0.5,
+                 l_cl: int = 1, noise: str = 'device', seed: int = 0):
+        if mode not in ('simgcl', 'xsimgcl'):
+            raise ValueError("CLEngine: mode must be 'simgcl' or 'xsimgcl'")
+        if noise not in ('device', 'host'):
+            raise ValueError("CLEngine: noise must be 'device' or 'host'")
+        if mode == 'xsimgcl' and not (1 <= int(l_cl) <= int(n_layers)):
+            raise ValueError("XSimGCL requires 1 <= l_cl <= layers (contrastive snapshot at GCN layer l_cl); "
+                             f"got l_cl={l_cl}, layers={n_layers}.")
+        super().__init__(user0, item0, rowptr, col, val, n_layers, lr, reg, device, optimizer)
+        if self.d > 256:
+            raise RuntimeError("CLEngine: embedding widths above 256 are not supported by the perturbation / InfoNCE kernels")
+        self.mode, self.eps, self.tau, self.cl_rate, self.l_cl = mode, float(eps), float(tau), float(cl_rate), int(l_cl)
+        self.noise, self.seed, self.draw = noise, int(seed), 0
+        self.loss = torch.zeros(4, dtype=torch.float32, device=self.device)
+        # perturbed means P: V1, V2 (simgcl) / the one pass's mean (xsimgcl); CL and its gradient table (xsimgcl)
+        self.P = [torch.empty_like(self.E) for _ in range(2 if mode == 'simgcl' else 1)]
+        self.CL = torch.empty_like(self.E) if mode == 'xsimgcl' else None
+        self.GC = torch.zeros_like(self.E) if mode == 'xsimgcl' else None
+        # uniforms of one layer: always in host mode; in device mode only for widths with zero-padded columns (the
+        # row norm must run over the logical width)
+        self._noise_buf = torch.zeros_like(self.E) if (noise == 'host' or self.d != self.d_logical) else None
+        self.first_noise_crc = None
+        self._nce_ws, self._nce_cap = None, 0
+        self._l2n = torch.zeros(2, dtype=torch.float32, device=self.device)
+
+    def enable_data_parallel(self, dp: DPContext) -> None:
+        raise RuntimeError("SimGCL / XSimGCL: data-parallel training is not built (single GPU only)")
+
+    def enable_row_sharding(self, dp: DPContext) -> None:
+        raise RuntimeError("SimGCL / XSimGCL: row-sharded propagation is not built (single GPU only)")
+
+    def last_loss(self) -> float:
+        """bpr + l2 + cl_rate * (cl_user + cl_item) of the last step, as the reference prints it (host sync)."""
+        l = self.loss.tolist()
+        return l[0] + l[1] + self.cl_rate * (l[2] + l[3])
+
+    def _layer_noise(self) -> Optional[torch.Tensor]:
+        """The uniforms of the next perturbed layer as a buffer, or None = generate them in registers."""
+        if self.noise == 'host':
+            r = torch.rand((self.E.shape[0], self.d_logical), dtype=torch.float32)     # the reference's rand_like (CPU stream)
+            if self.first_noise_crc is None:                     # parity runs compare it with the reference's first draw
+                self.first_noise_crc = zlib.crc32(r.numpy().tobytes())
+            self._noise_buf[:, : self.d_logical].copy_(r, non_blocking=False)
+            return self._noise_buf
+        if self._noise_buf is None:
+            return None
+        self.k.noise_uniform(self.E.shape[0], self.d, self.seed, draw=self.draw, out=self._noise_buf)
+        self._noise_buf[:, self.d_logical:].zero_()
+        return self._noise_buf
+
+    def _propagate(self, out: torch.Tensor, perturbed: bool = False, cl_out: Optional[torch.Tensor] = None) -> None:
+        c = 1.0 / self.L
+        x = self.E
+        for k in range(self.L):
+            last = k == self.L - 1
+            acc_in = None if k == 0 else out
+            if not perturbed:
+                y = None if last else self.X[k & 1]
+                self.k.spmm_csr(self.rowptr, self.col, self.val, x, y=y, acc_in=acc_in, s_in=1.0, acc_out=out,
+                                s_out=c if last else 1.0, sched=self.sched)
+            else:
+                y = cl_out if (cl_out is not None and k == self.l_cl - 1) else self.X[k & 1]
+                self.k.spmm_csr(self.rowptr, self.col, self.val, x, y=y, sched=self.sched)
+                self.k.perturb_rows(y, self.eps, noise=self._layer_noise(), seed=self.seed, draw=self.draw, acc_in=acc_in,
+                                    s_in=1.0, acc_out=out, s_out=c if last else 1.0)
+                self.draw += 1
+            x = y
+
+    def forward(self):
+        self._propagate(self.OUT)
+        return self._view(self.OUT[: self.user_num]), self._view(self.OUT[self.user_num:])
+
+    def _nce(self, v1, v2, rows, g1, g2, loss) -> None:
+        n, d = int(rows.shape[0]), self.d
+        if self._nce_ws is None or self._nce_cap < n:
+            self._nce_cap = n
+            self._nce_ws = self.k.infonce_workspace(n, d, self.device)
+        self.k.infonce(v1, v2, self.tau, True, rows1=rows, rows2=rows, n_max=n, scale=self.cl_rate, accumulate=True,
+                       grad1=g1, grad2=g2, loss=loss, workspace=self._nce_ws)
+
+    def step(self, user_idx, pos_idx, neg_idx, plan: Optional[torch.Tensor] = None, loss_out=None,
+             step_scalars=None) -> None:
+        """One optimiser step; ``plan`` (ops.build_plans_device) makes the BPR gradient rows deterministic.  ``loss_out``:
+        optional 4-float device buffer for [bpr, l2, cl_user, cl_item]."""
+        U, B = self.user_num, user_idx.shape[0]
+        loss = self.loss if loss_out is None else loss_out
+        g = self.dOUT
+        if not self._dout_clean:
+            g.zero_()
+        uu = torch.unique(user_idx)                                  # sorted, unique, int32 (host sync: sizes the batches)
+        ii = torch.unique(pos_idx) + U                               # table rows of the positives
+        if self.mode == 'simgcl':
+            self._propagate(self.OUT)
+            self._propagate(self.P[0], perturbed=True)
+            self._propagate(self.P[1], perturbed=True)
+            rec, v1, v2, g2 = self.OUT, self.P[0], self.P[1], g
+        else:
+            self._propagate(self.P[0], perturbed=True, cl_out=self.CL)
+            self.GC.zero_()
+            rec, v1, v2, g2 = self.P[0], self.P[0], self.CL, self.GC
+        # bpr_loss on the batch's rows; its l2 term (which covers the negatives too) is switched off ...
+        self.k.bpr_fwd_bwd(rec[:U], rec[U:], rec[U:], user_idx, pos_idx, neg_idx, 0.0, g[:U], g[U:], g[U:], loss,
+                           plan=plan, workspace=self._ws(B))
+        # ... l2_reg_loss(reg, u, p) of the reference: the user and positive rows only.  index_put_(accumulate) sums
+        # duplicate rows in a fixed order (index_add_ uses atomics: two runs would differ in the last bits)
+        ul, pl = user_idx.long(), pos_idx.long() + U
+        for s, idx in enumerate((ul, pl)):
+            rows = rec[idx]
+            self.k.l2_norm(rows, out=self._l2n[s:s + 1])
+            g.index_put_((idx,), self.k.l2_reg_bwd(rows, self.reg, self._l2n[s:s + 1], None), accumulate=True)
+        loss[1:2] = self._l2n.sum() * (self.reg / B)
+        self._nce(v1, v2, uu, g, g2, loss[2:3])
+        self._nce(v1, v2, ii, g, g2, loss[3:4])
+        self._backward_cl(step_scalars)
+
+    def _backward_cl(self, step_scalars) -> None:
+        """dE0 from g (= dOUT) [and g_c] by L SpMMs, then the optimiser step (in the last SpMM's epilogue where built)."""
+        L, c, g, gc = self.L, 1.0 / self.L, self.dOUT, self.GC
+        self.step_count += 1
+        # D_L = c g (+ g_c): kept as (g, pending scale c) unless g_c has to be added to it
+        if gc is not None and self.l_cl == L:
+            gc.add_(g, alpha=c)
+            x, lazy = gc, False
+        else:
+            x, lazy = g, True
+        for k in range(L - 1, 0, -1):                                # D_k = c g + [k == l_cl] g_c + A D_{k+1}
+            dst = self.X[k & 1]
+            self.k.spmm_csr(self.rowptr, self.col, self.val, x, y=None, acc_in=g, s_in=1.0 if lazy else c, acc_out=dst,
+                            s_out=c if lazy else 1.0, sched=self.sched)
+            lazy = False
+            if gc is not None and k == self.l_cl:
+                dst.add_(gc)
+            x = dst
+        s_out = c if lazy else 1.0                                   # dE0 = A D_1
+        if self.fuse_adam:
+            # g is not the gathered operand for L >= 2 (nor for xsimgcl with L == l_cl == 1): the epilogue clears it
+            clear = x is not g
+            self._dout_clean = clear
+            acc_in = g if clear else None                            # read with s_in = 0: only there to be cleared
+            if self.optimizer == 'sgd':
+                self.k.spmm_csr_sgd(self.rowptr, self.col, self.val, x, acc_in, 0.0, self.G if self.keep_grad else None,
+                                    s_out, self.sched, self.E, self.lr, zero_acc_in=clear)
+            else:
+                self.k.spmm_csr_adam(self.rowptr, self.col, self.val, x, acc_in, 0.0, self.G if self.keep_grad else None,
+                                     s_out, self.sched, self.E, self.M, self.V, self.step_count, lr=self.lr,
+                                     step_scalars=step_scalars, zero_acc_in=clear)
+            return
+        self.k.spmm_csr(self.rowptr, self.col, self.val, x, y=None, acc_in=None, s_in=0.0, acc_out=self.G, s_out=s_out,
+                        sched=self.sched)
+        self._dout_clean = False
+        if self.optimizer == 'sgd':
+            self.k.sgd_dense(self.E, self.G, self.lr, zero_grad=False)
+        else:
+            self.k.adam_dense(self.E, self.G, self.M, self.V, self.step_count, lr=self.lr, zero_grad=False,
+                              step_scalars=step_scalars)
 
 
 class EpochRunner:

@@ -490,6 +490,27 @@ int crh_infonce_f32(const float* view1, const int32_t* rows1, const float* view2
                     float* grad1, float* grad2, float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The layer perturbation of SimGCL / XSimGCL (model/SimGCL.py:106-108), in place on one (n_rows, d) fp32 layer output
+ * of the propagation, d % 4 == 0, 4 <= d <= 256, every pointer 16-byte aligned.  Per row, r = the row's d uniforms:
+ *     nrm = max(sqrt(sum r^2), 1e-12)                       (F.normalize's clamp)
+ *     y[c] += (sign(y[c]) * (r[c] / nrm)) * eps             (sign(0) = 0: an exact zero stays zero)
+ *     acc_out = (acc_in * s_in + y_new) * s_out             (only if acc_out != NULL; acc_in NULL = 0, may alias acc_out:
+ *                                                            the layer mean, which must see the perturbed rows)
+ * One lane group of d/4 lanes per row, the norm reduced across its lanes; no LDS, no atomics.  The uniforms:
+ *   noise != NULL  read from that (n_rows, d) buffer (parity with the reference: drawn on the host by torch)
+ *   noise == NULL  Philox4x32-10 in registers: key = (seed lo, seed hi), counter = (g lo, g hi, draw lo, draw hi) with
+ *                  g = row * (d/4) + c/4; output word j belongs to column 4 * (c/4) + j; u = (word >> 8) * 2^-24 in [0, 1);
+ *                  draw = (draw_dev ? *draw_dev : 0) + draw_offset (a device int64, so a captured graph can advance it)
+ * crh_noise_uniform_f32 writes exactly the uniforms the second mode uses (the two modes compare bit for bit).
+ * acc_in without acc_out is an argument error; n_rows == 0 launches nothing.
+ */
+int crh_noise_uniform_f32(float* out, int64_t n_rows, int d, uint64_t seed, const int64_t* draw_dev,
+                          int64_t draw_offset, void* stream);
+int crh_perturb_rows_f32(float* y, int64_t n_rows, int d, float eps, const float* noise, uint64_t seed,
+                         const int64_t* draw_dev, int64_t draw_offset, const float* acc_in, float s_in,
+                         float* acc_out, float s_out, void* stream);
+
+/*
  * HOST-side negative sampler reproducing util/utils.py:123-157 (next_batch_pairwise) and NumPy's
  * legacy MT19937 stream bit for bit (np.random.seed / shuffle / choice), on internal ids.
  * All pointers are HOST pointers.  rec_* are the training records in file order; n_items_seen =
