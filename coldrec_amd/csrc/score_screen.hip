@@ -18,6 +18,8 @@
 
 #include "score_topk_common.h"
 
+#include <hipcub/device/device_radix_sort.hpp>
+
 namespace crh_score {
 namespace {
 
@@ -56,10 +58,18 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // max |x| over the finite entries of rows (rows ? rows[r] : r) of a [*][SD] table -> atomicMax on the float bits of stats[word]
+// KEYS (the item table, rows == NULL): the pass also leaves a 16-bit norm key per row, the high half of the float bits of its
+// sum of squares (fp32, reduced over the 32 consecutive lanes that hold the row; monotone in the norm, about 0.4 % per step).  A
+// row whose sum is not finite -- a NaN or an inf entry, or an overflow -- gets the key of +inf.  The key only orders the fp16 pass
+// (screen_sortkey_kernel); no bound and no certificate reads it.
+constexpr unsigned SCREEN_KEY_NONFINITE = 0x7F80u;
+template <bool KEYS>
 __global__ __launch_bounds__(256) void screen_maxabs_kernel(const float* __restrict__ tab, const int32_t* __restrict__ rows,
-                                                            int64_t n_rows, unsigned* __restrict__ stats, int word) {
+                                                            int64_t n_rows, unsigned* __restrict__ stats, int word,
+                                                            uint16_t* __restrict__ keys) {
     const int64_t n4 = n_rows * (SD / 4);
     float m = 0.0f;
+    // (n4 and the stride are multiples of 32: the 32 lanes of a row run the same trips)
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) {
         const int64_t r = e / (SD / 4);
         const int64_t row = rows ? (int64_t)rows[r] : r;
@@ -68,6 +78,13 @@ __global__ __launch_bounds__(256) void screen_maxabs_kernel(const float* __restr
         for (int c = 0; c < 4; ++c) {
             const float ax = fabsf(x[c]);
             if (ax <= 3.4028235e38f) m = fmaxf(m, ax);     // NaN and inf fail the test: they reach the residuals instead
+        }
+        if constexpr (KEYS) {
+            float ss = x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3];
+#pragma unroll
+            for (int o = 16; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+            if ((threadIdx.x & 31) == 0)
+                keys[r] = (uint16_t)(ss <= 3.4028235e38f ? __float_as_uint(ss) >> 16 : SCREEN_KEY_NONFINITE);
         }
     }
     __shared__ float red[4];
@@ -175,6 +192,23 @@ __global__ __launch_bounds__(256) void screen_idmap_kernel(const uint32_t* __res
         idmap[pos++] = id0 + __builtin_ctz(m);
         m &= m - 1;
     }
+}
+
+// Sort keys of the ordered map: slot q of the ascending map gets the complement of its row's norm key, so that an ascending
+// stable sort streams the rows by descending norm, ascending id inside a key; every slot behind the live rows gets the key that
+// sorts last (a live all-zero row shares it and stays in front of them: the sort is stable), so the live ids fill [0, n_live).
+__global__ __launch_bounds__(256) void screen_sortkey_kernel(const int32_t* __restrict__ idmap, const uint16_t* __restrict__ rowkeys,
+                                                             const unsigned* __restrict__ n_live, int64_t item_base, int64_t n_slots,
+                                                             uint16_t* __restrict__ skeys) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n_slots) return;
+    skeys[q] = q < (int64_t)*n_live ? (uint16_t)~rowkeys[(int64_t)idmap[q] - item_base] : (uint16_t)0xFFFFu;
+}
+
+// the norm keys along a sorted map, for crh_score_topk_screen_map
+__global__ __launch_bounds__(256) void screen_mapkeys_kernel(const uint16_t* __restrict__ skeys, int64_t n, int32_t* __restrict__ out) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < n) out[q] = (int32_t)(uint16_t)~skeys[q];
 }
 
 // Item shard -> fp16 in the fragment-ordered packed layout of pack_items_f16_kernel<128> (tile t, unit c = 8 elements of row r at
@@ -489,22 +523,57 @@ int screen_fallback_slices(int64_t n_items) {
 // block sums of the live-row scan (screen_live_*_kernel): one word per LIVE_WPB bitmap words of the main range
 size_t screen_scan_bytes(int64_t n_main) { return (size_t)((n_main + 31) / 32 / LIVE_WPB + 2) * sizeof(unsigned); }
 
-int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, int64_t prefix, int32_t* idmap, unsigned* scan,
-                       hipStream_t st) {
-    const int64_t T = (s.n_items + 31) / 32;     // (compacted: the upper bound; the kernel walks the live tiles)
-    hipLaunchKernelGGL(screen_maxabs_kernel, dim3(2048), dim3(256), 0, st, s.item_emb, nullptr, s.n_items, s.stats, 0);
+// slots of the live-row map of a main range of n_main items: whole tiles plus the one the id DMA of the last tile may touch
+int64_t screen_map_slots(int64_t n_main) { return ((n_main + 31) / 32 + 1) * 32; }
+
+// Temporary storage reserved for the ordered map's sort of n_slots (16-bit key, id) pairs.  The radix sort asks for its
+// alternate key and id buffers (6 bytes per pair), digit histograms and one look-back word per digit and block (below 2 bytes per
+// pair at any block size it is built with); what it asks for is checked against this when it runs (launch_screen_map).
+size_t screen_sort_bytes(int64_t n_slots) { return (size_t)n_slots * 8 + ((size_t)1 << 20); }
+
+// The live-row map of [item_base + prefix, item_base + n_items): ascending in idmap; with ord also sorted stably by descending
+// norm key into ord->idmap (the keys along it in ord->skeys_out).  No host synchronisation: the sort covers every slot.
+int launch_screen_map(const uint32_t* bitmap, int64_t item_base, int64_t n_items, int64_t prefix, unsigned* n_live, unsigned* scan,
+                      int32_t* idmap, const ScreenOrder* ord, hipStream_t st) {
+    const int64_t g0 = item_base + prefix, g1 = item_base + n_items;
+    const int64_t n_words = ((g1 - 1) >> 5) - (g0 >> 5) + 1, nb = (n_words + LIVE_WPB - 1) / LIVE_WPB;
+    hipLaunchKernelGGL(screen_live_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, bitmap, g0, g1, scan);
     CRH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(screen_maxabs_kernel, dim3(256), dim3(256), 0, st, s.user_emb, s.users, s.n_users, s.stats, 1);
+    hipLaunchKernelGGL(screen_live_scan_kernel, dim3(1), dim3(256), 0, st, scan, nb, n_live);
+    CRH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(screen_idmap_kernel, dim3((unsigned)nb), dim3(256), 0, st, bitmap, g0, g1, scan, idmap);
+    CRH_HIP(hipGetLastError());
+    if (ord == nullptr) return CRH_OK;
+    const int64_t n_slots = screen_map_slots(n_items - prefix);
+    hipLaunchKernelGGL(screen_sortkey_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, st, idmap, ord->rowkeys, n_live,
+                       item_base, n_slots, ord->skeys_in);
+    CRH_HIP(hipGetLastError());
+    size_t need = 0;
+    CRH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, ord->skeys_in, ord->skeys_out, idmap, ord->idmap, (int)n_slots, 0, 16, st));
+    if (need > ord->sort_tmp_bytes) {
+        crh_set_error("screened route: the ordered map's sort asks for %zu bytes of temporary storage, %zu are reserved", need,
+                      ord->sort_tmp_bytes);
+        return CRH_ERR_WS;
+    }
+    need = ord->sort_tmp_bytes;
+    CRH_HIP(hipcub::DeviceRadixSort::SortPairs(ord->sort_tmp, need, ord->skeys_in, ord->skeys_out, idmap, ord->idmap, (int)n_slots, 0, 16, st));
+    return CRH_OK;
+}
+
+int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, int64_t prefix, int32_t* idmap, unsigned* scan,
+                       const ScreenOrder* ord, hipStream_t st) {
+    const int64_t T = (s.n_items + 31) / 32;     // (compacted: the upper bound; the kernel walks the live tiles)
+    if (ord != nullptr)
+        hipLaunchKernelGGL(screen_maxabs_kernel<true>, dim3(2048), dim3(256), 0, st, s.item_emb, nullptr, s.n_items, s.stats, 0, ord->rowkeys);
+    else
+        hipLaunchKernelGGL(screen_maxabs_kernel<false>, dim3(2048), dim3(256), 0, st, s.item_emb, nullptr, s.n_items, s.stats, 0, nullptr);
+    CRH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(screen_maxabs_kernel<false>, dim3(256), dim3(256), 0, st, s.user_emb, s.users, s.n_users, s.stats, 1, nullptr);
     CRH_HIP(hipGetLastError());
     if (idmap != nullptr) {
-        const int64_t g0 = s.item_base + prefix, g1 = s.item_base + s.n_items;
-        const int64_t n_words = ((g1 - 1) >> 5) - (g0 >> 5) + 1, nb = (n_words + LIVE_WPB - 1) / LIVE_WPB;
-        hipLaunchKernelGGL(screen_live_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, s.bitmap, g0, g1, scan);
-        CRH_HIP(hipGetLastError());
-        hipLaunchKernelGGL(screen_live_scan_kernel, dim3(1), dim3(256), 0, st, scan, nb, s.stats + SCREEN_STAT_LIVE);
-        CRH_HIP(hipGetLastError());
-        hipLaunchKernelGGL(screen_idmap_kernel, dim3((unsigned)nb), dim3(256), 0, st, s.bitmap, g0, g1, scan, idmap);
-        CRH_HIP(hipGetLastError());
+        const int rc = launch_screen_map(s.bitmap, s.item_base, s.n_items, prefix, s.stats + SCREEN_STAT_LIVE, scan, idmap, ord, st);
+        if (rc != CRH_OK) return rc;
+        if (ord != nullptr) idmap = ord->idmap;
     }
     hipLaunchKernelGGL(screen_items_kernel, dim3((unsigned)(T < 4096 ? T : 4096)), dim3(256), 0, st, s.item_emb, s.n_items, s.bitmap,
                        s.item_base, packed, s.stats, prefix, idmap);
@@ -514,6 +583,50 @@ int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, int6
                        uh, s.ustat, s.stats);
     CRH_HIP(hipGetLastError());
     return CRH_OK;
+}
+
+// Only the map construction of stage 0, into buffers of its own (crh_score_topk_screen_map; synchronises): map_out and keys_out take
+// n_items - prefix entries each, the first *count of them meaningful.
+int screen_map_only(const uint32_t* bitmap, const float* item_emb, int64_t n_items, int64_t item_base, int64_t prefix, int ordered,
+                    int32_t* map_out, int32_t* keys_out, int64_t* count, hipStream_t st) {
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const int64_t n_main = n_items - prefix, n_slots = screen_map_slots(n_main);
+    const size_t o_scan = 256, o_map = o_scan + al(screen_scan_bytes(n_main)), o_rk = o_map + al((size_t)n_slots * 4),
+                 o_k0 = o_rk + al((size_t)n_items * 2), o_k1 = o_k0 + al((size_t)n_slots * 2), o_m1 = o_k1 + al((size_t)n_slots * 2),
+                 o_tmp = o_m1 + al((size_t)n_slots * 4), total = o_tmp + screen_sort_bytes(n_slots);
+    char* buf = nullptr;
+    CRH_HIP(hipMalloc(reinterpret_cast<void**>(&buf), total));
+    ScreenOrder ord;
+    ord.rowkeys = reinterpret_cast<uint16_t*>(buf + o_rk);
+    ord.skeys_in = reinterpret_cast<uint16_t*>(buf + o_k0);
+    ord.skeys_out = reinterpret_cast<uint16_t*>(buf + o_k1);
+    ord.idmap = reinterpret_cast<int32_t*>(buf + o_m1);
+    ord.sort_tmp = buf + o_tmp;
+    ord.sort_tmp_bytes = screen_sort_bytes(n_slots);
+    unsigned* stats = reinterpret_cast<unsigned*>(buf);
+    int32_t* idmap = reinterpret_cast<int32_t*>(buf + o_map);
+    int rc = CRH_OK;
+    unsigned live = 0;
+    hipError_t e = hipMemsetAsync(buf, 0, 256, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(screen_maxabs_kernel<true>, dim3(2048), dim3(256), 0, st, item_emb, nullptr, n_items, stats, 0, ord.rowkeys);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) rc = launch_screen_map(bitmap, item_base, n_items, prefix, stats + SCREEN_STAT_LIVE, reinterpret_cast<unsigned*>(buf + o_scan), idmap, &ord, st);
+    if (e == hipSuccess && rc == CRH_OK) {
+        // (the unordered map's keys: those of its rows, as the sort received them)
+        hipLaunchKernelGGL(screen_mapkeys_kernel, dim3((unsigned)((n_main + 255) / 256)), dim3(256), 0, st,
+                           ordered ? ord.skeys_out : ord.skeys_in, n_main, keys_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && rc == CRH_OK)
+        e = hipMemcpyAsync(map_out, ordered ? ord.idmap : idmap, (size_t)n_main * 4, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && rc == CRH_OK) e = hipMemcpyAsync(&live, stats + SCREEN_STAT_LIVE, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    CRH_HIP(e);
+    if (rc == CRH_OK) *count = (int64_t)live;
+    return rc;
 }
 
 int launch_screen_certify(const ScreenArgs& s, hipStream_t st) {

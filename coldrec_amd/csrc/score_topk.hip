@@ -991,11 +991,12 @@ int screen_splits(int64_t n_users, int64_t n_main, bool seeded) {
     return s;
 }
 struct ScreenLayout {
-    size_t stats, ustat, fail, uh, seed, cand, packed, tbits, sync, idmap, scan, scratch, need;
+    size_t stats, ustat, fail, uh, seed, cand, packed, tbits, sync, idmap, scan, rowkeys, skeys, idmap2, sorttmp, scratch, need;
 };
 // compact: with the live-row map of the main range (one id per item, rounded up to whole tiles plus the one the id DMA of the
-// last tile may touch) and the block sums of its scan
-ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool compact = false) {
+// last tile may touch: screen_map_slots) and the block sums of its scan; ordered (needs compact): behind them the norm keys of
+// the shard's rows, the sort keys along both maps, the sorted map and the sort's temporary storage
+ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool compact = false, bool ordered = false) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     ScreenLayout L;
     L.stats = 0;
@@ -1008,8 +1009,14 @@ ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool com
     L.tbits = L.packed + packed_bytes(n_items, 128, 2);
     L.sync = L.tbits + tbits_bytes(n_items);
     L.idmap = L.sync + sync_bytes(n_items);
-    L.scan = L.idmap + (compact ? al((size_t)(((n_items - P + 31) / 32 + 1) * 32) * sizeof(int32_t)) : 0);
-    L.scratch = L.scan + (compact ? al(screen_scan_bytes(n_items - P)) : 0);
+    const size_t slots = (size_t)screen_map_slots(n_items - P);
+    L.scan = L.idmap + (compact ? al(slots * sizeof(int32_t)) : 0);
+    L.rowkeys = L.scan + (compact ? al(screen_scan_bytes(n_items - P)) : 0);
+    ordered = ordered && compact;
+    L.skeys = L.rowkeys + (ordered ? al((size_t)n_items * sizeof(uint16_t)) : 0);
+    L.idmap2 = L.skeys + (ordered ? 2 * al(slots * sizeof(uint16_t)) : 0);
+    L.sorttmp = L.idmap2 + (ordered ? al(slots * sizeof(int32_t)) : 0);
+    L.scratch = L.sorttmp + (ordered ? al(screen_sort_bytes((int64_t)slots)) : 0);
     // scratch: the stage-1 split lists, the prefix's score block (one 64-user group at the least) and the fallback's slice lists
     const int S = screen_splits(n_users, n_items - P, P > 0);
     const size_t lists = S > 1 ? (size_t)S * n_users * SCREEN_KP * 8 : 0;
@@ -1034,6 +1041,16 @@ bool screen_compact(int64_t n_users, int64_t n_items, size_t workspace_bytes, bo
     const char* e = getenv("CRH_SCORE_SCREEN_COMPACT");
     if (!has_bitmap || (e && atoi(e) == 0)) return false;
     return workspace_bytes >= screen_layout(n_users, n_items, screen_prefix(n_items), true).need;
+}
+// CRH_SCORE_SCREEN_ORDER (read per call): 1 (default) a compacted call whose fp16 pass is ONE cut streams the live rows of the main
+// range by descending norm (ScreenOrder), when the workspace holds the sorted map as well; 0 streams them by ascending id.  With
+// cuts the bounds of a cut come from the ascending map and a count only the device knows, so those calls stay ascending.
+bool screen_ordered(int64_t n_users, int64_t n_items, size_t workspace_bytes, bool has_bitmap) {
+    const char* e = getenv("CRH_SCORE_SCREEN_ORDER");
+    if ((e && atoi(e) == 0) || !screen_compact(n_users, n_items, workspace_bytes, has_bitmap)) return false;
+    const int64_t P = screen_prefix(n_items);
+    if (screen_splits(n_users, n_items - P, P > 0) != 1) return false;
+    return workspace_bytes >= screen_layout(n_users, n_items, P, true, true).need;
 }
 bool screen_route(int esz, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes, bool has_bitmap, int n_splits) {
     const int mode = screen_mode();
@@ -1403,11 +1420,22 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     constexpr int KP = SCREEN_KP, D = 128;
     const int64_t P = screen_prefix(n_items);
     const bool compact = screen_compact(n_users, n_items, workspace_bytes, cand_bitmap != nullptr);
-    const ScreenLayout L = screen_layout(n_users, n_items, P, compact);
+    const bool ordered = screen_ordered(n_users, n_items, workspace_bytes, cand_bitmap != nullptr);
+    const ScreenLayout L = screen_layout(n_users, n_items, P, compact, ordered);
     CRH_CHECK_ARG(workspace_bytes >= L.need, "%s: workspace %zu < %zu bytes (screened route)", who, workspace_bytes, L.need);
     int32_t* idmap = compact ? reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + L.idmap) : nullptr;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(workspace);
+    ScreenOrder ord;
+    if (ordered) {
+        const size_t slots = (size_t)screen_map_slots(n_items - P);
+        ord.rowkeys = reinterpret_cast<uint16_t*>(ws + L.rowkeys);
+        ord.skeys_in = reinterpret_cast<uint16_t*>(ws + L.skeys);
+        ord.skeys_out = reinterpret_cast<uint16_t*>(ws + L.skeys + (L.idmap2 - L.skeys) / 2);
+        ord.idmap = reinterpret_cast<int32_t*>(ws + L.idmap2);
+        ord.sort_tmp = ws + L.sorttmp;
+        ord.sort_tmp_bytes = screen_sort_bytes((int64_t)slots);
+    }
     _Float16* pk = reinterpret_cast<_Float16*>(ws + L.packed);
     _Float16* uh = reinterpret_cast<_Float16*>(ws + L.uh);
     float* seed_s = reinterpret_cast<float*>(ws + L.seed);
@@ -1443,7 +1471,7 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
 
     // ---- stage 0: fp16 copies (items packed, users in `users` order) and the norms of the bound
     CRH_HIP(hipMemsetAsync(s.stats, 0, 256, st));
-    int rc = launch_screen_prep(s, pk, uh, P, idmap, reinterpret_cast<unsigned*>(ws + L.scan), st);
+    int rc = launch_screen_prep(s, pk, uh, P, idmap, reinterpret_cast<unsigned*>(ws + L.scan), ordered ? &ord : nullptr, st);
     if (rc != CRH_OK) return rc;
     if (ev_kernel_start) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_start), st));
 
@@ -1529,7 +1557,7 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
         }
     }
     if (compact) {               // the stream holds the unmasked rows only: no tile bits, the rows' ids instead
-        a.idmap = idmap;
+        a.idmap = ordered ? ord.idmap : idmap;      // (ordered: one cut, the only launch that may stream another order)
         a.n_live = s.stats + SCREEN_STAT_LIVE;
     } else if (cand_bitmap) {
         uint32_t* tb = reinterpret_cast<uint32_t*>(ws + L.tbits);
@@ -1642,6 +1670,29 @@ extern "C" int crh_score_topk_screen_plan(int64_t n_users, int64_t n_items, size
     if (cuts) *cuts = screen_splits(n_users, n_items - P, P > 0);
     if (compact) *compact = screen_compact(n_users, n_items, workspace_bytes, has_bitmap != 0) ? 1 : 0;
     return CRH_OK;
+}
+
+// Would a screened call of this shape stream the live rows of its main range by descending norm (CRH_SCORE_SCREEN_ORDER, read per
+// call: 1 default)?  Needs the compaction, a fp16 pass of one cut and a workspace that holds the sorted map.
+extern "C" int crh_score_topk_screen_ordered(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap) {
+    if (n_users <= 0 || n_items <= 0) return 0;
+    return screen_ordered(n_users, n_items, workspace_bytes, has_bitmap != 0) ? 1 : 0;
+}
+
+// Only the map construction of the screened route's stage 0, for tests: the live-row map of [item_base + prefix, item_base +
+// n_items) under `bitmap` (bits of GLOBAL ids), ordered != 0 sorted as the ordered route streams it, and the norm keys along it.
+// map_out and keys_out (device, int32) take n_items - prefix entries, the first *count of them meaningful.  Allocates its own
+// buffers and synchronises `stream`.
+extern "C" int crh_score_topk_screen_map(const uint32_t* bitmap, const float* item_emb, int64_t n_items, int64_t item_base,
+                                         int64_t prefix, int ordered, int32_t* map_out, int32_t* keys_out, int64_t* count,
+                                         void* stream) {
+    CRH_CHECK_ARG(bitmap && item_emb && map_out && keys_out && count, "crh_score_topk_screen_map: NULL argument");
+    CRH_CHECK_ARG(prefix >= 0 && (prefix & 31) == 0 && n_items > prefix, "crh_score_topk_screen_map: prefix %lld of %lld items",
+                  (long long)prefix, (long long)n_items);
+    CRH_CHECK_ARG(((uintptr_t)item_emb & 15) == 0, "crh_score_topk_screen_map: table must be 16-byte aligned");
+    CRH_CHECK_ARG(item_base >= 0 && item_base + n_items < (int64_t)CRH_PAD_IDX, "crh_score_topk_screen_map: item ids exceed int32");
+    return screen_map_only(bitmap, item_emb, n_items, item_base, prefix, ordered, map_out, keys_out, count,
+                           reinterpret_cast<hipStream_t>(stream));
 }
 
 // Uncertified users of the last screened call that used this workspace (a workspace word; waits for `stream`).

@@ -43,8 +43,9 @@ struct ScoreArgs {
     // without a bitmap -- any readable memory of at least 4 bytes per tile (never looked at)
     const uint32_t* tile_bits;
     // DMA kernel over a COMPACTED stream (the screened route's fp16 pass under a candidate bitmap, score_screen.hip): row q of
-    // the packed copy is the q-th unmasked item of the shard, idmap[q] its global id (ascending), *n_live the number of such
-    // rows (on the device; n_items is its upper bound, which the host sized the launch by).  NULL: rows are items.
+    // the packed copy is the q-th unmasked item of the shard in the map's order, idmap[q] its global id (ascending whenever the
+    // launch has more than one cut; any order with one cut: ScreenOrder), *n_live the number of such rows (on the device;
+    // n_items is its upper bound, which the host sized the launch by).  NULL: rows are items.
     const int32_t* idmap;
     const unsigned* n_live;
 };
@@ -420,8 +421,25 @@ __attribute__((visibility("hidden"))) int screen_fallback_slices(int64_t n_items
 // their number in s.stats[SCREEN_STAT_LIVE]; scan = screen_scan_bytes of scratch words)
 constexpr int SCREEN_STAT_LIVE = 6;
 __attribute__((visibility("hidden"))) size_t screen_scan_bytes(int64_t n_main);
+// The ORDERED map (CRH_SCORE_SCREEN_ORDER; one cut only): the live rows streamed by descending norm key, ascending id inside a key,
+// so that every user's threshold rises early and fewer later rows beat it.  Insertion is order-independent under the canonical
+// key, so lists, certificates and results are those of the ascending map.  Buffers of screen_map_slots(n_main) entries each.
+struct ScreenOrder {
+    uint16_t* rowkeys;            // [n_items] norm key per shard row (screen_maxabs_kernel<true>)
+    uint16_t* skeys_in;           // sort keys along the ascending map
+    uint16_t* skeys_out;          // ... and along the sorted one
+    int32_t* idmap;               // the sorted map
+    void* sort_tmp;               // the sort's temporary storage
+    size_t sort_tmp_bytes;        // >= screen_sort_bytes(slots)
+};
+__attribute__((visibility("hidden"))) int64_t screen_map_slots(int64_t n_main);
+__attribute__((visibility("hidden"))) size_t screen_sort_bytes(int64_t n_slots);
+// ord != NULL (needs idmap): stage 1 and the packed copy follow ord->idmap
 __attribute__((visibility("hidden"))) int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, int64_t prefix,
-                                                             int32_t* idmap, unsigned* scan, hipStream_t st);
+                                                             int32_t* idmap, unsigned* scan, const ScreenOrder* ord, hipStream_t st);
+__attribute__((visibility("hidden"))) int screen_map_only(const uint32_t* bitmap, const float* item_emb, int64_t n_items,
+                                                          int64_t item_base, int64_t prefix, int ordered, int32_t* map_out,
+                                                          int32_t* keys_out, int64_t* count, hipStream_t st);
 __attribute__((visibility("hidden"))) int launch_screen_certify(const ScreenArgs& s, hipStream_t st);
 
 }  // namespace crh_score

@@ -213,7 +213,7 @@ __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau
 // 0.85 us -- less than a DMA round trip -- so the fp16 kernel keeps the barrier form.
 //
 // CM = the COMPACTED stream (fp16 d=128: the screened route's pass under a candidate bitmap).  The packed copy holds the unmasked
-// rows only (ScoreArgs::idmap, n_live).  The tile count, the cuts' bounds and the DMA clamp come from *n_live; the host sized the
+// rows only, in the map's order (ScoreArgs::idmap, n_live).  The tile count, the cuts' bounds and the DMA clamp come from *n_live; the host sized the
 // grid, the cuts and the lockstep windows by its upper bound n_items, and every workgroup of a cut walks the same tiles.  A
 // candidate's id comes out of the id slots in LDS (IDS_B, in the place of the tile bits: there is no masked row to tell apart);
 // lists, filters, seeds and the cuts' merge stay in id space.
@@ -258,13 +258,18 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     const int64_t t0 = NT * split / S, t1 = NT * (split + 1) / S;
     const int64_t split_end = (t1 << 5) < n_rows ? (t1 << 5) : n_rows;
     const int64_t slot0w = ug * UPW;
-    // ids [lo, hi) of this cut's rows, worked out where they are used (CM: out of the map, which ascends; an empty cut gets an
-    // empty range)
+    // ids [lo, hi) of this cut's rows, worked out where they are used (CM: with cuts out of the map, which ascends then, and an
+    // empty cut gets an empty range; one cut holds the whole range, in whatever order the map streams it)
     auto cut_ids = [&](int& lo, int& hi) __attribute__((always_inline)) {
         if constexpr (CM) {
             const int id_end = (int)(a.item_base + a.n_items);
-            lo = (t0 << 5) < n_rows ? a.idmap[t0 << 5] : id_end;
-            hi = (t1 << 5) < n_rows ? a.idmap[t1 << 5] : id_end;
+            if (S == 1) {
+                lo = (int)a.item_base;
+                hi = id_end;
+            } else {
+                lo = (t0 << 5) < n_rows ? a.idmap[t0 << 5] : id_end;
+                hi = (t1 << 5) < n_rows ? a.idmap[t1 << 5] : id_end;
+            }
         } else {
             lo = (int)(a.item_base + (t0 << 5));
             hi = (int)(a.item_base + split_end);

@@ -162,6 +162,34 @@ def score_topk_screen_plan(n_users: int, n_items: int, d: int, k: int, has_bitma
     return {"cuts": int(cuts.value), "compact": bool(compact.value)}
 
 
+def score_topk_screen_ordered(n_users: int, n_items: int, d: int, k: int, has_bitmap: bool = True) -> bool:
+    """Does a screened call of this shape stream the unmasked rows of its main range by descending norm (CRH_SCORE_SCREEN_ORDER)?
+    True when the compaction is on, the fp16 pass is one cut and the workspace ``score_topk`` passes holds the sorted map."""
+    L = _lib.lib()
+    ws_bytes = L.crh_score_topk_workspace_bytes(n_users, n_items, d, k)
+    return bool(L.crh_score_topk_screen_ordered(n_users, n_items, ws_bytes, 1 if has_bitmap else 0))
+
+
+def score_topk_screen_map(cand_bitmap: torch.Tensor, item_emb: torch.Tensor, item_base: int = 0, prefix: int = 0,
+                          ordered: bool = True):
+    """Only the map construction of the screened route's stage 0 (a test entry point): ``(map, keys)``, int32 device tensors --
+    the ids of the unmasked items of ``[item_base + prefix, item_base + n_items)`` in the order the fp16 pass streams them and
+    the 16-bit norm keys of those rows."""
+    import ctypes
+    _need_cuda(cand_bitmap, item_emb)
+    assert cand_bitmap.dtype == torch.int32 and item_emb.dtype == torch.float32 and item_emb.shape[1] == 128
+    item_emb = item_emb.contiguous()
+    n_main = item_emb.shape[0] - prefix
+    out_map = torch.empty(n_main, dtype=torch.int32, device=item_emb.device)
+    out_keys = torch.empty(n_main, dtype=torch.int32, device=item_emb.device)
+    count = ctypes.c_int64(0)
+    rc = _lib.lib().crh_score_topk_screen_map(_lib.ptr(cand_bitmap), _lib.ptr(item_emb), item_emb.shape[0], item_base, prefix,
+                                              1 if ordered else 0, _lib.ptr(out_map), _lib.ptr(out_keys), ctypes.byref(count),
+                                              _lib.current_stream())
+    _lib.check(rc, "crh_score_topk_screen_map")
+    return out_map[:count.value], out_keys[:count.value]
+
+
 def score_topk_uncertified(device=None) -> int:
     """Users the last screened ``score_topk`` call on this device and stream could not certify (they took the exact fallback).
     Synchronises the stream; only meaningful right after a call that ``score_topk_route(...)["screened"]`` reports."""

@@ -103,6 +103,17 @@ const char* crh_score_topk_route_kernel(int route);
  * pass streams only the rows the candidate bitmap leaves (CRH_SCORE_SCREEN_COMPACT, read per call: 1 default, 0 keeps the masked
  * rows in the stream as zeros; results are identical either way). */
 int crh_score_topk_screen_plan(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap, int* cuts, int* compact);
+/* crh_score_topk_screen_ordered: 1 if a screened call of this shape streams the unmasked rows of its main range by descending
+ * row norm (CRH_SCORE_SCREEN_ORDER, read per call: 1 default, 0 keeps the ascending order; results are identical either way):
+ * the compaction is on, the fp16 pass is one cut and the workspace holds the sorted map.  High-norm rows raise every user's
+ * threshold early, so fewer later rows cost a list insert.
+ * crh_score_topk_screen_map (tests): only that map -- the ids of the unmasked items of [item_base + prefix, item_base + n_items)
+ * under `bitmap` (bits of global ids; prefix a multiple of 32), ascending (ordered = 0) or as the ordered route streams them, and
+ * the 16-bit norm keys along it, into device int32 buffers of n_items - prefix entries; *count = the entries that are meaningful.
+ * Allocates its own buffers and synchronises `stream`. */
+int crh_score_topk_screen_ordered(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap);
+int crh_score_topk_screen_map(const uint32_t* bitmap, const float* item_emb, int64_t n_items, int64_t item_base, int64_t prefix,
+                              int ordered, int32_t* map_out, int32_t* keys_out, int64_t* count, void* stream);
 int crh_score_topk_screened(int elem_bytes, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes,
                             int has_bitmap, int n_splits);
 int64_t crh_score_topk_uncertified(const void* workspace, void* stream);

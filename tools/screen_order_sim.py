@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""CPU model of the bookkeeping of the screened route's fp16 pass, to price the order its rows are streamed in.
+
+One workgroup: 512 users in 4 waves of 128, K' = 28 candidates per user, lists seeded exactly from the first 8 192 ids, then the
+live rows of the main range in tiles of 32.  A wave has an event in a tile when any of its users has a row above the user's
+current K'-th score; the workgroup waits at the tile's barrier whenever any of its four waves has one.  The model counts, for the
+ascending order and for the order by descending norm key (the high 16 bits of the fp32 sum of squares, ascending id inside a key):
+events per wave, tiles in which any wave has an event, and the sum over tiles of the busiest wave's candidates.  Tables are drawn
+like the bench's (uniform, xavier bound); --norm-sigma scales the item rows by a lognormal factor.
+
+    python tools/screen_order_sim.py [--items 8000000] [--users 512] [--norm-sigma 0.0]
+"""
+import argparse
+
+import numpy as np
+
+KP, SEED, TILE, WAVE = 28, 8192, 32, 128
+
+
+def norm_keys(V):
+    ss = np.einsum("ij,ij->i", V, V, dtype=np.float32)
+    return (ss.view(np.uint32) >> 16).astype(np.int64)
+
+
+def stream(U, V, order, chunk=8192):
+    """Events of streaming V[order] behind the seed prefix; returns (events per wave, busy tiles, sum of busiest-wave candidates)."""
+    nu = U.shape[0]
+    n_waves = nu // WAVE
+    lists = -np.sort(-(U @ V[:SEED].T), axis=1)[:, :KP].copy()      # descending; column KP-1 is the threshold
+    n_tiles = (len(order) + TILE - 1) // TILE
+    cand = np.zeros((n_tiles, n_waves), np.int32)
+    for c0 in range(0, len(order), chunk):
+        S = U @ V[order[c0:c0 + chunk]].T
+        us, ps = np.nonzero(S > lists[:, KP - 1:KP])                 # a superset: thresholds only rise inside the chunk
+        for j in np.argsort(ps, kind="stable"):
+            u, p = us[j], ps[j]
+            s = S[u, p]
+            if s > lists[u, KP - 1]:
+                row = lists[u]
+                q = np.searchsorted(-row, -s)
+                row[q + 1:] = row[q:-1]
+                row[q] = s
+                cand[(c0 + p) // TILE, u // WAVE] += 1
+    per_wave = (cand > 0).sum(0).mean()
+    return per_wave, int((cand > 0).any(1).sum()), int(cand.max(1).sum())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--items", type=int, default=8_000_000, help="live items (the bench: 10 M less 20 % cold)")
+    ap.add_argument("--users", type=int, default=512)
+    ap.add_argument("--norm-sigma", type=float, default=0.0)
+    a = ap.parse_args()
+    d = 128
+    rng = np.random.default_rng(0)
+    U = ((rng.random((a.users, d), dtype=np.float32) * 2 - 1) * np.sqrt(6 / (1_000_000 + d))).astype(np.float32)
+    V = ((rng.random((a.items, d), dtype=np.float32) * 2 - 1) * np.sqrt(6 / (10_000_000 + d))).astype(np.float32)
+    if a.norm_sigma > 0:
+        V *= np.exp(rng.normal(0.0, a.norm_sigma, (a.items, 1))).astype(np.float32)
+    main_ids = np.arange(SEED, a.items)
+    keys = norm_keys(V[SEED:])
+    by_norm = main_ids[np.argsort(-keys, kind="stable")]
+    print("distinct keys in the main range: %d" % len(np.unique(keys)))
+    r_id = stream(U, V, main_ids)
+    r_nm = stream(U, V, by_norm)
+    names = ("events per wave", "tiles where any of the %d waves has an event" % (a.users // WAVE),
+             "sum over tiles of the busiest wave's candidates")
+    print("| | id order | main range by descending norm key | change |")
+    print("|---|---|---|---|")
+    for n, x, y in zip(names, r_id, r_nm):
+        print("| %s | %.0f | %.0f | %+.1f %% |" % (n, x, y, 100.0 * (y - x) / x))
+
+
+if __name__ == "__main__":
+    main()
