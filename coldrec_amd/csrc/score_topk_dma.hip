@@ -68,6 +68,83 @@ constexpr bool DMA_ONE_TRIP_F32 = false;
 #else
 constexpr bool DMA_ONE_TRIP_F32 = true;
 #endif
+// One candidate of an event, shared by the 32x32 and the 16x16 forms of the slow path: the LDS batch read, the "cannot enter"
+// test, the rated filter with its bounded search, the insert and the user's new threshold out of registers.  sc / gi = the
+// candidate's score and id, bm_masked = its candidate-bitmap bit, ul / slot = its user's column in the wave and slot in the call,
+// mine = "this lane holds that user's threshold" (the caller's accumulator layout decides which lanes those are).
+template <bool ONE_TRIP>
+__device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, int ul, int64_t slot, float* ls, int* li, int* cnt, int K,
+                                              const ScoreArgs& a, int lane, const unsigned* rfilter, bool mine, float& tau_reg) {
+    float* lsu = ls + ul * K;
+    int* liu = li + ul * K;
+    // one batch of LDS reads: fill, tail entry, filter word
+    const unsigned hsh = rated_hash192(gi);
+    const int n_raw = cnt[ul];
+    const int le = ONE_TRIP ? (lane < K ? lane : K - 1) : K - 1;   // (ONE_TRIP: lane l reads entry l; the others the tail entry)
+    const float ks_raw = lsu[le];
+    const int ki_raw = liu[le];
+    const unsigned fw_raw = a.rated_rowptr ? rfilter[ul * DMA_FW + (hsh >> 5)] : 0u;
+    const int n = __builtin_amdgcn_readfirstlane(n_raw);
+    if (n >= K) {
+        const float ks = ONE_TRIP ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ks_raw), K - 1))
+                                  : __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ks_raw)));
+        const int ki = ONE_TRIP ? __builtin_amdgcn_readlane(ki_raw, K - 1) : __builtin_amdgcn_readfirstlane(ki_raw);
+        if (!crh_better(fmaxf(sc, CRH_MASKED_SCORE), gi, ks, ki)) return;   // cannot enter a full list
+    }
+    bool masked = bm_masked;
+    if (!masked && ((__builtin_amdgcn_readfirstlane(fw_raw) >> (hsh & 31)) & 1u)) {
+        const int64_t lo = a.rated_rowptr[slot], hi = a.rated_rowptr[slot + 1];
+        masked = wave_is_masked_at(gi, lo, hi, a.rated_col, nullptr, lane);
+        // every load of the search has landed HERE, inside the rare branch: left pending on this exit, hipcc guards the
+        // join with s_waitcnt vmcnt(0) -- paid by EVERY event, and vmcnt counts the tile DMAs in flight too: the
+        // flag form issued them one group (0.8 us) earlier, the barrier form at 256-byte rows in this very group, so an
+        // event waited for a DMA round trip (round 6, found in the ISA; tile_slow_path has had the same fix since round 4)
+        __builtin_amdgcn_s_waitcnt(0x0f70);
+    }
+    if (masked) sc = CRH_MASKED_SCORE;
+    // wave_list_insert (k <= 64 here) that also hands back the user's NEW threshold out of the registers it already
+    // holds -- the k-th entry after the insert is the old (k-1)-th or the candidate -- instead of reading it back
+    float es = CRH_NEG_INF;
+    int ei = CRH_PAD_IDX;
+    if constexpr (ONE_TRIP) {
+        if (lane < n) {
+            es = ks_raw;
+            ei = ki_raw;
+        }
+    } else {
+        if (lane < n) {
+            es = lsu[lane];
+            ei = liu[lane];
+        }
+    }
+    const int p = __popcll(__ballot(lane < n && crh_better(es, ei, sc, gi)));
+    if (p < K) {
+        if (lane >= p && lane < n && lane + 1 < K) {
+            lsu[lane + 1] = es;
+            liu[lane + 1] = ei;
+        }
+        const int n2 = n < K ? n + 1 : K;
+        if (lane == 0) {
+            lsu[p] = sc;
+            liu[p] = gi;
+            cnt[ul] = n2;
+        }
+        if (n2 >= K) {
+            const float prev = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, es), K >= 2 ? K - 2 : 0));
+            const float kth = (p == K - 1) ? sc : prev;
+            if (mine) tau_reg = kth >= CRH_MASKED_SCORE ? kth : CRH_NEG_INF;
+        }
+    }
+}
+
+// MFMA shape of the screen's two launches (fp16 d=128; M16 of the kernel): v_mfma_f32_16x16x32_f16, which holds a higher clock on
+// this power-limited stream than 32x32x16 at the same cycles per flop (round 11).  The approximate scores differ in their last
+// bits (32 products per instruction instead of 16); the screen's certificate covers any fp32 accumulation order.
+#ifdef CRH_DMA_SCREEN_MFMA32                 // (variant build: the 32x32x16 form, tools/ab_lib.sh)
+constexpr bool DMA_SCREEN_M16 = false;
+#else
+constexpr bool DMA_SCREEN_M16 = true;
+#endif
 // CM (compacted stream): row q of the stream is the q-th unmasked item; idv = the ids of this tile's rows (lane l: row l & 31),
 // read from LDS once per event by the caller.  item0 and split_end stay row numbers; there are no masked rows (tb = 0).
 template <bool ONE_TRIP, bool CM>
@@ -95,80 +172,91 @@ __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau
         const int64_t slot = slot0 + jl;
         if (slot >= a.n_users) continue;
         const int ul = ucol0 + jl;
-        float* lsu = ls + ul * K;
-        int* liu = li + ul * K;
         while (cmL) {
             const int r = __builtin_ctz(cmL);
             cmL &= cmL - 1;
             const int64_t il = item0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
             if (il >= split_end) continue;   // clamped duplicate rows of the tail tile
-            float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pick16u(acc, r)), L));
+            const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pick16u(acc, r)), L));
             int gi;
             if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, (r & 3) + 8 * (r >> 2) + 4 * hh);
             else gi = (int)(a.item_base + il);
-            // one batch of LDS reads: fill, tail entry, filter word
-            const unsigned hsh = rated_hash192(gi);
-            const int n_raw = cnt[ul];
-            const int le = ONE_TRIP ? (lane < K ? lane : K - 1) : K - 1;   // (ONE_TRIP: lane l reads entry l; the others the tail entry)
-            const float ks_raw = lsu[le];
-            const int ki_raw = liu[le];
-            const unsigned fw_raw = a.rated_rowptr ? rfilter[ul * DMA_FW + (hsh >> 5)] : 0u;
-            const int n = __builtin_amdgcn_readfirstlane(n_raw);
-            if (n >= K) {
-                const float ks = ONE_TRIP ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ks_raw), K - 1))
-                                          : __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ks_raw)));
-                const int ki = ONE_TRIP ? __builtin_amdgcn_readlane(ki_raw, K - 1) : __builtin_amdgcn_readfirstlane(ki_raw);
-                if (!crh_better(fmaxf(sc, CRH_MASKED_SCORE), gi, ks, ki)) continue;   // cannot enter a full list
-            }
-            bool masked = (bmL >> r) & 1u;
-            if (!masked && ((__builtin_amdgcn_readfirstlane(fw_raw) >> (hsh & 31)) & 1u)) {
-                const int64_t lo = a.rated_rowptr[slot], hi = a.rated_rowptr[slot + 1];
-                masked = wave_is_masked_at(gi, lo, hi, a.rated_col, nullptr, lane);
-                // every load of the search has landed HERE, inside the rare branch: left pending on this exit, hipcc guards the
-                // join with s_waitcnt vmcnt(0) -- paid by EVERY event, and vmcnt counts the tile DMAs in flight too: the
-                // flag form issued them one group (0.8 us) earlier, the barrier form at 256-byte rows in this very group, so an
-                // event waited for a DMA round trip (round 6, found in the ISA; tile_slow_path has had the same fix since round 4)
-                __builtin_amdgcn_s_waitcnt(0x0f70);
-            }
-            if (masked) sc = CRH_MASKED_SCORE;
-            // wave_list_insert (k <= 64 here) that also hands back the user's NEW threshold out of the registers it already
-            // holds -- the k-th entry after the insert is the old (k-1)-th or the candidate -- instead of reading it back
-            {
-                float es = CRH_NEG_INF;
-                int ei = CRH_PAD_IDX;
-                if constexpr (ONE_TRIP) {
-                    if (lane < n) {
-                        es = ks_raw;
-                        ei = ki_raw;
-                    }
-                } else {
-                    if (lane < n) {
-                        es = lsu[lane];
-                        ei = liu[lane];
-                    }
-                }
-                const int p = __popcll(__ballot(lane < n && crh_better(es, ei, sc, gi)));
-                if (p < K) {
-                    if (lane >= p && lane < n && lane + 1 < K) {
-                        lsu[lane + 1] = es;
-                        liu[lane + 1] = ei;
-                    }
-                    const int n2 = n < K ? n + 1 : K;
-                    if (lane == 0) {
-                        lsu[p] = sc;
-                        liu[p] = gi;
-                        cnt[ul] = n2;
-                    }
-                    if (n2 >= K) {
-                        const float prev = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, es), K >= 2 ? K - 2 : 0));
-                        const float kth = (p == K - 1) ? sc : prev;
-                        if ((lane & 31) == jl) tau_reg = kth >= CRH_MASKED_SCORE ? kth : CRH_NEG_INF;
-                    }
-                }
-            }
+            dma_candidate<ONE_TRIP>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 31) == jl, tau_reg);
         }
     }
     // (no read-back of the thresholds: every insert above updated its user's lanes; padding columns keep their +inf)
+}
+
+// The same event for the 16x16x32 form (M16 below): acc = the two 16x16 accumulators of one block of 16 users, element 4 mb + r of
+// lane (c = lane & 15, g = lane >> 4) = tile row 16 mb + 4 g + r for user column c; all four g-lanes of a user hold its threshold.
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ float max8(const f32x8& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float a0, a1, a2, r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(a0) : "v"(v[0]), "v"(v[1]), "v"(v[2]));
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(a1) : "v"(v[3]), "v"(v[4]), "v"(v[5]));
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(a2) : "v"(v[6]), "v"(v[7]), "v"(a0));
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a1), "v"(a2));
+    return r;
+#else
+    return fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
+#endif
+}
+__device__ __forceinline__ float acc_max(const f32x8& v) { return max8(v); }
+__device__ __forceinline__ float acc_max(const f32x16& v) { return max16(v); }
+__device__ __forceinline__ unsigned gt_mask8(const f32x8& v, float t) {   // as gt_mask16
+    unsigned m = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int r = 7; r >= 0; --r)
+        asm("v_cmp_gt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m) : "v"(v[r]), "v"(t) : "vcc");
+#endif
+    return m;
+}
+// v[r] for a wave-uniform r, as a select tree on scalar conditions: the two halves of an accumulator pair are separate register
+// tuples, so there is no register-indexed move to be had as in pick16u.  (NOTE, hipcc 7.2: v[readfirstlane(r)] on this f32x8 was
+// compiled to a read of element 0 whatever r -- found in the ISA; every candidate but a tile's first row would have carried a wrong score.)
+__device__ __forceinline__ float pick8u(const f32x8& v, int r) {
+    const bool b0 = r & 1, b1 = r & 2, b2 = r & 4;
+    const float p0 = b0 ? v[1] : v[0], p1 = b0 ? v[3] : v[2], p2 = b0 ? v[5] : v[4], p3 = b0 ? v[7] : v[6];
+    const float q0 = b1 ? p1 : p0, q1 = b1 ? p3 : p2;
+    return b2 ? q1 : q0;
+}
+template <bool CM>
+__device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& tau_reg, float* ls, int* li, int* cnt, int K, int ucol0,
+                                                     int64_t slot0, const ScoreArgs& a, int64_t item0, int64_t split_end, int lane,
+                                                     unsigned tb, const unsigned* rfilter, int idv) {
+    unsigned cm = gt_mask8(acc, tau_reg);
+    unsigned m8 = 0u;                                             // masked rows of this lane, as in the 32x32 form
+    if (tb != 0u && __ballot(tau_reg < 0.0f) != 0ull) {           // wave-uniform
+        const int g4 = 4 * (lane >> 4);
+        m8 = ((tb >> g4) & 0xFu) | (((tb >> (16 + g4)) & 0xFu) << 4);
+        if (tau_reg > CRH_NEG_INF) cm &= ~m8;
+    }
+    const unsigned bm = cm & m8;
+    unsigned long long lanes = __ballot(cm != 0u);
+    while (lanes) {
+        const int L = __builtin_ctzll(lanes);
+        lanes &= lanes - 1;
+        unsigned cmL = __builtin_amdgcn_readlane(cm, L);
+        const unsigned bmL = __builtin_amdgcn_readlane(bm, L);
+        const int jl = L & 15, g = L >> 4;
+        const int64_t slot = slot0 + jl;
+        if (slot >= a.n_users) continue;
+        const int ul = ucol0 + jl;
+        while (cmL) {
+            const int r = __builtin_ctz(cmL);
+            cmL &= cmL - 1;
+            const int row = 16 * (r >> 2) + 4 * g + (r & 3);
+            const int64_t il = item0 + row;
+            if (il >= split_end) continue;   // clamped duplicate rows of the tail tile
+            const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pick8u(acc, r)), L));
+            int gi;
+            if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, row);
+            else gi = (int)(a.item_base + il);
+            dma_candidate<false>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg);
+        }
+    }
 }
 
 
@@ -217,9 +305,31 @@ __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau
 // grid, the cuts and the lockstep windows by its upper bound n_items, and every workgroup of a cut walks the same tiles.  A
 // candidate's id comes out of the id slots in LDS (IDS_B, in the place of the tile bits: there is no masked row to tell apart);
 // lists, filters, seeds and the cuts' merge stay in id space.
-template <typename T, int D, int R, bool FL, bool CM = false>
+//
+// M16 = the 16x16x32 MFMA form (fp16 d=128: both launches of the screened route's pass, round 11).  The same tile, the same ring, barrier,
+// DMA placement and two accumulator sets; what changes is the register layout.  The chip is power-limited on this stream, and it
+// holds a higher clock on v_mfma_f32_16x16x32_f16 than on 32x32x16 at the same matrix-pipe cycles per flop
+// (tools/probes/mfma_energy_probe.hip shape, profiles/r11_mfma_shape_probe.log: 1.97 against 1.63 GHz in the bare loop).
+//   * users in 8 blocks of 16 columns: lane (c = lane & 15, g = lane >> 4) holds, for block nb and k-step ks, the 16 bytes at offset
+//     64 ks + 16 g of the row of user 16 nb + c -- 32 fragments, 128 AGPRs as before; tau[8], the same value in all four g-lanes;
+//   * the packed tile is unchanged (chunk q, 16-byte slot 32 h + i = row i, halfs 16 q + 8 h .. + 7); the A fragment of item half
+//     mb and k-step ks is row 16 mb + c, halfs 32 ks + 8 g .. + 7 = byte ks 2048 + (g >> 1) 1024 + (g & 1) 512 + mb 256 + c 16: one
+//     per-lane base, immediate offsets, one ds_read_b128 per fragment and eight per tile as before, conflict-free;
+//   * a group is k-step ks: its two fragments (mb = 0, 1) each feed the 8 independent MFMAs over nb -- 16 MFMAs of 16 cycles;
+//   * accumulators acc[set][nb] as f32x8: element 4 mb + r of lane (c, g) = tile row 16 mb + 4 g + r for user 16 nb + c;
+//   * a 16-cycle MFMA hides two other instructions, a 32-cycle one six, so the threshold test is spread: the maxima in group 0,
+//     the barrier and the DMA issue in group 1, the compares and the events behind group 2.  (An event reads registers, the id
+//     slots and the tile bits of tile j-1, all of which outlive body j: its place inside the body is free.)
+// The approximate scores differ from the 32x32 form's in their last bits (another accumulation order); the screen's results do not
+// (stage 2 rescores, and its bound covers any fp32 accumulation order).  The public fp16 routes never run this kernel at d=128.
+template <typename T, int D, int R, bool FL, bool CM = false, bool M16 = false>
 __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     constexpr int NW = DMA_NW, UW = 4, UPW = DMA_UPW;
+    static_assert(!M16 || (std::is_same<T, _Float16>::value && D == 128 && !FL), "the 16x16x32 form is the fp16 d=128 screen's");
+    // register shapes of the two MFMA forms: user blocks of UB columns, NU of them per wave; b[BQ][NU] user fragments (BQ 32-byte
+    // chunks, or M16: 64-byte k-steps); accumulators of NR registers per user block (M16: both 16-row halves of the tile in one f32x8)
+    constexpr int UB = M16 ? 16 : 32, NU = UPW / UB, NR = M16 ? 8 : 16;
+    using AccT = std::conditional_t<M16, f32x8, f32x16>;
     // body j issues the DMA of tile j + PF; in the flag form it publishes its pieces of tile j + PF - 1 (issued one body ago) first:
     // a wave may lead the slowest reader by (NG - 2) / NG of a tile and the slowest refiller by one tile
     constexpr int PF = FL ? 2 : 3;
@@ -231,6 +341,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     constexpr int CPW = NCH / NW;                      // 1 KiB DMA pieces of a tile each wave issues
     constexpr int GR = 2, NG = NCH / GR;               // A fragments are read in groups of GR chunks, one group ahead
     constexpr int BG = NG / 2 - 1;                     // the group in front of which the ring barrier sits
+    constexpr int TG = M16 ? 2 : 1;                    // the group behind which tile j-1's threshold test (and its events) sits
     static_assert(NCH % NW == 0 && NG % 4 == 0 && BG + 2 < NG, "row width not supported by the DMA kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -242,7 +353,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     const bool live = ug_raw < a.n_ugroups;            // a dead wave still fetches and synchronises
     const int64_t ug = live ? ug_raw : a.n_ugroups - 1;
     const int K = a.k;
-    const int i = lane & 31, h = lane >> 5;
+    const int i = lane & (M16 ? 15 : 31), h = lane >> (M16 ? 4 : 5);   // user column in its block, k-group (M16: c and g of the 16x16x32 layout)
 
     char* ring = smem;                                  // [R][TILE_B]
     unsigned* tbits = reinterpret_cast<unsigned*>(smem + R * TILE_B);   // [2][64]; CM: [IDS_SLOTS + 1][32] ids
@@ -324,28 +435,29 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         }
     }
 
-    f32x4 b[NCH][UW];
-    float tau[UW];
+    constexpr int BQ = M16 ? ROWB / 64 : NCH;
+    f32x4 b[BQ][NU];
+    float tau[NU];
 #pragma unroll
-    for (int u = 0; u < UW; ++u) {
-        int64_t slot = slot0w + 32 * u + i;
+    for (int u = 0; u < NU; ++u) {
+        int64_t slot = slot0w + UB * u + i;
         tau[u] = slot < a.n_users ? CRH_NEG_INF : __builtin_inff();      // padding columns never take a candidate
-        if (a.seed_score && slot < a.n_users) tau[u] = wave_list_tau(ls + (32 * u + i) * K, cnt[32 * u + i], K);
+        if (a.seed_score && slot < a.n_users) tau[u] = wave_list_tau(ls + (UB * u + i) * K, cnt[UB * u + i], K);
         if (slot >= a.n_users) slot = a.n_users - 1;
         const int64_t row = a.users ? (int64_t)a.users[slot] : a.user_base + slot;
         const char* up = reinterpret_cast<const char*>(a.user_emb) + row * ROWB + 16 * h;
 #pragma unroll
-        for (int q = 0; q < NCH; ++q) {
-            b[q][u] = load16(up + 32 * q);
+        for (int q = 0; q < BQ; ++q) {
+            b[q][u] = load16(up + (M16 ? 64 : 32) * q);      // M16: lane (c, g) holds halfs 32 q + 8 g .. + 7 of user 16 u + c
             if constexpr (Elem<T>::kSwap) chunk_swap(b[q][u]);
         }
     }
     // the user fragments live in AGPRs from here on (and have landed: nothing of theirs is left on the VM counter)
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
-    for (int q = 0; q < NCH; ++q)
+    for (int q = 0; q < BQ; ++q)
 #pragma unroll
-        for (int u = 0; u < UW; ++u) {
+        for (int u = 0; u < NU; ++u) {
             if constexpr (sizeof(T) == 4) {     // fp32 MFMAs take ONE dword per operand: pinned as a 4-vector hipcc copies every
                 asm volatile("" : "+a"(b[q][u].x));   // component to a VGPR first (v_accvgpr_read per MFMA, 23 spills); as four
                 asm volatile("" : "+a"(b[q][u].y));   // scalars the MFMA reads a[N] directly
@@ -411,24 +523,28 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 #endif
     };
 
-    f32x16 acc[2][UW];
+    AccT acc[2][NU];
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
-        for (int u = 0; u < UW; ++u)
+        for (int u = 0; u < NU; ++u)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[p][u][r] = 0.0f;
+            for (int r = 0; r < NR; ++r) acc[p][u][r] = 0.0f;
     // A fragments: LDS -> registers by inline asm with COUNTED waits.  Left to hipcc the loop gets "s_waitcnt lgkmcnt(0)" right
     // behind the reads of the NEXT group (seen in the ISA: every second group stalls for a full LDS round trip).  The asm reads
     // are invisible to the compiler's counter bookkeeping; lds_wait names the registers it guards, so no MFMA that consumes
     // them can be scheduled above it (cdna_hip_programming.md 5.7: form (ii)).  LDS operations complete in order, so
     // lgkmcnt(2 GR) = "everything but the 2 GR reads issued last has landed" also covers any list access of the slow path.
     f32x4 c[4][GR];
-    const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)ring + lane * 16;
+    // M16: the fragment of item half mb and k-step ks wants row 16 mb + c, halfs 32 ks + 8 g .. + 7 in lane (c, g) -- chunk
+    // 2 ks + (g >> 1), slot 32 (g & 1) + 16 mb + c of the packed tile: one per-lane base and the immediate offsets ks * 2048 + mb * 256.
+    // A group is one k-step, its two fragments the two halves.  (Lanes 0 - 15 of a read are 16 consecutive slots: no bank conflict.)
+    const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)ring +
+                              (M16 ? (lane >> 5) * 1024 + ((lane >> 4) & 1) * 512 + (lane & 15) * 16 : lane * 16);
     auto lds_group = [&](f32x4(&dst)[GR], uint32_t addr, auto Gc) __attribute__((always_inline)) {
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[0]) : "v"(addr), "i"((decltype(Gc)::value * GR + 0) * 1024));
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[1]) : "v"(addr), "i"((decltype(Gc)::value * GR + 1) * 1024));
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[1]) : "v"(addr), "i"(M16 ? decltype(Gc)::value * GR * 1024 + 256 : (decltype(Gc)::value * GR + 1) * 1024));
 #endif
     };
     auto lds_wait = [&](f32x4(&x)[GR], auto Nc) __attribute__((always_inline)) {
@@ -493,7 +609,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     auto body = [&](auto Pc, int j, int s_cur, int s_nxt, int s_fill) __attribute__((always_inline)) {
         constexpr int P = decltype(Pc)::value, Q = 1 - P;
         const uint32_t src = ring_lds + s_cur * TILE_B, srcn = ring_lds + s_nxt * TILE_B;
-        float m[UW];
+        float m[NU];
         // one group of GR chunks; g is a compile-time constant (every register array below is indexed statically)
         auto group = [&](auto Gc) __attribute__((always_inline)) {
             constexpr int g = decltype(Gc)::value;
@@ -522,12 +638,14 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 dma_tile(j + 3, s_fill);
                 // one DMA instruction and a few of its address instructions per MFMA gap instead of all of them in one gap
                 // (+0.9 % on the same box: a single wave per SIMD hides about five issue slots per MFMA, not twenty)
+                // (M16: a 16-cycle MFMA hides two instructions, not six: one scalar and one vector address instruction per gap, the
+                // DMAs wherever their addresses are ready)
 #pragma unroll
-                for (int q = 0; q < 8; ++q) {
+                for (int q = 0; q < (M16 ? 16 : 8); ++q) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x004, 2, 0);   // SALU
+                    __builtin_amdgcn_sched_group_barrier(0x004, M16 ? 1 : 2, 0);   // SALU
                     __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // VALU
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read (the DMA)
+                    if constexpr (!M16) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read (the DMA)
                 }
             }
             if constexpr (FL) {
@@ -570,6 +688,27 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                         (mma_f32_hooked<UW, JJ * 4 * UW>(acc[P], c[g & 3][JJ], b[g * GR + JJ], hook), ...);
                     }(std::make_integer_sequence<int, GR>{});
                 }
+            } else if constexpr (M16) {
+                // k-step g: each of the two fragments (item halves) feeds the 8 independent MFMAs over the user blocks -- 16 MFMAs of 16
+                // cycles, the 256 matrix-pipe cycles of a group of the 32x32 form
+                if constexpr (g == 0) {
+#pragma unroll
+                    for (int u = 0; u < NU; ++u)
+#pragma unroll
+                        for (int r = 0; r < NR; ++r) acc[P][u][r] = 0.0f;
+                }
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb) {
+                    const f16x8 ca = __builtin_bit_cast(f16x8, c[g & 3][mb]);
+#pragma unroll
+                    for (int u = 0; u < NU; ++u) {
+                        AccT& x = acc[P][u];
+                        f32x4 t = mb ? f32x4{x[4], x[5], x[6], x[7]} : f32x4{x[0], x[1], x[2], x[3]};
+                        t = __builtin_amdgcn_mfma_f32_16x16x32_f16(ca, __builtin_bit_cast(f16x8, b[g][u]), t, 0, 0, 0);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) x[4 * mb + r] = t[r];
+                    }
+                }
             } else {
 #pragma unroll
                 for (int jj = 0; jj < GR; ++jj) {
@@ -584,17 +723,41 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     Elem<T>::template mma<UW>(acc[P], c[g & 3][jj], b[g * GR + jj]);
                 }
             }
-            if constexpr (g == 1) {
+            // the maxima of tile j-1's accumulators.  M16: a 16-cycle MFMA hides two instructions where a 32-cycle one hides six, so the
+            // test is spread over three groups -- the maxima in group 0, which carries nothing else (two per MFMA), the barrier and
+            // the DMA issue in group 1 as ever, the compares and the event in group 2 (TG)
+            if constexpr (M16 && g == 0) {
 #pragma unroll
-                for (int u = 0; u < UW; ++u) m[u] = max16(acc[Q][u]);
+                for (int u = 0; u < NU; ++u) m[u] = acc_max(acc[Q][u]);
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // VALU
+                }
+            }
+            if constexpr (!M16 && g == 1) {
+#pragma unroll
+                for (int u = 0; u < UW; ++u) m[u] = acc_max(acc[Q][u]);
+            }
+            unsigned long long hitm = 0ull;
+            if constexpr (M16 && g == TG) {      // the compares ride the group's MFMAs too (behind them they are paid in full)
+#pragma unroll
+                for (int u = 0; u < NU; ++u) hitm |= __ballot(m[u] > tau[u]);
+#pragma unroll
+                for (int q = 0; q < NU; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // VALU
+                    __builtin_amdgcn_sched_group_barrier(0x004, 1, 0);   // SALU
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (g == 1) {
+            if constexpr (g == TG) {
                 // four compares straight into scalar masks (OR-ed per lane first, the ballot of the result was a select and a second
                 // compare: two VALU instructions per tile beside MFMAs that hide none)
-                unsigned long long hitm = 0ull;
+                if constexpr (!M16) {
 #pragma unroll
-                for (int u = 0; u < UW; ++u) hitm |= __ballot(m[u] > tau[u]);
+                    for (int u = 0; u < UW; ++u) hitm |= __ballot(m[u] > tau[u]);
+                }
                 if (hitm != 0ull && live && j > 0 && !(CRH_ABLATE(a.ablate) & 1)) {
 #ifdef CRH_PROFILE
                     const unsigned long long ev_t0 = a.wave_clock != nullptr ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -604,10 +767,15 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     int idv = 0;                     // CM: the selected tile's ids, one LDS read per event (where tb's was)
                     if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
 #pragma unroll
-                    for (int u = 0; u < UW; ++u)
-                        if (__ballot(m[u] > tau[u]) != 0ull)
-                            tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32, CM>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a,
-                                                                                        ts << 5, split_end, lane, tb, rfilter, idv);
+                    for (int u = 0; u < NU; ++u)
+                        if (__ballot(m[u] > tau[u]) != 0ull) {
+                            if constexpr (M16)
+                                tile_slow_path_dma16<CM>(acc[Q][u], tau[u], ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, lane, tb,
+                                                         rfilter, idv);
+                            else
+                                tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32, CM>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a,
+                                                                                            ts << 5, split_end, lane, tb, rfilter, idv);
+                        }
                     // the list stores of the inserts are drained HERE: left pending, the compiler parks an lgkmcnt(0) at a
                     // later point of the common path, right behind the fragment reads of the barrier group
                     __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -718,10 +886,10 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     }
 }
 
-template <typename T, int D, int R, bool FL, bool CM = false>
+template <typename T, int D, int R, bool FL, bool CM = false, bool M16 = false>
 int launch_score_dma_t(const ScoreArgs& a, hipStream_t stream) {
     const size_t lds = score_dma_lds_bytes(D * (int)sizeof(T), a.k, R, FL, CM);
-    auto kern = score_topk_dma_kernel<T, D, R, FL, CM>;
+    auto kern = score_topk_dma_kernel<T, D, R, FL, CM, M16>;
     CRH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds));
     const int64_t blocks = ((a.n_ugroups + DMA_NW - 1) / DMA_NW) * a.n_splits;
@@ -750,9 +918,11 @@ int score_dma_ring_slots(int esz, int d, int k, int mode) {
 int launch_score_dma(int esz, int d, int mode, const ScoreArgs& a, hipStream_t stream) {
     if (esz == 2 && d == 128 && a.idmap != nullptr) {     // the compacted stream of the screened route
         if (score_dma_lds_bytes(d * esz, a.k, 4, false, true) > 160 * 1024) return CRH_ERR_ARG;
-        return launch_score_dma_t<_Float16, 128, 4, false, true>(a, stream);
+        return launch_score_dma_t<_Float16, 128, 4, false, true, DMA_SCREEN_M16>(a, stream);
     }
-    if (esz == 2) return d == 128 ? launch_score_dma_t<_Float16, 128, 4, false>(a, stream) : launch_score_dma_t<_Float16, 256, 4, false>(a, stream);
+    // (fp16 d=128 reaches this kernel from the screen only -- the public fp16 d=128 calls take the ring kernel, score_topk.hip
+    // dma_rows -- so both of its launches share one definition of the approximate score)
+    if (esz == 2) return d == 128 ? launch_score_dma_t<_Float16, 128, 4, false, false, DMA_SCREEN_M16>(a, stream) : launch_score_dma_t<_Float16, 256, 4, false>(a, stream);
     if (d == 64) return launch_score_dma_t<float, 64, 4, false>(a, stream);
     return mode == 2 ? launch_score_dma_t<float, 128, 4, true>(a, stream) : launch_score_dma_t<float, 128, 4, false>(a, stream);
 }
