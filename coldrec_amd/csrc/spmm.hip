@@ -14,9 +14,11 @@
 // the oracle's order (oracle/topk_oracle.c orc_spmm_csr), so results are reproducible bit for bit.
 // Catalogues are Zipf-shaped (a popular item has thousands of edges, a user a few dozen), so the
 // caller may pass a SCHEDULE built once per graph: rows of <= 64 edges are one work item of a lane
-// group; the few heavier rows get a whole wave each (its lane groups take the row's 64-edge segments
-// round robin and their partial sums are combined by shuffles in a fixed order: deterministic, the
-// association differs from the single chain).  One launch, no partials in memory.
+// group; the few heavier rows get a whole workgroup each (heavy_row: its lane groups take contiguous
+// chunks of the row's edge list and their partial sums are combined in a fixed order, a shuffle tree
+// per wave and (w0 + w1) + (w2 + w3) across the waves: deterministic, the association differs from
+// the single chain -- oracle/spmm_model.py restates it on the host and tests/test_spmm_edges_gpu.py
+// compares bit for bit).  One launch, no partials in memory.
 //
 // XCD-aware column slicing: for graphs whose dense operand does not fit one XCD's 4 MiB L2 but a column
 // slice of it does (CiteULike: 22.5 K rows x 512 B = 11.5 MB; a quarter = 2.9 MB), the feature columns

@@ -5,7 +5,7 @@ Per case: random table sizes / widths / batch sizes / duplicate patterns, then
   * crh_bpr_fwd_bwd_f32 with the atomics backward and with the reverse-index ("plan") backward vs the fp64
     closed form (1e-5 on the losses, 5e-4 / scaled absolute on gradients); the plan backward twice -> identical bits;
   * crh_spmm_csr_f32 with and without the schedule on a random Zipf graph vs the C oracle: rows in one piece
-    bit-exact, heavy rows to rounding;
+    bit-exact, heavy rows bit-exact against the host model of their sum tree (oracle/spmm_model.py);
   * a few optimiser steps with the dense Adam and with the touched-rows replay -> identical bits after the flush;
   * whole epochs with the one-launch MF step (crh_mf_step_f32) against the three-kernel step -> same losses and tables
     up to the summation order of the norms, and bit-identical when repeated;
@@ -28,9 +28,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from coldrec_amd import ops  # noqa: E402
+from coldrec_amd import _lib, ops  # noqa: E402
 from coldrec_amd.train import EpochRunner, MFEngine  # noqa: E402
 from oracle import oracle_np as orc  # noqa: E402
+from oracle import spmm_model  # noqa: E402
 
 DEV = torch.device("cuda:0")
 
@@ -111,14 +112,19 @@ def case_spmm(rng):
     one = deg <= sched.seg
     if not np.array_equal(y1[one], want[one]):
         fail("spmm sched light rows", d=d, n=n_u + n_i)
-    # heavy rows are summed in a different (fixed) association: bound the difference by the row's condition,
-    # 4 ulp-ish of sum |a_ij x_j| (fp64 reference via scipy)
+    # heavy rows are summed in a different, FIXED association (chunks per lane group, shuffle tree, four waves): the host
+    # model of that tree (oracle/spmm_model.py) under each row's own lane-group width gives the bits
+    G = int(_lib.lib().crh_spmm_lane_group(n_u + n_i, d, int(rowptr[-1])))
+    n_sub = spmm_model.n_sub_of_rows(n_u + n_i, sched.t[3].cpu().numpy(), sched.t[5].cpu().numpy())
+    tree = spmm_model.spmm_scheduled(rowptr, col, val, X, G, sched.seg, n_sub)
+    if not np.array_equal(y1.view(np.int32), tree.view(np.int32)):
+        badr = np.nonzero((y1.view(np.int32) != tree.view(np.int32)).any(1))[0]
+        fail("spmm sched heavy rows", d=d, n=n_u + n_i, G=G, rows=[(int(r), int(deg[r]), int(n_sub[r])) for r in badr[:6]])
+    # the epilogue against fp64, within the rows' condition (4 ulp-ish of sum |a_ij x_j|, fp64 reference via scipy)
     import scipy.sparse as sp
     A = sp.csr_matrix((val.astype(np.float64), col, rowptr), shape=(n_u + n_i, n_u + n_i))
     p64 = A @ X.astype(np.float64)
     bound = (abs(A) @ np.abs(X).astype(np.float64)) * 4e-7 + 1e-9
-    if not np.all(np.abs(y1[~one] - p64[~one]) <= bound[~one] + 1e-6 * np.abs(p64[~one])):
-        fail("spmm sched heavy rows", d=d, n=n_u + n_i)
     a_want = (Z.astype(np.float64) * 0.5 + p64) * 2.0
     if not np.all(np.abs(A1.cpu().numpy() - a_want) <= 2 * bound + 1e-6 * (np.abs(a_want) + np.abs(Z))):
         fail("spmm epilogue", d=d)

@@ -1,4 +1,5 @@
-"""Edges of the training kernels (coldrec_amd/csrc/bpr_adam.hip, l2_reg.hip, spmm.hip's SGD epilogue): the shapes, widths,
+"""Edges of the training kernels (coldrec_amd/csrc/bpr_adam.hip, l2_reg.hip, spmm.hip's SGD epilogue -- the SpMM's own
+widths, cuts and heavy-row sum tree are tests/test_spmm_edges_gpu.py): the shapes, widths,
 grid caps, heavy-row thresholds and row-ownership splits where a change of lane mapping, ownership or reduction order would
 otherwise go unnoticed.  Every kernel is driven through coldrec_amd.ops or the C ABI and compared with either
 
