@@ -93,6 +93,11 @@ SIGNATURES = {
     "crh_infonce_workspace_bytes": (_sz, [_i64, _i32]),
     "crh_infonce_splits": (_i32, [_i64]),
     "crh_infonce_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "crh_clcrec_max_neg": (_i32, []),
+    "crh_clcrec_chunk_rows": (_i32, []),
+    "crh_clcrec_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
+    "crh_clcrec_f32": (_i32, [_vp] * 12 + [_i64] + [_vp] * 3 + [_i64, _i64, _i32, _i32, _i64, _f32, _f32, _f32, _f32,
+                              _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "crh_noise_uniform_f32": (_i32, [_vp, _i64, _i32, ctypes.c_uint64, _vp, _i64, _vp]),
     "crh_perturb_rows_f32": (_i32, [_vp, _i64, _i32, _f32, _vp, ctypes.c_uint64, _vp, _i64, _vp, _f32, _vp, _f32, _vp]),
     "crh_comm_unique_id": (_i32, [_vp]),

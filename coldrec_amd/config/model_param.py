@@ -16,7 +16,8 @@ def _str2bool(v):
 
 def model_specific_param(model_name, parser, available_models):
     if model_name not in available_models:
-        names = available_models.names() if hasattr(available_models, 'names') else available_models.keys()
+        names = available_models.resolvable() if hasattr(available_models, 'resolvable') else \
+            available_models.names() if hasattr(available_models, 'names') else available_models.keys()
         raise ValueError(f"Invalid model name: {model_name}. Available models: {list(names)}")
     # MF and LightGCN take no flags beyond the common ones (--layers is common, main.py:94)
     if model_name == 'DropoutNet':      # config/model_param.py:242-255
@@ -34,4 +35,10 @@ def model_specific_param(model_name, parser, available_models):
                             help='(addition) where the perturbation noise comes from: device = generated in the kernel '
                                  '(Philox4x32-10 keyed by --seed); host = torch.rand on the CPU generator, uploaded per '
                                  'layer -- the reference\'s own stream, for parity runs')
+    if model_name == 'CLCRec':      # config/model_param.py:125-129
+        parser.add_argument('--num_neg', type=int, default=128, help='Sampled negatives per record')
+        parser.add_argument('--temp_value', type=float, default=2.0, help='Contrastive loss temperature')
+        parser.add_argument('--lr_lambda', type=float, default=0.5, help='Weight of the embedding-content contrastive loss')
+        parser.add_argument('--num_sample', type=float, default=0.5,
+                            help='Share of the batch rows (drawn with replacement) scored on content instead of embedding')
     return parser

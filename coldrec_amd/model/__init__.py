@@ -6,13 +6,16 @@ subclasses ``BaseColdStartTrainer`` can be registered with ``register(name, cls)
 
 ``keys()`` lists the core trainers plus whatever ``register()`` added.  The contrastive trainers (SimGCL, XSimGCL)
 resolve by name through ``[]``, ``.get()`` and ``in`` as well, from a cache of their own: resolving one never changes
-what ``keys()`` reports.  ``names()`` is everything a ``--model`` flag can name.
+what ``keys()`` reports.  The cold-start trainer CLCRec resolves the same way from a third table and is not part of
+``names()`` either (both listings are pinned); ``resolvable()`` is everything a ``--model`` flag can name.
 """
 import importlib
 
 _BUILTIN = {'MF': ('.MF', 'MF'), 'LightGCN': ('.LightGCN', 'LightGCN'), 'DropoutNet': ('.DropoutNet', 'DropoutNet')}
 _CONTRASTIVE = {'SimGCL': ('.SimGCL', 'SimGCL'), 'XSimGCL': ('.XSimGCL', 'XSimGCL')}
+_COLD = {'CLCRec': ('.CLCRec', 'CLCRec')}
 _contrastive_cache = {}
+_cold_cache = {}
 
 
 class _Registry(dict):
@@ -22,6 +25,11 @@ class _Registry(dict):
                 mod, cls = _CONTRASTIVE[name]
                 _contrastive_cache[name] = getattr(importlib.import_module(mod, __name__), cls)
             return _contrastive_cache[name]
+        if name in _COLD:
+            if name not in _cold_cache:
+                mod, cls = _COLD[name]
+                _cold_cache[name] = getattr(importlib.import_module(mod, __name__), cls)
+            return _cold_cache[name]
         if name not in _BUILTIN:
             raise KeyError(name)
         mod, cls = _BUILTIN[name]
@@ -35,7 +43,7 @@ class _Registry(dict):
             return default
 
     def __contains__(self, name):
-        return name in _BUILTIN or name in _CONTRASTIVE or dict.__contains__(self, name)
+        return name in _BUILTIN or name in _CONTRASTIVE or name in _COLD or dict.__contains__(self, name)
 
     def keys(self):
         return sorted(set(_BUILTIN) | set(dict.keys(self)))
@@ -44,8 +52,16 @@ class _Registry(dict):
         """Every model name that resolves: core + contrastive + registered."""
         return sorted(set(_BUILTIN) | set(_CONTRASTIVE) | set(dict.keys(self)))
 
+    def resolvable(self):
+        """Everything a ``--model`` flag can name: ``names()`` + the cold-start trainers."""
+        return sorted(set(self.names()) | set(_COLD))
+
 
 AVAILABLE_MODELS = _Registry()
+
+
+def resolvable():
+    return AVAILABLE_MODELS.resolvable()
 
 
 def register(name, cls):

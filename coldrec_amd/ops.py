@@ -867,6 +867,126 @@ def infonce(view1: torch.Tensor, view2: torch.Tensor, tau: float, b_cos: bool = 
     return loss, grad1, grad2
 
 
+# ---- CLCRec's contrastive loss (clcrec.hip) --------------------------------------------------------------------------
+
+def clcrec_max_neg() -> int:
+    return int(_lib.lib().crh_clcrec_max_neg())
+
+
+def clcrec_workspace_bytes(batch: int, n_neg: int, d: int, n_slots: int) -> int:
+    return int(_lib.lib().crh_clcrec_workspace_bytes(int(batch), int(n_neg), int(d), int(n_slots)))
+
+
+def clcrec_workspace(batch: int, n_neg: int, d: int, n_slots: int, device) -> torch.Tensor:
+    return torch.empty(max(clcrec_workspace_bytes(batch, n_neg, d, n_slots), 1), dtype=torch.uint8, device=device)
+
+
+def clcrec_plan(users: torch.Tensor, items: torch.Tensor, n_users: Optional[int] = None,
+                n_items: Optional[int] = None) -> dict:
+    """The index side of one crh_clcrec_f32 step.  users (B,), items (B, 1 + G): integer device tensors (column 0 = the
+    positive).  Returns int32 device tensors: users, items (flat), slot (the feat row of every flat row), slot_item (the
+    distinct items, ascending: what the encoder has to encode), and the inverse indices -- the flat rows grouped by slot
+    (slot_ptr, slot_rows; a stable sort, so ascending inside a slot), the slots' rows cut into chunks of
+    crh_clcrec_chunk_rows() (chunk_ptr, chunk_slot), the records grouped by user (user_ids, user_ptr, user_recs).
+    With n_users / n_items given, ids outside the tables raise instead of reaching the kernel."""
+    _need_cuda(users, items)
+    if users.dim() != 1 or items.dim() != 2 or items.shape[0] != users.shape[0] or items.shape[1] < 2 or users.shape[0] < 1:
+        raise RuntimeError("clcrec_plan: users must be (B,) and items (B, 1 + G) with B >= 1, G >= 1")
+    if users.dtype.is_floating_point or items.dtype.is_floating_point or users.device != items.device:
+        raise RuntimeError("clcrec_plan: users and items must be integer tensors on one device")
+    dev, i32 = users.device, torch.int32
+    flat = items.reshape(-1).long()
+    ulong = users.long()
+    if n_users is not None and (int(ulong.min()) < 0 or int(ulong.max()) >= n_users):
+        raise RuntimeError("clcrec_plan: user id outside the user table")
+    if n_items is not None and (int(flat.min()) < 0 or int(flat.max()) >= n_items):
+        raise RuntimeError("clcrec_plan: item id outside the item table")
+
+    def grouped(ids):
+        uniq, inv = torch.unique(ids, return_inverse=True)
+        order = torch.sort(inv, stable=True).indices
+        cnt = torch.bincount(inv, minlength=uniq.shape[0])
+        ptr = torch.zeros(uniq.shape[0] + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(cnt, 0, out=ptr[1:])
+        return uniq, inv, order, cnt, ptr
+
+    slot_item, slot, slot_rows, cnt, slot_ptr = grouped(flat)
+    chunk = int(_lib.lib().crh_clcrec_chunk_rows())
+    nch = (cnt + (chunk - 1)) // chunk
+    chunk_ptr = torch.zeros(slot_item.shape[0] + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(nch, 0, out=chunk_ptr[1:])
+    chunk_slot = torch.repeat_interleave(torch.arange(slot_item.shape[0], device=dev), nch)
+    user_ids, _, user_recs, _, user_ptr = grouped(ulong)
+    c = lambda t: t.to(i32).contiguous()
+    return dict(batch=int(users.shape[0]), n_neg=int(items.shape[1] - 1), n_slots=int(slot_item.shape[0]),
+                n_chunks=int(chunk_slot.shape[0]), n_users=int(user_ids.shape[0]),
+                user_range=(int(user_ids[0]), int(user_ids[-1])), item_range=(int(slot_item[0]), int(slot_item[-1])),
+                users=c(ulong), items=c(flat), slot=c(slot), slot_item=c(slot_item), slot_ptr=c(slot_ptr),
+                slot_rows=c(slot_rows), chunk_ptr=c(chunk_ptr), chunk_slot=c(chunk_slot), user_ids=c(user_ids),
+                user_ptr=c(user_ptr), user_recs=c(user_recs))
+
+
+def clcrec(user_table: torch.Tensor, item_table: torch.Tensor, feat: torch.Tensor, plan: dict, mix_count: torch.Tensor,
+           temp: float, lr_lambda: float, reg: float, scale: float = 1.0, grad_user=None, grad_item=None, grad_feat=None,
+           loss=None, workspace=None, want_user: bool = True, want_item: bool = True, want_feat: bool = True):
+    """CLCRec's loss and its three gradients in one call (crh_clcrec_f32).  user_table (nu, d), item_table (ni, d), feat
+    (plan['n_slots'], d): fp32 contiguous, d % 4 == 0 <= 256; plan: ``clcrec_plan``; mix_count: int32 (B (1 + G),), how often
+    the step's random index drew each flat row.  Returns (loss4 = [L1, L2, R, total], grad_user, grad_item, grad_feat);
+    gradients are d total / d table * scale, zero at rows the batch does not touch; one that is neither given nor wanted
+    is not computed (None)."""
+    _need_cuda(user_table, item_table, feat, mix_count, grad_user, grad_item, grad_feat, loss, workspace)
+    dev = user_table.device
+    for t in (user_table, item_table, feat):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise RuntimeError("clcrec: tables and feat must be contiguous 2-D float32 tensors")
+    d = user_table.shape[1]
+    if item_table.shape[1] != d or feat.shape[1] != d:
+        raise RuntimeError("clcrec: tables and feat differ in width")
+    if d % 4 != 0 or d < 4 or d > 256:
+        raise RuntimeError(f"clcrec: width {d} must be a multiple of 4 in [4, 256]")
+    B, G, S = plan["batch"], plan["n_neg"], plan["n_slots"]
+    if feat.shape[0] != S:
+        raise RuntimeError("clcrec: feat must have one row per slot of the plan")
+    if plan["user_range"][0] < 0 or plan["user_range"][1] >= user_table.shape[0] or plan["item_range"][0] < 0 \
+            or plan["item_range"][1] >= item_table.shape[0]:
+        raise RuntimeError("clcrec: the plan's ids lie outside the tables")
+    if mix_count.dtype != torch.int32 or not mix_count.is_contiguous() or mix_count.numel() != B * (1 + G):
+        raise RuntimeError("clcrec: mix_count must be a contiguous int32 tensor of B * (1 + G) elements")
+    for t in (item_table, feat, mix_count, plan["users"], grad_user, grad_item, grad_feat, loss, workspace):
+        if t is not None and t.device != dev:
+            raise RuntimeError("clcrec: every tensor must be on the tables' device")
+
+    def grad_buffer(g, like, want, touched_all):
+        if g is None:
+            if not want:
+                return None
+            return torch.empty_like(like) if touched_all else torch.zeros_like(like)
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != like.shape:
+            raise RuntimeError("clcrec: gradient buffers must be contiguous float32 tensors of the tables' shapes")
+        return g
+
+    grad_user = grad_buffer(grad_user, user_table, want_user, False)
+    grad_item = grad_buffer(grad_item, item_table, want_item, False)
+    grad_feat = grad_buffer(grad_feat, feat, want_feat, True)
+    if loss is None:
+        loss = torch.empty(4, dtype=torch.float32, device=dev)
+    elif loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 4:
+        raise RuntimeError("clcrec: loss must be a contiguous float32 buffer of at least four elements")
+    if workspace is None:
+        workspace = clcrec_workspace(B, G, d, S, dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise RuntimeError("clcrec: workspace must be a contiguous uint8 tensor")
+    p = plan
+    _lib.check(_lib.lib().crh_clcrec_f32(
+        _lib.ptr(user_table), _lib.ptr(item_table), _lib.ptr(feat), _lib.ptr(p["users"]), _lib.ptr(p["items"]),
+        _lib.ptr(p["slot"]), _lib.ptr(p["slot_item"]), _lib.ptr(mix_count), _lib.ptr(p["slot_ptr"]), _lib.ptr(p["slot_rows"]),
+        _lib.ptr(p["chunk_ptr"]), _lib.ptr(p["chunk_slot"]), int(p["n_chunks"]), _lib.ptr(p["user_ids"]),
+        _lib.ptr(p["user_ptr"]), _lib.ptr(p["user_recs"]), int(p["n_users"]), int(B), int(G), int(d), int(S), float(temp),
+        float(lr_lambda), float(reg), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item), _lib.ptr(grad_feat),
+        _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_clcrec_f32")
+    return loss, grad_user, grad_item, grad_feat
+
+
 # ---- SimGCL / XSimGCL layer perturbation (perturb.hip) ---------------------------------------------------------------
 
 def _perturb_checks(what: str, y: torch.Tensor, *others) -> None:

@@ -501,6 +501,40 @@ int crh_infonce_f32(const float* view1, const int32_t* rows1, const float* view2
                     float* grad1, float* grad2, float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The contrastive loss of CLCRec (reference model/CLCRec.py:117-153), forward and backward in one call.  B records, each
+ * the user users[b] and 1 + G items items[b (1+G) + g] (g = 0 the positive); feat holds the content encoder's output once
+ * per DISTINCT item of the batch: slot[r] = the feat row of flat row r, slot_item[s] = the item id feat row s encodes.
+ *     h_b = normalize(V[it_b0])   Z_bg = normalize(F_bg)   X_bg = mix_count[bg] > 0 ? F_bg : V[it_bg]
+ *     L1 = mean_b(lse_g <h_b, Z_bg>/T - <h_b, Z_b0>/T)    L2 = mean_b(lse_g <U[u_b], X_bg>/T - <U[u_b], X_b0>/T)
+ *     R = (mean_b |U[u_b]| + mean_bg |V[it_bg]|) / 2      total = lr_lambda L1 + (1 - lr_lambda) L2 + reg R
+ *   mix_count      int32 per flat row: how often the step's random index drew that row.  A COUNT, not a flag: the
+ *                  reference assigns through an index with duplicates and autograd hands each duplicate the full
+ *                  gradient, so grad_feat carries mix_count times the second softmax's term
+ *   inverse indices (ops.clcrec_plan builds them): slot_rows = the flat rows grouped by slot, ascending inside a slot,
+ *                  slot_ptr[n_slots + 1] their offsets; every slot's rows are cut into chunks of crh_clcrec_chunk_rows()
+ *                  rows: chunk_ptr[n_slots + 1] = offsets into the chunk list, chunk_slot[n_chunks] = each chunk's slot;
+ *                  user_ids[n_users] = the distinct users, user_recs = the records grouped by user (ascending inside a
+ *                  user), user_ptr[n_users + 1] their offsets
+ *   grad_*         d total / d table * scale, written at the touched rows only (users of the batch, items of the batch,
+ *                  every feat row); any may be NULL (not computed; the others keep their bits)
+ *   loss_out       4 device floats: L1, L2, R, total; NULL = not written
+ *   workspace      crh_clcrec_workspace_bytes(batch, n_neg, d, n_slots) bytes, 256-byte aligned
+ * d % 4 == 0, 4 <= d <= 256; 1 <= n_neg <= crh_clcrec_max_neg(); batch (1 + n_neg) < 2^31; tables and gradients 16-byte
+ * aligned.  No atomics, every sum in a fixed order: two identical calls give identical bits.  One wave per record, then
+ * one wave per chunk of a slot's rows, the chunks' partial sums added in chunk order; one wave per distinct user.
+ */
+int crh_clcrec_max_neg(void);
+int crh_clcrec_chunk_rows(void);
+size_t crh_clcrec_workspace_bytes(int64_t batch, int n_neg, int d, int64_t n_slots);
+int crh_clcrec_f32(const float* user_table, const float* item_table, const float* feat, const int32_t* users,
+                   const int32_t* items, const int32_t* slot, const int32_t* slot_item, const int32_t* mix_count,
+                   const int32_t* slot_ptr, const int32_t* slot_rows, const int32_t* chunk_ptr, const int32_t* chunk_slot,
+                   int64_t n_chunks, const int32_t* user_ids, const int32_t* user_ptr, const int32_t* user_recs,
+                   int64_t n_users, int64_t batch, int n_neg, int d, int64_t n_slots, float temp, float lr_lambda,
+                   float reg, float scale, float* grad_user, float* grad_item, float* grad_feat, float* loss_out,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The layer perturbation of SimGCL / XSimGCL (model/SimGCL.py:106-108), in place on one (n_rows, d) fp32 layer output
  * of the propagation, d % 4 == 0, 4 <= d <= 256, every pointer 16-byte aligned.  Per row, r = the row's d uniforms:
  *     nrm = max(sqrt(sum r^2), 1e-12)                       (F.normalize's clamp)
