@@ -42,6 +42,12 @@ SIGNATURES = {
                                   _vp, _sz, _vp]),
     "crh_score_topk_f32_ex": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp,
                                      _vp, _sz, _vp, _i32, _vp, _vp]),
+    "crh_score_screen_items_bytes": (_sz, [_i64, _i32]),
+    "crh_score_screen_items_prepare": (_i32, [_vp, _i64, _i32, _vp, _i64, _i64, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "crh_score_screen_items_destroy": (_i32, [_vp]),
+    "crh_score_topk_screen_item_preps": (_i64, []),
+    "crh_score_topk_f32_prepared": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp,
+                                           _vp, _sz, _vp, _i32, _vp, _vp, _vp]),
     "crh_score_topk_f16_supports_dim": (_i32, [_i32]),
     "crh_score_topk_f16_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "crh_score_topk_f16_ex": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp,

@@ -560,23 +560,27 @@ int launch_screen_map(const uint32_t* bitmap, int64_t item_base, int64_t n_items
     return CRH_OK;
 }
 
-int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, int64_t prefix, int32_t* idmap, unsigned* scan,
-                       const ScreenOrder* ord, hipStream_t st) {
+int launch_screen_prep_items(const ScreenArgs& s, unsigned* stats, _Float16* packed, int64_t prefix, int32_t* idmap, unsigned* scan,
+                             const ScreenOrder* ord, hipStream_t st) {
     const int64_t T = (s.n_items + 31) / 32;     // (compacted: the upper bound; the kernel walks the live tiles)
     if (ord != nullptr)
-        hipLaunchKernelGGL(screen_maxabs_kernel<true>, dim3(2048), dim3(256), 0, st, s.item_emb, nullptr, s.n_items, s.stats, 0, ord->rowkeys);
+        hipLaunchKernelGGL(screen_maxabs_kernel<true>, dim3(2048), dim3(256), 0, st, s.item_emb, nullptr, s.n_items, stats, 0, ord->rowkeys);
     else
-        hipLaunchKernelGGL(screen_maxabs_kernel<false>, dim3(2048), dim3(256), 0, st, s.item_emb, nullptr, s.n_items, s.stats, 0, nullptr);
-    CRH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(screen_maxabs_kernel<false>, dim3(256), dim3(256), 0, st, s.user_emb, s.users, s.n_users, s.stats, 1, nullptr);
+        hipLaunchKernelGGL(screen_maxabs_kernel<false>, dim3(2048), dim3(256), 0, st, s.item_emb, nullptr, s.n_items, stats, 0, nullptr);
     CRH_HIP(hipGetLastError());
     if (idmap != nullptr) {
-        const int rc = launch_screen_map(s.bitmap, s.item_base, s.n_items, prefix, s.stats + SCREEN_STAT_LIVE, scan, idmap, ord, st);
+        const int rc = launch_screen_map(s.bitmap, s.item_base, s.n_items, prefix, stats + SCREEN_STAT_LIVE, scan, idmap, ord, st);
         if (rc != CRH_OK) return rc;
         if (ord != nullptr) idmap = ord->idmap;
     }
     hipLaunchKernelGGL(screen_items_kernel, dim3((unsigned)(T < 4096 ? T : 4096)), dim3(256), 0, st, s.item_emb, s.n_items, s.bitmap,
-                       s.item_base, packed, s.stats, prefix, idmap);
+                       s.item_base, packed, stats, prefix, idmap);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+int launch_screen_prep_users(const ScreenArgs& s, _Float16* uh, hipStream_t st) {
+    hipLaunchKernelGGL(screen_maxabs_kernel<false>, dim3(256), dim3(256), 0, st, s.user_emb, s.users, s.n_users, s.stats, 1, nullptr);
     CRH_HIP(hipGetLastError());
     const int64_t ub = (s.n_users * 16 + 255) / 256;
     hipLaunchKernelGGL(screen_users_kernel, dim3((unsigned)(ub < 2048 ? ub : 2048)), dim3(256), 0, st, s.user_emb, s.users, s.n_users,

@@ -37,6 +37,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 #include "score_topk_common.h"
@@ -1074,10 +1075,51 @@ bool screen_route(int esz, int64_t n_users, int64_t n_items, int d, int k, size_
     return !r.dense && r.use_dma && r.dma_mode == 3;
 }
 
+// The ITEM half of stage 0 built once per table (crh_score_screen_items_prepare): what launch_screen_prep_items and
+// tile_bits_kernel leave for stages 1 and 2, in a buffer the caller owns, and what it was built for.  A screened call that is
+// handed one uses it when everything recorded here equals what the call would build itself (screen_items_match); any other call
+// rebuilds in its workspace.  The buffer, front to back: the stats block (item words set, stats[1] and stats[5] zero), the packed
+// fp16 copy, then under a bitmap the tile bits of the uncompacted form and the map stage 1 streams by (the sorted one when
+// ordered, else the ascending one; unused when not compacted).
+constexpr uint32_t SCREEN_ITEMS_MAGIC = 0x43524849u;
+struct ScreenItems {
+    uint32_t magic;
+    const float* item_emb;
+    int64_t n_items, item_base, prefix;
+    int d;
+    const uint32_t* bitmap;
+    bool compact, ordered;
+    hipStream_t stream;
+    char* buf;
+};
+struct ScreenItemsLayout {
+    size_t stats, packed, tbits, map, need;
+};
+ScreenItemsLayout screen_items_layout(int64_t n_items, bool has_bitmap) {
+    ScreenItemsLayout L;
+    L.stats = 0;
+    L.packed = 256;
+    L.tbits = L.packed + packed_bytes(n_items, 128, 2);
+    L.map = L.tbits + (has_bitmap ? tbits_bytes(n_items) : 0);
+    const size_t slots = (size_t)screen_map_slots(n_items);      // (of the whole shard, prefix or not: monotonic in n_items)
+    L.need = L.map + (has_bitmap ? (slots * sizeof(int32_t) + 255) & ~(size_t)255 : 0);
+    return L;
+}
+// CRH_SCORE_SCREEN_PREPARED (read per call): 1 (default) a screened call uses a matching prepared state; 0 ignores it.
+bool screen_items_match(const ScreenItems* p, const float* item_emb, int64_t n_items, int64_t item_base, const uint32_t* bitmap,
+                        int64_t prefix, bool compact, bool ordered, hipStream_t st) {
+    if (p == nullptr || p->magic != SCREEN_ITEMS_MAGIC) return false;
+    const char* e = getenv("CRH_SCORE_SCREEN_PREPARED");
+    if (e && atoi(e) == 0) return false;
+    return p->item_emb == item_emb && p->n_items == n_items && p->d == 128 && p->item_base == item_base && p->bitmap == bitmap &&
+           p->prefix == prefix && p->compact == compact && p->ordered == ordered && p->stream == st;
+}
+std::atomic<int64_t> screen_item_preps{0};      // runs of the item half in this process (crh_score_topk_screen_item_preps)
+
 int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_users, const float* item_emb, int64_t n_items,
                         const int64_t* rated_rowptr, const int32_t* rated_col, const uint32_t* cand_bitmap, int k, int64_t item_base,
                         float* out_score, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream,
-                        void* ev_kernel_start, void* ev_kernel_stop, const char* who);
+                        void* ev_kernel_start, void* ev_kernel_stop, const char* who, const ScreenItems* prepared);
 
 // esz = 4: fp32 tables, exact fp32 MFMA (canonical fma chain).  esz = 2: fp16 tables, fp32 accumulate.
 // Route of a call (n_splits == 0; a caller that names a split count gets the plain fused selection):
@@ -1091,12 +1133,12 @@ int score_topk_any(int esz, const void* user_emb, const int32_t* users, int64_t 
                    int64_t n_items, int d, const int64_t* rated_rowptr, const int32_t* rated_col,
                    const uint32_t* cand_bitmap, int k, int64_t item_base, float* out_score, int32_t* out_idx,
                    void* workspace, size_t workspace_bytes, void* stream, int n_splits, void* ev_kernel_start,
-                   void* ev_kernel_stop, const char* who) {
+                   void* ev_kernel_stop, const char* who, const ScreenItems* prepared = nullptr) {
     if (user_emb && item_emb && out_score && out_idx && workspace &&
         screen_route(esz, n_users, n_items, d, k, workspace_bytes, cand_bitmap != nullptr, n_splits))
         return score_topk_screened(reinterpret_cast<const float*>(user_emb), users, n_users, reinterpret_cast<const float*>(item_emb),
                                    n_items, rated_rowptr, rated_col, cand_bitmap, k, item_base, out_score, out_idx, workspace,
-                                   workspace_bytes, stream, ev_kernel_start, ev_kernel_stop, who);
+                                   workspace_bytes, stream, ev_kernel_start, ev_kernel_stop, who, prepared);
     // the seeded route's own predicate and prefix (shared with the workspace query: seed_route)
     const int64_t P = n_splits == 0 ? seed_route(esz, n_users, n_items, d) : 0;
     if (P > 0 && user_emb && item_emb && out_score && out_idx && n_users > 0 && k >= 1 && k <= CRH_MAX_K && workspace) {
@@ -1408,12 +1450,27 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
     return CRH_OK;
 }
 
+// The item half of stage 0 (the stats block zeroed before): launch_screen_prep_items, and for a bitmap that is not compacted away
+// the tile bits of the main range (tbits != NULL).  The one place it runs, in a call's workspace or into a prepared state.
+int screen_items_build(const ScreenArgs& s, unsigned* stats, _Float16* pk, int64_t P, int32_t* idmap, unsigned* scan,
+                       const ScreenOrder* ord, uint32_t* tbits, hipStream_t st) {
+    screen_item_preps.fetch_add(1, std::memory_order_relaxed);
+    const int rc = launch_screen_prep_items(s, stats, pk, P, idmap, scan, ord, st);
+    if (rc != CRH_OK) return rc;
+    if (tbits != nullptr) {
+        const int64_t n_main = s.n_items - P, T = (n_main + 31) / 32;
+        hipLaunchKernelGGL(tile_bits_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, s.bitmap, s.item_base + P, n_main, T, tbits);
+        CRH_HIP(hipGetLastError());
+    }
+    return CRH_OK;
+}
+
 // The screened route (see screen_route and score_screen.hip).  No host synchronisation: the fallback reads the count of uncertified
 // users from the device.
 int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_users, const float* item_emb, int64_t n_items,
                         const int64_t* rated_rowptr, const int32_t* rated_col, const uint32_t* cand_bitmap, int k, int64_t item_base,
                         float* out_score, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream,
-                        void* ev_kernel_start, void* ev_kernel_stop, const char* who) {
+                        void* ev_kernel_start, void* ev_kernel_stop, const char* who, const ScreenItems* prepared) {
     CRH_CHECK_ARG(((uintptr_t)user_emb & 15) == 0 && ((uintptr_t)item_emb & 15) == 0, "%s: tables must be 16-byte aligned", who);
     CRH_CHECK_ARG(rated_rowptr != nullptr || rated_col == nullptr, "%s: rated_col given without rated_rowptr", who);
     CRH_CHECK_ARG(item_base >= 0 && item_base + n_items < (int64_t)CRH_PAD_IDX, "%s: item ids exceed int32", who);
@@ -1436,7 +1493,13 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
         ord.sort_tmp = ws + L.sorttmp;
         ord.sort_tmp_bytes = screen_sort_bytes((int64_t)slots);
     }
-    _Float16* pk = reinterpret_cast<_Float16*>(ws + L.packed);
+    // a prepared item half built for this table, bitmap and plan: stage 0 runs its user half only, stage 1 reads the prepared copy
+    const bool reuse = screen_items_match(prepared, item_emb, n_items, item_base, cand_bitmap, P, compact, ordered, st);
+    const ScreenItemsLayout PL = screen_items_layout(n_items, cand_bitmap != nullptr);
+    _Float16* pk = reinterpret_cast<_Float16*>(reuse ? prepared->buf + PL.packed : ws + L.packed);
+    uint32_t* tbits = cand_bitmap && !compact ? reinterpret_cast<uint32_t*>(reuse ? prepared->buf + PL.tbits : ws + L.tbits) : nullptr;
+    const int32_t* stream_map = nullptr;        // compacted: the map stage 1 streams by
+    if (compact) stream_map = reuse ? reinterpret_cast<const int32_t*>(prepared->buf + PL.map) : (ordered ? ord.idmap : idmap);
     _Float16* uh = reinterpret_cast<_Float16*>(ws + L.uh);
     float* seed_s = reinterpret_cast<float*>(ws + L.seed);
     int32_t* seed_i = reinterpret_cast<int32_t*>(seed_s + (size_t)n_users * KP);
@@ -1470,8 +1533,15 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     s.out_idx = out_idx;
 
     // ---- stage 0: fp16 copies (items packed, users in `users` order) and the norms of the bound
-    CRH_HIP(hipMemsetAsync(s.stats, 0, 256, st));
-    int rc = launch_screen_prep(s, pk, uh, P, idmap, reinterpret_cast<unsigned*>(ws + L.scan), ordered ? &ord : nullptr, st);
+    int rc = CRH_OK;
+    if (reuse) {     // the prepared stats block carries the item words, zeros in the user scale and the uncertified count
+        CRH_HIP(hipMemcpyAsync(s.stats, prepared->buf + PL.stats, 256, hipMemcpyDeviceToDevice, st));
+    } else {
+        CRH_HIP(hipMemsetAsync(s.stats, 0, 256, st));
+        rc = screen_items_build(s, s.stats, pk, P, idmap, reinterpret_cast<unsigned*>(ws + L.scan), ordered ? &ord : nullptr, tbits, st);
+        if (rc != CRH_OK) return rc;
+    }
+    rc = launch_screen_prep_users(s, uh, st);
     if (rc != CRH_OK) return rc;
     if (ev_kernel_start) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_start), st));
 
@@ -1557,13 +1627,10 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
         }
     }
     if (compact) {               // the stream holds the unmasked rows only: no tile bits, the rows' ids instead
-        a.idmap = ordered ? ord.idmap : idmap;      // (ordered: one cut, the only launch that may stream another order)
+        a.idmap = stream_map;       // (ordered: one cut, the only launch that may stream another order)
         a.n_live = s.stats + SCREEN_STAT_LIVE;
     } else if (cand_bitmap) {
-        uint32_t* tb = reinterpret_cast<uint32_t*>(ws + L.tbits);
-        hipLaunchKernelGGL(tile_bits_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, cand_bitmap, a.item_base, n_main, T, tb);
-        CRH_HIP(hipGetLastError());
-        a.tile_bits = tb;
+        a.tile_bits = tbits;        // (of the main range: screen_items_build)
     }
 #ifdef CRH_PROFILE
     static const int timing = CRH_PROFILE_ENV("CRH_SCORE_TIMING");
@@ -1695,6 +1762,85 @@ extern "C" int crh_score_topk_screen_map(const uint32_t* bitmap, const float* it
                            reinterpret_cast<hipStream_t>(stream));
 }
 
+// The prepared item half of the screened route's stage 0 (ScreenItems).  Bytes of the caller's buffer: needs no GPU.
+extern "C" size_t crh_score_screen_items_bytes(int64_t n_items, int has_bitmap) {
+    if (n_items <= 0) return 0;
+    return screen_items_layout(n_items, has_bitmap != 0).need;
+}
+
+// Runs the item half for calls of n_users users with this workspace size (they decide whether the stream is compacted and
+// ordered) into items_buf, on `stream`, and returns the handle in *handle.  The workspace holds the temporaries (keys, scan words,
+// the sort's storage) where a call would put them.  No host synchronisation.
+extern "C" int crh_score_screen_items_prepare(const float* item_emb, int64_t n_items, int d, const uint32_t* cand_bitmap,
+                                              int64_t item_base, int64_t n_users, void* items_buf, size_t items_bytes,
+                                              void* workspace, size_t workspace_bytes, void* stream, void** handle) {
+    const char* who = "crh_score_screen_items_prepare";
+    CRH_CHECK_ARG(item_emb && items_buf && workspace && handle, "%s: NULL argument", who);
+    CRH_CHECK_ARG(d == 128, "%s: d=%d (the screened route ranks d=128 tables)", who, d);
+    CRH_CHECK_ARG(n_users > 0 && n_items > 0, "%s: empty block", who);
+    CRH_CHECK_ARG(((uintptr_t)item_emb & 15) == 0 && ((uintptr_t)items_buf & 255) == 0, "%s: table must be 16-byte, buffer 256-byte aligned", who);
+    CRH_CHECK_ARG(item_base >= 0 && item_base + n_items < (int64_t)CRH_PAD_IDX, "%s: item ids exceed int32", who);
+    const bool has_bitmap = cand_bitmap != nullptr;
+    const ScreenItemsLayout PL = screen_items_layout(n_items, has_bitmap);
+    CRH_CHECK_ARG(items_bytes >= PL.need, "%s: buffer %zu < %zu bytes", who, items_bytes, PL.need);
+    const int64_t P = screen_prefix(n_items);
+    const bool compact = screen_compact(n_users, n_items, workspace_bytes, has_bitmap);
+    const bool ordered = screen_ordered(n_users, n_items, workspace_bytes, has_bitmap);
+    const ScreenLayout L = screen_layout(n_users, n_items, P, compact, ordered);
+    CRH_CHECK_ARG(workspace_bytes >= L.need, "%s: workspace %zu < %zu bytes (screened route)", who, workspace_bytes, L.need);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* ws = reinterpret_cast<char*>(workspace);
+    char* buf = reinterpret_cast<char*>(items_buf);
+    int32_t* own_map = reinterpret_cast<int32_t*>(buf + PL.map);
+    ScreenOrder ord;
+    if (ordered) {       // the ascending map is a temporary of the sort; the state keeps the sorted one
+        const size_t slots = (size_t)screen_map_slots(n_items - P);
+        ord.rowkeys = reinterpret_cast<uint16_t*>(ws + L.rowkeys);
+        ord.skeys_in = reinterpret_cast<uint16_t*>(ws + L.skeys);
+        ord.skeys_out = reinterpret_cast<uint16_t*>(ws + L.skeys + (L.idmap2 - L.skeys) / 2);
+        ord.idmap = own_map;
+        ord.sort_tmp = ws + L.sorttmp;
+        ord.sort_tmp_bytes = screen_sort_bytes((int64_t)slots);
+    }
+    int32_t* idmap = compact ? (ordered ? reinterpret_cast<int32_t*>(ws + L.idmap) : own_map) : nullptr;
+    ScreenArgs s = {};
+    s.item_emb = item_emb;
+    s.n_items = n_items;
+    s.item_base = item_base;
+    s.bitmap = cand_bitmap;
+    unsigned* stats = reinterpret_cast<unsigned*>(buf + PL.stats);
+    CRH_HIP(hipMemsetAsync(stats, 0, 256, st));
+    const int rc = screen_items_build(s, stats, reinterpret_cast<_Float16*>(buf + PL.packed), P, idmap, reinterpret_cast<unsigned*>(ws + L.scan),
+                                      ordered ? &ord : nullptr, has_bitmap && !compact ? reinterpret_cast<uint32_t*>(buf + PL.tbits) : nullptr, st);
+    if (rc != CRH_OK) return rc;
+    ScreenItems* p = new ScreenItems;
+    p->magic = SCREEN_ITEMS_MAGIC;
+    p->item_emb = item_emb;
+    p->n_items = n_items;
+    p->item_base = item_base;
+    p->prefix = P;
+    p->d = d;
+    p->bitmap = cand_bitmap;
+    p->compact = compact;
+    p->ordered = ordered;
+    p->stream = st;
+    p->buf = buf;
+    *handle = p;
+    return CRH_OK;
+}
+
+extern "C" int crh_score_screen_items_destroy(void* handle) {
+    if (handle == nullptr) return CRH_OK;
+    ScreenItems* p = reinterpret_cast<ScreenItems*>(handle);
+    CRH_CHECK_ARG(p->magic == SCREEN_ITEMS_MAGIC, "crh_score_screen_items_destroy: not a prepared-items handle");
+    p->magic = 0;
+    delete p;
+    return CRH_OK;
+}
+
+// runs of the item half in this process, in a call's workspace or into a prepared state
+extern "C" int64_t crh_score_topk_screen_item_preps(void) { return screen_item_preps.load(std::memory_order_relaxed); }
+
 // Uncertified users of the last screened call that used this workspace (a workspace word; waits for `stream`).
 extern "C" int64_t crh_score_topk_uncertified(const void* workspace, void* stream) {
     CRH_CHECK_ARG(workspace != nullptr, "crh_score_topk_uncertified: NULL workspace");
@@ -1726,6 +1872,20 @@ extern "C" int crh_score_topk_f32_ex(const float* user_emb, const int32_t* users
     return score_topk_any(4, user_emb, users, n_users, item_emb, n_items, d, rated_rowptr, rated_col, cand_bitmap, k,
                           item_base, out_score, out_idx, workspace, workspace_bytes, stream, n_splits,
                           ev_kernel_start, ev_kernel_stop, "crh_score_topk_f32");
+}
+
+// crh_score_topk_f32_ex with a prepared item half (may be NULL): used when the call takes the screened route and the state was
+// built for this table, bitmap, base, stream and plan; otherwise the call is crh_score_topk_f32_ex.
+extern "C" int crh_score_topk_f32_prepared(const float* user_emb, const int32_t* users, int64_t n_users,
+                                           const float* item_emb, int64_t n_items, int d,
+                                           const int64_t* rated_rowptr, const int32_t* rated_col,
+                                           const uint32_t* cand_bitmap, int k, int64_t item_base,
+                                           float* out_score, int32_t* out_idx, void* workspace,
+                                           size_t workspace_bytes, void* stream, int n_splits,
+                                           void* ev_kernel_start, void* ev_kernel_stop, const void* prepared) {
+    return score_topk_any(4, user_emb, users, n_users, item_emb, n_items, d, rated_rowptr, rated_col, cand_bitmap, k,
+                          item_base, out_score, out_idx, workspace, workspace_bytes, stream, n_splits,
+                          ev_kernel_start, ev_kernel_stop, "crh_score_topk_f32", reinterpret_cast<const ScreenItems*>(prepared));
 }
 
 extern "C" int crh_score_topk_f32(const float* user_emb, const int32_t* users, int64_t n_users,

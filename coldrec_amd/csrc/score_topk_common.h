@@ -434,9 +434,14 @@ struct ScreenOrder {
 };
 __attribute__((visibility("hidden"))) int64_t screen_map_slots(int64_t n_main);
 __attribute__((visibility("hidden"))) size_t screen_sort_bytes(int64_t n_slots);
+// Stage 0 in its two halves.  The ITEM half depends on the shard and the bitmap alone (the table's scale into stats[0], the map and
+// its count into stats[SCREEN_STAT_LIVE], the packed copy, R, N, N^ into stats[2..4]), so a caller may run it once per table
+// (ScreenItems); the USER half (the users' scale into s.stats[1], their fp16 rows and norms) runs per call.  The item half reads
+// s.item_emb, s.n_items, s.item_base and s.bitmap only and writes `stats`, which need not be s.stats.
 // ord != NULL (needs idmap): stage 1 and the packed copy follow ord->idmap
-__attribute__((visibility("hidden"))) int launch_screen_prep(const ScreenArgs& s, _Float16* packed, _Float16* uh, int64_t prefix,
-                                                             int32_t* idmap, unsigned* scan, const ScreenOrder* ord, hipStream_t st);
+__attribute__((visibility("hidden"))) int launch_screen_prep_items(const ScreenArgs& s, unsigned* stats, _Float16* packed, int64_t prefix,
+                                                                   int32_t* idmap, unsigned* scan, const ScreenOrder* ord, hipStream_t st);
+__attribute__((visibility("hidden"))) int launch_screen_prep_users(const ScreenArgs& s, _Float16* uh, hipStream_t st);
 __attribute__((visibility("hidden"))) int screen_map_only(const uint32_t* bitmap, const float* item_emb, int64_t n_items,
                                                           int64_t item_base, int64_t prefix, int ordered, int32_t* map_out,
                                                           int32_t* keys_out, int64_t* count, hipStream_t st);

@@ -81,14 +81,17 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
 def score_topk(user_emb: torch.Tensor, users: Optional[torch.Tensor], item_emb: torch.Tensor, k: int,
                rated_rowptr: Optional[torch.Tensor] = None, rated_col: Optional[torch.Tensor] = None,
                cand_bitmap: Optional[torch.Tensor] = None, item_base: int = 0, n_splits: int = 0,
-               out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, kernel_events=None, pack: bool = True):
+               out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, kernel_events=None, pack: bool = True,
+               prepared: Optional["PreparedItems"] = None):
     """Fused ``user_emb[users] @ item_emb.T`` -> masks -> top-k (model/MF.py:58-63 +
     model/BaseRecommender.py:175-182).  Returns (scores fp32, global item ids int32), each
     (n_users, k), canonical order.  fp32 tables: exact fp32 MFMA, bit-identical to the oracle's fma chain;
     fp16 tables (both): fp16 MFMA with fp32 accumulation (config 5, generated embeddings).  ``users`` int32 rows of user_emb or None for all rows.
     ``kernel_events``: optional (hipEvent_t, hipEvent_t) raw handles recorded around the scoring
     kernel alone (bench.py's roofline measurement).  ``pack=False`` withholds the workspace for the
-    fragment-ordered copy of the item shard (row-major kernel: same results, less memory, ~0.9x speed)."""
+    fragment-ordered copy of the item shard (row-major kernel: same results, less memory, ~0.9x speed).
+    ``prepared``: a ``PreparedItems`` of ``prepare_items`` for this table, bitmap and base; a call that takes the screened route
+    then skips the item half of its stage 0.  A state that does not fit the call is ignored: same results, nothing saved."""
     _need_cuda(user_emb, users, item_emb, rated_rowptr, rated_col, cand_bitmap)
     if user_emb.dtype != item_emb.dtype or user_emb.dtype not in (torch.float32, torch.float16):
         raise RuntimeError("score_topk: both tables fp32 (exact, canonical) or both fp16 (fp32 accumulate)")
@@ -113,14 +116,101 @@ def score_topk(user_emb: torch.Tensor, users: Optional[torch.Tensor], item_emb: 
     full = L.crh_score_topk_f16_workspace_bytes if half else L.crh_score_topk_workspace_bytes
     ws_bytes = full(n_users, n_items, d, k) if pack else L.crh_score_topk_min_workspace_bytes(n_users, k)
     ws = _workspace(ws_bytes, dev)
-    rc = (L.crh_score_topk_f16_ex if half else L.crh_score_topk_f32_ex)(_lib.ptr(user_emb), _lib.ptr(users), n_users, _lib.ptr(item_emb), n_items, d,
-                                 _lib.ptr(rated_rowptr), _lib.ptr(rated_col), _lib.ptr(cand_bitmap), k,
-                                 item_base, _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(ws), ws_bytes,
-                                 _lib.current_stream(), n_splits,
-                                 kernel_events[0] if kernel_events else None,
-                                 kernel_events[1] if kernel_events else None)
+    args = (_lib.ptr(user_emb), _lib.ptr(users), n_users, _lib.ptr(item_emb), n_items, d,
+            _lib.ptr(rated_rowptr), _lib.ptr(rated_col), _lib.ptr(cand_bitmap), k,
+            item_base, _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(ws), ws_bytes,
+            _lib.current_stream(), n_splits,
+            kernel_events[0] if kernel_events else None,
+            kernel_events[1] if kernel_events else None)
+    if prepared is not None and not half and pack and prepared.fits(item_emb, cand_bitmap, item_base):
+        # (built at first use, for this call's plan; the library compares the rest and ignores a state of another plan)
+        rc = L.crh_score_topk_f32_prepared(*args, prepared.handle_for(n_users, ws, ws_bytes))
+    else:
+        rc = (L.crh_score_topk_f16_ex if half else L.crh_score_topk_f32_ex)(*args)
     _lib.check(rc, "crh_score_topk_f32")
     return out
+
+
+class PreparedItems:
+    """The item half of the screened route's stage 0 (the packed fp16 copy of the shard, the live-row map under the candidate
+    bitmap, the maxima of the certificate's bound), built ONCE and handed to every ``score_topk`` call of an evaluation
+    (``prepared=``).  It owns a private device buffer -- never the shared scratch, which other ops overwrite -- and the native
+    handle, freed on deletion.
+
+    The native state is built at the first call that uses it, for that call's plan (user count and workspace decide whether the
+    fp16 pass is compacted and ordered), or explicitly by ``build(n_users, k)``.  Calls of another plan ignore it.
+
+    CONTRACT.  The state is a copy: the table and the bitmap must not change while it is in use.  In-place torch edits are seen
+    through the tensors' ``_version`` (``fits`` then fails and the call rebuilds per call); writes through raw pointers -- the
+    library's own optimiser kernels write that way -- are NOT seen: make a new ``PreparedItems`` after them.  This matters for
+    soundness, not only for speed: the certificate's R, N, N^ are those of the prepared copy."""
+
+    def __init__(self, item_emb: torch.Tensor, cand_bitmap: Optional[torch.Tensor] = None, item_base: int = 0):
+        _need_cuda(item_emb, cand_bitmap)
+        if item_emb.dtype != torch.float32 or item_emb.dim() != 2 or item_emb.shape[1] != 128 or not item_emb.is_contiguous():
+            raise RuntimeError("prepare_items: the screened route ranks contiguous fp32 tables of width 128")
+        if cand_bitmap is not None and (cand_bitmap.dtype != torch.int32 or not cand_bitmap.is_contiguous()):
+            raise RuntimeError("prepare_items: cand_bitmap must be contiguous int32 words")
+        self.item_emb, self.cand_bitmap, self.item_base = item_emb, cand_bitmap, int(item_base)
+        self.item_ptr, self.item_version = item_emb.data_ptr(), item_emb._version
+        self.bitmap_ptr = None if cand_bitmap is None else cand_bitmap.data_ptr()
+        self.bitmap_version = None if cand_bitmap is None else cand_bitmap._version
+        self.stream = torch.cuda.current_stream(item_emb.device).cuda_stream
+        nbytes = int(_lib.lib().crh_score_screen_items_bytes(item_emb.shape[0], 0 if cand_bitmap is None else 1))
+        self.buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=item_emb.device)
+        self.handle = None
+
+    def fits(self, item_emb: torch.Tensor, cand_bitmap: Optional[torch.Tensor], item_base: int = 0) -> bool:
+        """Was this state made for exactly these tensors, unchanged since, on the current stream?"""
+        if item_emb.data_ptr() != self.item_ptr or item_emb.shape != self.item_emb.shape or int(item_base) != self.item_base:
+            return False
+        if self.item_emb._version != self.item_version or item_emb._version != self.item_version:
+            return False
+        if (cand_bitmap is None) != (self.cand_bitmap is None):
+            return False
+        if cand_bitmap is not None and (cand_bitmap.data_ptr() != self.bitmap_ptr or cand_bitmap._version != self.bitmap_version
+                                        or self.cand_bitmap._version != self.bitmap_version):
+            return False
+        return torch.cuda.current_stream(item_emb.device).cuda_stream == self.stream
+
+    def handle_for(self, n_users: int, ws: torch.Tensor, ws_bytes: int):
+        if self.handle is None:
+            h = ctypes.c_void_p(None)
+            rc = _lib.lib().crh_score_screen_items_prepare(self.item_ptr, self.item_emb.shape[0], 128, self.bitmap_ptr, self.item_base,
+                                                           int(n_users), _lib.ptr(self.buf), self.buf.numel(), _lib.ptr(ws),
+                                                           int(ws_bytes), self.stream, ctypes.byref(h))
+            _lib.check(rc, "crh_score_screen_items_prepare")
+            self.handle = h
+        return self.handle
+
+    def build(self, n_users: int, k: int) -> "PreparedItems":
+        """Build the native state now, for ``score_topk`` calls of ``n_users`` users and this ``k`` on the current stream."""
+        if torch.cuda.current_stream(self.item_emb.device).cuda_stream != self.stream:
+            raise RuntimeError("PreparedItems.build: not the stream the state was made on")
+        ws_bytes = int(_lib.lib().crh_score_topk_workspace_bytes(int(n_users), self.item_emb.shape[0], 128, int(k)))
+        self.handle_for(n_users, _workspace(ws_bytes, self.item_emb.device), ws_bytes)
+        return self
+
+    def close(self) -> None:
+        h, self.handle = self.handle, None
+        if h is not None:
+            _lib.lib().crh_score_screen_items_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def prepare_items(item_emb: torch.Tensor, cand_bitmap: Optional[torch.Tensor] = None, item_base: int = 0) -> PreparedItems:
+    """A ``PreparedItems`` for ``score_topk(..., prepared=)``: see the class for what it holds and for its contract."""
+    return PreparedItems(item_emb, cand_bitmap, item_base)
+
+
+def screen_item_preps() -> int:
+    """Runs of the item half of the screened route's stage 0 in this process, prepared or inside a call (a host counter)."""
+    return int(_lib.lib().crh_score_topk_screen_item_preps())
 
 
 ROUTE_NAMES = {1: "dense", 2: "fused-wave", 3: "fused-wg", 4: "fused-dma"}

@@ -117,6 +117,39 @@ int crh_score_topk_screen_map(const uint32_t* bitmap, const float* item_emb, int
 int crh_score_topk_screened(int elem_bytes, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes,
                             int has_bitmap, int n_splits);
 int64_t crh_score_topk_uncertified(const void* workspace, void* stream);
+/* The screened route's PREPARED ITEMS.  Stage 0 of a screened call has an item half -- the table's scale and norm keys, the
+ * live-row map under the bitmap and its sort, the packed fp16 copy with the maxima R, N, N^ of the certificate's bound, the tile
+ * bits -- that depends on the item shard and the candidate bitmap alone.  An evaluation walks many user blocks against one
+ * frozen table, so a caller may run that half once into a device buffer of its own and hand it to every call:
+ *   crh_score_screen_items_bytes    bytes of that buffer for a shard of n_items rows, with or without a bitmap (no GPU needed);
+ *   crh_score_screen_items_prepare  runs the item half on `stream` into items_buf (256-byte aligned) for calls of n_users users
+ *                                   with a workspace of workspace_bytes (they decide whether the fp16 pass is compacted and
+ *                                   ordered); `workspace` holds the temporaries and may be the calls' own.  *handle receives a
+ *                                   small host object that records what the state was built for.  No host synchronisation;
+ *   crh_score_topk_f32_prepared     crh_score_topk_f32_ex plus that handle (or NULL).  The state is used only when the call takes
+ *                                   the screened route, item_emb, n_items, item_base, cand_bitmap, the prefix and `stream` are
+ *                                   those it was prepared with, and the call's own compact / ordered decisions equal the
+ *                                   state's; the call then runs only the user half of stage 0.  Any other call rebuilds in its
+ *                                   workspace: a mismatch is not an error.  CRH_SCORE_SCREEN_PREPARED (read per call): 1
+ *                                   (default) use a matching state, 0 ignore it.  Results are identical either way;
+ *   crh_score_screen_items_destroy  frees the handle (not the buffer, which the caller owns);
+ *   crh_score_topk_screen_item_preps  runs of the item half in this process so far, prepared or inside a call.
+ * CONTRACT: the handle compares pointers, not contents.  Between prepare and the last call that uses the handle neither the
+ * item rows nor the bitmap words may change, and items_buf must stay allocated and untouched; after a change, prepare again.  This
+ * is a matter of soundness, not only of speed: the certificate's R, N, N^ are those of the prepared copy. */
+size_t crh_score_screen_items_bytes(int64_t n_items, int has_bitmap);
+int crh_score_screen_items_prepare(const float* item_emb, int64_t n_items, int d, const uint32_t* cand_bitmap, int64_t item_base,
+                                   int64_t n_users, void* items_buf, size_t items_bytes, void* workspace, size_t workspace_bytes,
+                                   void* stream, void** handle);
+int crh_score_screen_items_destroy(void* handle);
+int64_t crh_score_topk_screen_item_preps(void);
+int crh_score_topk_f32_prepared(const float* user_emb, const int32_t* users, int64_t n_users,
+                                const float* item_emb, int64_t n_items, int d,
+                                const int64_t* rated_rowptr, const int32_t* rated_col,
+                                const uint32_t* cand_bitmap, int k, int64_t item_base,
+                                float* out_score, int32_t* out_idx, void* workspace,
+                                size_t workspace_bytes, void* stream, int n_splits,
+                                void* ev_kernel_start, void* ev_kernel_stop, const void* prepared);
 int crh_score_topk_f32(const float* user_emb, const int32_t* users, int64_t n_users,
                        const float* item_emb, int64_t n_items, int d,
                        const int64_t* rated_rowptr, const int32_t* rated_col,
