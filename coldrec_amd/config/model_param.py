@@ -41,4 +41,17 @@ def model_specific_param(model_name, parser, available_models):
         parser.add_argument('--lr_lambda', type=float, default=0.5, help='Weight of the embedding-content contrastive loss')
         parser.add_argument('--num_sample', type=float, default=0.5,
                             help='Share of the batch rows (drawn with replacement) scored on content instead of embedding')
+    if model_name == 'CCFCRec':      # config/model_param.py:130-144
+        parser.add_argument('--positive_number', type=int, default=5, help='Contrast positives per record')
+        parser.add_argument('--negative_number', type=int, default=40, help='Contrast negatives per positive')
+        parser.add_argument('--self_neg_number', type=int, default=40, help='Self-contrast negatives per record')
+        parser.add_argument('--tau', type=float, default=0.1, help='Contrast loss temperature')
+        parser.add_argument('--lambda1', type=float, default=0.6, help='Weight of the two contrast losses')
+        parser.add_argument('--attr_present_dim', type=int, default=64, help='Width of the attribute embeddings')
+        parser.add_argument('--implicit_dim', type=int, default=64, help='Width of the user / item tables')
+        parser.add_argument('--cat_implicit_dim', type=int, default=64, help='Hidden width of the generator')
+        parser.add_argument('--pretrain', type=_str2bool, default=False, nargs='?', const=True,
+                            help='Load both tables from ./emb/{dataset}_cold_item_{backbone}_{user,item}_emb.pt')
+        parser.add_argument('--pretrain_update', type=_str2bool, default=False, nargs='?', const=True,
+                            help='With --pretrain: train the loaded tables (true) or keep them frozen (false)')
     return parser

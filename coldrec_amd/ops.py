@@ -971,6 +971,17 @@ def clcrec_workspace(batch: int, n_neg: int, d: int, n_slots: int, device) -> to
     return torch.empty(max(clcrec_workspace_bytes(batch, n_neg, d, n_slots), 1), dtype=torch.uint8, device=device)
 
 
+def _grouped(ids: torch.Tensor):
+    """ids (M,) int64 -> (the distinct ids ascending, every position's index into them, the positions grouped by id -- a
+    stable sort, so ascending inside an id --, the groups' sizes and offsets)."""
+    uniq, inv = torch.unique(ids, return_inverse=True)
+    order = torch.sort(inv, stable=True).indices
+    cnt = torch.bincount(inv, minlength=uniq.shape[0])
+    ptr = torch.zeros(uniq.shape[0] + 1, dtype=torch.int64, device=ids.device)
+    torch.cumsum(cnt, 0, out=ptr[1:])
+    return uniq, inv, order, cnt, ptr
+
+
 def clcrec_plan(users: torch.Tensor, items: torch.Tensor, n_users: Optional[int] = None,
                 n_items: Optional[int] = None) -> dict:
     """The index side of one crh_clcrec_f32 step.  users (B,), items (B, 1 + G): integer device tensors (column 0 = the
@@ -992,21 +1003,13 @@ def clcrec_plan(users: torch.Tensor, items: torch.Tensor, n_users: Optional[int]
     if n_items is not None and (int(flat.min()) < 0 or int(flat.max()) >= n_items):
         raise RuntimeError("clcrec_plan: item id outside the item table")
 
-    def grouped(ids):
-        uniq, inv = torch.unique(ids, return_inverse=True)
-        order = torch.sort(inv, stable=True).indices
-        cnt = torch.bincount(inv, minlength=uniq.shape[0])
-        ptr = torch.zeros(uniq.shape[0] + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(cnt, 0, out=ptr[1:])
-        return uniq, inv, order, cnt, ptr
-
-    slot_item, slot, slot_rows, cnt, slot_ptr = grouped(flat)
+    slot_item, slot, slot_rows, cnt, slot_ptr = _grouped(flat)
     chunk = int(_lib.lib().crh_clcrec_chunk_rows())
     nch = (cnt + (chunk - 1)) // chunk
     chunk_ptr = torch.zeros(slot_item.shape[0] + 1, dtype=torch.int64, device=dev)
     torch.cumsum(nch, 0, out=chunk_ptr[1:])
     chunk_slot = torch.repeat_interleave(torch.arange(slot_item.shape[0], device=dev), nch)
-    user_ids, _, user_recs, _, user_ptr = grouped(ulong)
+    user_ids, _, user_recs, _, user_ptr = _grouped(ulong)
     c = lambda t: t.to(i32).contiguous()
     return dict(batch=int(users.shape[0]), n_neg=int(items.shape[1] - 1), n_slots=int(slot_item.shape[0]),
                 n_chunks=int(chunk_slot.shape[0]), n_users=int(user_ids.shape[0]),
@@ -1075,6 +1078,142 @@ def clcrec(user_table: torch.Tensor, item_table: torch.Tensor, feat: torch.Tenso
         float(lr_lambda), float(reg), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item), _lib.ptr(grad_feat),
         _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_clcrec_f32")
     return loss, grad_user, grad_item, grad_feat
+
+
+# ---- CCFCRec's loss (ccfcrec.hip) ------------------------------------------------------------------------------------
+
+def ccfcrec_max_rows() -> int:
+    return int(_lib.lib().crh_ccfcrec_max_rows())
+
+
+def ccfcrec_rows(n_pos: int, n_neg: int, n_self: int) -> int:
+    """R = 1 + P + P N + S: the item rows one record gathers."""
+    return 1 + int(n_pos) + int(n_pos) * int(n_neg) + int(n_self)
+
+
+def ccfcrec_workspace_bytes(batch: int, n_pos: int, n_neg: int, n_self: int, d: int, n_items: int, n_users: int) -> int:
+    return int(_lib.lib().crh_ccfcrec_workspace_bytes(int(batch), int(n_pos), int(n_neg), int(n_self), int(d),
+                                                      int(n_items), int(n_users)))
+
+
+def ccfcrec_workspace(batch: int, n_pos: int, n_neg: int, n_self: int, d: int, n_items: int, n_users: int,
+                      device) -> torch.Tensor:
+    return torch.empty(max(ccfcrec_workspace_bytes(batch, n_pos, n_neg, n_self, d, n_items, n_users), 1),
+                       dtype=torch.uint8, device=device)
+
+
+def _owner_chunks(ids: torch.Tensor, chunk: int):
+    """``_grouped`` with every group cut into chunks of ``chunk`` positions: (distinct ids, grouped positions, offsets,
+    offsets into the chunk list, each chunk's group)."""
+    uniq, _, order, cnt, ptr = _grouped(ids)
+    nch = (cnt + (chunk - 1)) // chunk
+    chunk_ptr = torch.zeros(uniq.shape[0] + 1, dtype=torch.int64, device=ids.device)
+    torch.cumsum(nch, 0, out=chunk_ptr[1:])
+    chunk_own = torch.repeat_interleave(torch.arange(uniq.shape[0], device=ids.device), nch)
+    return uniq, order, ptr, chunk_ptr, chunk_own
+
+
+def ccfcrec_plan(users: torch.Tensor, items: torch.Tensor, neg_users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
+                 self_neg: torch.Tensor, n_users: Optional[int] = None, n_items: Optional[int] = None) -> dict:
+    """The index side of one crh_ccfcrec_f32 step.  users, items, neg_users (B,), pos (B, P), neg (B, P, N), self_neg
+    (B, S): integer device tensors.  Returns int32 device tensors: users, neg_users, items (B R flat: the record's item, its
+    positives, negatives, self-negatives) and the inverse indices -- the flat rows grouped by item (item_ids, item_ptr,
+    item_occ; a stable sort, so ascending inside an item) and cut into chunks of crh_ccfcrec_chunk_rows() (item_chunk_ptr,
+    item_chunk_own), and the same over the 2B user occurrences (users, then neg_users).  With n_users / n_items given,
+    ids outside the tables raise instead of reaching the kernel."""
+    _need_cuda(users, items, neg_users, pos, neg, self_neg)
+    B = users.shape[0] if users.dim() == 1 else 0
+    if B < 1 or items.shape != (B,) or neg_users.shape != (B,) or pos.dim() != 2 or neg.dim() != 3 or self_neg.dim() != 2 \
+            or pos.shape[0] != B or neg.shape[:2] != pos.shape or self_neg.shape[0] != B or pos.shape[1] < 1 \
+            or neg.shape[2] < 1 or self_neg.shape[1] < 1:
+        raise RuntimeError("ccfcrec_plan: users, items, neg_users must be (B,), pos (B, P), neg (B, P, N), self_neg (B, S) "
+                           "with B, P, N, S >= 1")
+    ts = (users, items, neg_users, pos, neg, self_neg)
+    if any(t.dtype.is_floating_point or t.device != users.device for t in ts):
+        raise RuntimeError("ccfcrec_plan: the six index tensors must be integer tensors on one device")
+    i32 = torch.int32
+    P, N, S = int(pos.shape[1]), int(neg.shape[2]), int(self_neg.shape[1])
+    flat = torch.cat([items.long().view(B, 1), pos.long(), neg.long().reshape(B, P * N), self_neg.long()], 1).reshape(-1)
+    both = torch.cat([users.long(), neg_users.long()])
+    user_range, item_range = (int(both.min()), int(both.max())), (int(flat.min()), int(flat.max()))
+    if n_users is not None and (user_range[0] < 0 or user_range[1] >= n_users):
+        raise RuntimeError("ccfcrec_plan: user id outside the user table")
+    if n_items is not None and (item_range[0] < 0 or item_range[1] >= n_items):
+        raise RuntimeError("ccfcrec_plan: item id outside the item table")
+    chunk = int(_lib.lib().crh_ccfcrec_chunk_rows())
+    item_ids, item_occ, item_ptr, item_chunk_ptr, item_chunk_own = _owner_chunks(flat, chunk)
+    user_ids, user_occ, user_ptr, user_chunk_ptr, user_chunk_own = _owner_chunks(both, chunk)
+    c = lambda t: t.to(i32).contiguous()
+    return dict(batch=B, n_pos=P, n_neg=N, n_self=S, n_items=int(item_ids.shape[0]), n_users=int(user_ids.shape[0]),
+                n_item_chunks=int(item_chunk_own.shape[0]), n_user_chunks=int(user_chunk_own.shape[0]),
+                user_range=user_range, item_range=item_range, users=c(both[:B]), neg_users=c(both[B:]), items=c(flat),
+                item_ids=c(item_ids), item_ptr=c(item_ptr), item_occ=c(item_occ), item_chunk_ptr=c(item_chunk_ptr),
+                item_chunk_own=c(item_chunk_own), user_ids=c(user_ids), user_ptr=c(user_ptr), user_occ=c(user_occ),
+                user_chunk_ptr=c(user_chunk_ptr), user_chunk_own=c(user_chunk_own))
+
+
+def ccfcrec(user_table: torch.Tensor, item_table: torch.Tensor, q: torch.Tensor, plan: dict, tau: float, lambda1: float,
+            scale: float = 1.0, grad_user=None, grad_item=None, grad_q=None, loss=None, workspace=None,
+            want_user: bool = True, want_item: bool = True, want_q: bool = True):
+    """CCFCRec's loss and its three gradients in one call (crh_ccfcrec_f32).  user_table (nu, d), item_table (ni, d), q
+    (B, d) = the content encoder's output for the records' items: fp32 contiguous, d % 4 == 0 <= 256; plan:
+    ``ccfcrec_plan``.  Returns (loss5 = [L_c, L_s, L_r1, L_r2, total], grad_user, grad_item, grad_q); gradients are
+    d total / d table * scale, zero at rows the batch does not touch; one that is neither given nor wanted is not
+    computed (None).  Rows of zero norm are outside the contract (the reference divides by the norm)."""
+    _need_cuda(user_table, item_table, q, grad_user, grad_item, grad_q, loss, workspace)
+    dev = user_table.device
+    for t in (user_table, item_table, q):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise RuntimeError("ccfcrec: tables and q must be contiguous 2-D float32 tensors")
+    d = user_table.shape[1]
+    if item_table.shape[1] != d or q.shape[1] != d:
+        raise RuntimeError("ccfcrec: tables and q differ in width")
+    if d % 4 != 0 or d < 4 or d > 256:
+        raise RuntimeError(f"ccfcrec: width {d} must be a multiple of 4 in [4, 256]")
+    B, P, N, S = plan["batch"], plan["n_pos"], plan["n_neg"], plan["n_self"]
+    if ccfcrec_rows(P, N, S) > ccfcrec_max_rows():
+        raise RuntimeError(f"ccfcrec: 1 + P + P N + S = {ccfcrec_rows(P, N, S)} rows per record exceed the cap "
+                           f"{ccfcrec_max_rows()}")
+    if q.shape[0] != B:
+        raise RuntimeError("ccfcrec: q must have one row per record of the plan")
+    if plan["user_range"][0] < 0 or plan["user_range"][1] >= user_table.shape[0] or plan["item_range"][0] < 0 \
+            or plan["item_range"][1] >= item_table.shape[0]:
+        raise RuntimeError("ccfcrec: the plan's ids lie outside the tables")
+    for t in (item_table, q, plan["users"], grad_user, grad_item, grad_q, loss, workspace):
+        if t is not None and t.device != dev:
+            raise RuntimeError("ccfcrec: every tensor must be on the tables' device")
+
+    def grad_buffer(g, like, want, touched_all):
+        if g is None:
+            if not want:
+                return None
+            return torch.empty_like(like) if touched_all else torch.zeros_like(like)
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != like.shape:
+            raise RuntimeError("ccfcrec: gradient buffers must be contiguous float32 tensors of the tables' shapes")
+        return g
+
+    grad_user = grad_buffer(grad_user, user_table, want_user, False)
+    grad_item = grad_buffer(grad_item, item_table, want_item, False)
+    grad_q = grad_buffer(grad_q, q, want_q, True)
+    if loss is None:
+        loss = torch.empty(5, dtype=torch.float32, device=dev)
+    elif loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 5:
+        raise RuntimeError("ccfcrec: loss must be a contiguous float32 buffer of at least five elements")
+    if workspace is None:
+        workspace = ccfcrec_workspace(B, P, N, S, d, plan["n_items"], plan["n_users"], dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise RuntimeError("ccfcrec: workspace must be a contiguous uint8 tensor")
+    p = plan
+    _lib.check(_lib.lib().crh_ccfcrec_f32(
+        _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]), _lib.ptr(q),
+        _lib.ptr(p["users"]), _lib.ptr(p["neg_users"]), _lib.ptr(p["items"]), int(p["user_range"][0]),
+        int(p["user_range"][1]), int(p["item_range"][0]), int(p["item_range"][1]), _lib.ptr(p["item_ids"]),
+        _lib.ptr(p["item_ptr"]), _lib.ptr(p["item_occ"]), _lib.ptr(p["item_chunk_ptr"]), _lib.ptr(p["item_chunk_own"]),
+        int(p["n_items"]), int(p["n_item_chunks"]), _lib.ptr(p["user_ids"]), _lib.ptr(p["user_ptr"]), _lib.ptr(p["user_occ"]),
+        _lib.ptr(p["user_chunk_ptr"]), _lib.ptr(p["user_chunk_own"]), int(p["n_users"]), int(p["n_user_chunks"]), int(B),
+        int(P), int(N), int(S), int(d), float(tau), float(lambda1), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item),
+        _lib.ptr(grad_q), _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_ccfcrec_f32")
+    return loss, grad_user, grad_item, grad_q
 
 
 # ---- SimGCL / XSimGCL layer perturbation (perturb.hip) ---------------------------------------------------------------

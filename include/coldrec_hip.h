@@ -568,6 +568,48 @@ int crh_clcrec_f32(const float* user_table, const float* item_table, const float
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The loss of CCFCRec (reference model/CCFCRec.py:53-87), forward and backward in one call.  B records, each the user
+ * users[b], the negative user neg_users[b] and R = 1 + P + P N + S item rows items[b R + r]: r = 0 the record's item i_b,
+ * then the P positives, then the P N negatives (positive-major), then the S self-negatives; q (B, d) = the content
+ * encoder's output for i_b.  With c(x) = <q_b, V[x]> / (tau |q_b| |V[x]|):
+ *     L_c  = (1/P) sum_b sum_p [log(e^c(pos_bp) + sum_n e^c(neg_bpn)) - c(pos_bp)]
+ *     L_s  =       sum_b       [log(e^c(i_b) + sum_s e^c(sneg_bs)) - c(i_b)]
+ *     L_r1 = sum_b softplus(-(<V[i_b], U[u_b]> - <V[i_b], U[k_b]>))   L_r2 = the same with q_b in V[i_b]'s place
+ *     total = lambda1 (L_c + L_s) + (1 - lambda1)(L_r1 + L_r2)           (sums over the batch, not means; no regulariser)
+ * As in the reference there is no epsilon under the norms: a q row or a gathered item row of zero norm is outside the
+ * contract (the result is not finite; nothing is read or written out of bounds).
+ *   user_rows, item_rows  the tables' row counts; user_min .. item_max = the smallest and largest id of users + neg_users
+ *                  and of items, as the caller states them (ops.ccfcrec_plan measures them): a range that leaves its
+ *                  table is an argument error
+ *   inverse indices (ops.ccfcrec_plan builds them): item_ids[n_items] = the distinct items, item_occ = the flat rows
+ *                  b R + r grouped by item (a stable sort: ascending inside an item), item_ptr[n_items + 1] their offsets;
+ *                  every item's rows are cut into chunks of crh_ccfcrec_chunk_rows(): item_chunk_ptr[n_items + 1] =
+ *                  offsets into the chunk list, item_chunk_own[n_item_chunks] = each chunk's index into item_ids.  The
+ *                  user_* arrays are the same over the 2B occurrences o (o < B: users[o], else neg_users[o - B])
+ *   grad_user, grad_item  d total / d table * scale, written at the touched rows only (the caller zeroes the rest);
+ *   grad_q         (B, d), every row.  Any may be NULL: its owner pass does not run and the others keep their bits
+ *   loss_out       5 device floats: L_c, L_s, L_r1, L_r2, total; NULL = not written
+ *   workspace      crh_ccfcrec_workspace_bytes(...) bytes, 256-byte aligned
+ * d % 4 == 0, 4 <= d <= 256; P, N, S >= 1; R <= crh_ccfcrec_max_rows(); batch R < 2^31; tables, q and gradients 16-byte
+ * aligned.  No atomics, every sum in an order fixed by the shape: two identical calls give identical bits.  One wave per
+ * record, then one wave per chunk of an owner's occurrences and the chunks' partial sums added in chunk order.
+ */
+int crh_ccfcrec_max_rows(void);
+int crh_ccfcrec_chunk_rows(void);
+size_t crh_ccfcrec_workspace_bytes(int64_t batch, int n_pos, int n_neg, int n_self, int d, int64_t n_items,
+                                   int64_t n_users);
+int crh_ccfcrec_f32(const float* user_table, int64_t user_rows, const float* item_table, int64_t item_rows,
+                    const float* q, const int32_t* users, const int32_t* neg_users, const int32_t* items,
+                    int user_min, int user_max, int item_min, int item_max,
+                    const int32_t* item_ids, const int32_t* item_ptr,
+                    const int32_t* item_occ, const int32_t* item_chunk_ptr, const int32_t* item_chunk_own,
+                    int64_t n_items, int64_t n_item_chunks, const int32_t* user_ids, const int32_t* user_ptr,
+                    const int32_t* user_occ, const int32_t* user_chunk_ptr, const int32_t* user_chunk_own,
+                    int64_t n_users, int64_t n_user_chunks, int64_t batch, int n_pos, int n_neg, int n_self, int d,
+                    float tau, float lambda1, float scale, float* grad_user, float* grad_item, float* grad_q,
+                    float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The layer perturbation of SimGCL / XSimGCL (model/SimGCL.py:106-108), in place on one (n_rows, d) fp32 layer output
  * of the propagation, d % 4 == 0, 4 <= d <= 256, every pointer 16-byte aligned.  Per row, r = the row's d uniforms:
  *     nrm = max(sqrt(sum r^2), 1e-12)                       (F.normalize's clamp)
