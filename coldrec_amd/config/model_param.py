@@ -54,4 +54,12 @@ def model_specific_param(model_name, parser, available_models):
                             help='Load both tables from ./emb/{dataset}_cold_item_{backbone}_{user,item}_emb.pt')
         parser.add_argument('--pretrain_update', type=_str2bool, default=False, nargs='?', const=True,
                             help='With --pretrain: train the loaded tables (true) or keep them frozen (false)')
+    if model_name == 'ALDI':      # config/model_param.py:82-93
+        parser.add_argument('--alpha', type=float, default=0.9, help='Weight of the ranking distillation loss')
+        parser.add_argument('--beta', type=float, default=0.05, help='Weight of the identification distillation loss')
+        parser.add_argument('--gamma', type=float, default=0.1, help='Weight of the rating distillation loss')
+        parser.add_argument('--tws', type=int, default=0, choices=[0, 1],
+                            help='1: weight the two distillation losses by the positive item\'s frequency')
+        parser.add_argument('--freq_coef_M', type=float, default=4, help='Cap of the frequency weights: tanh(M)')
+        parser.add_argument('--aldi_hidden', type=int, default=200, help='Hidden width of the two student towers')
     return parser

@@ -8,8 +8,10 @@ Subclasses implement ``train / predict / batch_predict / save`` and publish ``se
 Evaluation (``_evaluate``, reference lines 153-188) never materialises the (users x items) score
 block when the plugin's ``batch_predict`` is the stock ``user_emb[users] @ item_emb.T``: users,
 rated-item CSR and the warm/cold candidate bitmap are cached on the GPU per (set, type) and one
-call of crh_score_topk_f32 returns the masked top-k.  Any other ``batch_predict`` (VBPR, ALDI, ...)
-is honoured: its dense block goes through crh_mask_topk_f32.  Either way the order is the canonical
+call of crh_score_topk_f32 returns the masked top-k.  Any other ``batch_predict`` (VBPR, ...)
+is honoured: its dense block goes through crh_mask_topk_f32.  A trainer whose user table depends on the item
+(ALDI: teacher users for warm items, generated users for cold ones) names its tables in ``_eval_parts``:
+one fused scoring call per table, the lists merged by crh_merge_topk.  Either way the order is the canonical
 (score desc, index asc) one, and the metrics are computed on arrays (util/evaluator.py).
 """
 from __future__ import annotations
@@ -288,7 +290,7 @@ class BaseColdStartTrainer(ABC):
             'users': users, 'users_int': torch.from_numpy(uint.astype(np.int32)).to(dev),
             'rated_rowptr': torch.from_numpy(rowptr).to(dev) if rowptr[-1] else None, 'rated_rowptr_host': rowptr,
             'rated_col': torch.from_numpy(np.ascontiguousarray(col)).to(dev) if rowptr[-1] else None,
-            'bitmap': ops.make_bitmap(d.item_num, masked, dev),
+            'bitmap': ops.make_bitmap(d.item_num, masked, dev), 'masked_ids': masked,
             'gt_rowptr': gt_rowptr, 'gt_items': gt_items, 'fingerprint': (len(users), int(gt_rowptr[-1])),
             'gt_dense': truth_dense(gt_rowptr, gt_items, len(d.item)),
         }
@@ -317,6 +319,11 @@ class BaseColdStartTrainer(ABC):
             c = self._get_eval_cache(data_set, data_type)
         if len(c['users']) == 0:        # an empty warm / cold / valid split: the reference reports zeros, no kernel runs
             return c, None, None
+        parts = self._eval_parts()
+        if parts is not None:
+            ranked = self._topk_parts(c, parts)
+            if ranked is not None:
+                return (c,) + ranked
         fused = self.fused_eval
         if fused is None:
             fused = _is_stock_batch_predict(type(self).batch_predict)
@@ -339,25 +346,7 @@ class BaseColdStartTrainer(ABC):
 
                 def rank(users, rp, rc, out=None):
                     return eng.topk(ue, users, rp, rc, c['bitmap'])
-            n, blk = len(c['users']), self.EVAL_USER_BLOCK
-            if n <= blk:
-                s, i = rank(c['users_int'], c['rated_rowptr'], c['rated_col'])
-            else:
-                # catalogue-scale evaluations (S-EVAL: 1e6 users) go in blocks of EVAL_USER_BLOCK users: the kernel's
-                # partial-list workspace is 64 x users x k x 8 bytes (10 GB for 1e6 users at once), and 2048 groups of 64
-                # users already fill the chip -- one block is one launch at the headline's shape
-                s = torch.empty((n, self.max_N), dtype=torch.float32, device=ue.device)
-                i = torch.empty((n, self.max_N), dtype=torch.int32, device=ue.device)
-                rp_all, rc_all, rp_host = c['rated_rowptr'], c['rated_col'], c['rated_rowptr_host']
-                for b0 in range(0, n, blk):
-                    b1 = min(n, b0 + blk)
-                    rp = rc = None
-                    if rp_all is not None:
-                        rp = (rp_all[b0:b1 + 1] - rp_all[b0]).contiguous()
-                        rc = rc_all[int(rp_host[b0]):int(rp_host[b1])]
-                    bs_, bi_ = rank(c['users_int'][b0:b1], rp, rc, out=(s[b0:b1], i[b0:b1]))
-                    if bs_.data_ptr() != s[b0:b1].data_ptr():          # the sharded engine returns its own (merged) block
-                        s[b0:b1], i[b0:b1] = bs_, bi_
+            s, i = self._rank_in_blocks(c, rank, ue.device)
         else:
             parts_s, parts_i = [], []
             for lo in range(0, len(c['users']), self.batch_size):
@@ -374,9 +363,93 @@ class BaseColdStartTrainer(ABC):
             s, i = torch.cat(parts_s), torch.cat(parts_i)
         return c, s, i
 
+    def _rank_in_blocks(self, c, rank, dev):
+        """``rank(users, rated_rowptr, rated_col, out=None)`` over the split's users, EVAL_USER_BLOCK at a time."""
+        n, blk = len(c['users']), self.EVAL_USER_BLOCK
+        if n <= blk:
+            return rank(c['users_int'], c['rated_rowptr'], c['rated_col'])
+        # catalogue-scale evaluations (S-EVAL: 1e6 users) go in blocks of EVAL_USER_BLOCK users: the kernel's
+        # partial-list workspace is 64 x users x k x 8 bytes (10 GB for 1e6 users at once), and 2048 groups of 64
+        # users already fill the chip -- one block is one launch at the headline's shape
+        s = torch.empty((n, self.max_N), dtype=torch.float32, device=dev)
+        i = torch.empty((n, self.max_N), dtype=torch.int32, device=dev)
+        rp_all, rc_all, rp_host = c['rated_rowptr'], c['rated_col'], c['rated_rowptr_host']
+        for b0 in range(0, n, blk):
+            b1 = min(n, b0 + blk)
+            rp = rc = None
+            if rp_all is not None:
+                rp = (rp_all[b0:b1 + 1] - rp_all[b0]).contiguous()
+                rc = rc_all[int(rp_host[b0]):int(rp_host[b1])]
+            bs_, bi_ = rank(c['users_int'][b0:b1], rp, rc, out=(s[b0:b1], i[b0:b1]))
+            if bs_.data_ptr() != s[b0:b1].data_ptr():          # the sharded engine returns its own (merged) block
+                s[b0:b1], i[b0:b1] = bs_, bi_
+        return s, i
+
+    # ------------------------------------------------------------------ ranking with a user table per item partition
+    def _eval_parts(self):
+        """Opt-in hook for a trainer whose user table depends on the item (ALDI: warm items are scored with the teacher's
+        users, cold items with generated ones).  None (the default): one user table, the routes of ``_topk_device``.
+        Otherwise a list of ``(user table, internal ids of the items this table does NOT score)`` -- 2-D device tensors
+        of ``item_emb``'s width, the item sets fixed for the trainer's life -- that splits the catalogue: every item is
+        scored by exactly one part.  ``batch_predict`` must compute the same composed block; it stays the route of a
+        data-parallel launch and of parts that do not split the catalogue (the reference scores an uncovered item 0)."""
+        return None
+
+    def _parts_plan(self, c, parts):
+        """Per split, cached: (usable, [(part, bitmap = the split's mask OR the part's)]) without the parts whose items the
+        split masks entirely.  Usable: the parts split the catalogue, and when two lists are merged every user keeps at
+        least k unmasked candidates (the merge then never meets a masked fill-in, which both lists would carry)."""
+        plan = c.get('parts_plan')
+        if plan is None:
+            n = int(self.data.item_num)
+            split = np.zeros(n, bool)
+            if c['masked_ids'] is not None:
+                split[np.asarray(c['masked_ids'], np.int64)] = True
+            scored = np.zeros(n, np.int32)
+            active = []
+            for p, (_table, ids) in enumerate(parts):
+                m = np.zeros(n, bool)
+                if ids is not None and len(ids):
+                    m[np.asarray(ids, np.int64)] = True
+                scored += ~m
+                both = split | m
+                if not both.all():
+                    active.append((p, ops.make_bitmap(n, np.nonzero(both)[0], self.device)))
+            rated = np.diff(c['rated_rowptr_host'])
+            real_min = n - int(split.sum()) - (int(rated.max()) if rated.size else 0)
+            usable = bool((scored == 1).all()) and len(active) >= 1 and (len(active) == 1 or real_min >= self.max_N)
+            plan = c['parts_plan'] = (usable, active)
+        return plan
+
+    def _topk_parts(self, c, parts):
+        """(scores, ids) of the split by one fused scoring call per active part, merged canonically; None when the
+        two-table route does not apply (``batch_predict`` ranks then)."""
+        ie = getattr(self, 'item_emb', None)
+        tables = [t for t, _ in parts]
+        if dp_from_env() is not None or not all(torch.is_tensor(t) and t.is_cuda and t.dim() == 2 for t in tables + [ie]):
+            return None
+        usable, active = self._parts_plan(c, parts)
+        if not usable:
+            return None
+        if not getattr(self, '_route_told', False):
+            self._route_told = True
+            self._tell_route(True, True, c, parts=len(active))
+        tdt = torch.float16 if getattr(self.args, 'score_dtype', 'fp32') == 'fp16' else torch.float32
+        ie = ie.detach().to(tdt)
+        lists = []
+        for p, bitmap in active:
+            ue = tables[p].detach().to(tdt)
+
+            def rank(users, rp, rc, out=None):
+                return ops.score_topk(ue, users, ie, self.max_N, rp, rc, bitmap, out=out)
+            lists.append(self._rank_in_blocks(c, rank, ie.device))
+        if len(lists) == 1:
+            return lists[0]
+        return ops.merge_topk(torch.stack([s for s, _ in lists]), torch.stack([i for _, i in lists]), self.max_N)
+
     DENSE_BLOCK_WARN_BYTES = 4 << 30
 
-    def _tell_route(self, fused: bool, stock: bool, c) -> None:
+    def _tell_route(self, fused: bool, stock: bool, c, parts: int = 0) -> None:
         """One line at a trainer's first evaluation: which route ranks -- the fused kernel the LIBRARY names for the shape
         (crh_score_topk_route) or batch_predict's dense block -- and a warning when that block is catalogue-sized."""
         n_items = int(self.data.item_num) if hasattr(self.data, 'item_num') else len(self.data.item)
@@ -386,6 +459,11 @@ class BaseColdStartTrainer(ABC):
             r = ops.score_topk_route(min(len(c['users']), self.EVAL_USER_BLOCK), int(ie.shape[0]), int(ie.shape[1]), self.max_N,
                                      half=half, has_bitmap=c['bitmap'] is not None)
             form = f", {r['dma_form']} form" if r.get('dma_form') else ''
+            if parts:
+                print(f"Evaluation route: two-table fused HIP scoring: one user table per item partition, {parts} call"
+                      f"{'s' if parts > 1 else ''} of {r['kernel']} ({r['route']}{form}) over the item table"
+                      f"{', lists merged by crh_merge_topk' if parts > 1 else ''}; no score block is written")
+                return
             print(f"Evaluation route: fused HIP scoring + masks + top-{self.max_N} ({r['kernel']}, {r['route']}{form}"
                   f"{', seeded from a %d-item prefix' % r['prefix_items'] if r['seeded'] else ''}); no score block is written")
             return

@@ -1216,6 +1216,82 @@ def ccfcrec(user_table: torch.Tensor, item_table: torch.Tensor, q: torch.Tensor,
     return loss, grad_user, grad_item, grad_q
 
 
+# ---- ALDI's loss (aldi.hip) ------------------------------------------------------------------------------------------
+
+def aldi_workspace_bytes(batch: int, d: int) -> int:
+    return int(_lib.lib().crh_aldi_workspace_bytes(int(batch), int(d)))
+
+
+def aldi_workspace(batch: int, d: int, device) -> torch.Tensor:
+    return torch.empty(max(aldi_workspace_bytes(batch, d), 1), dtype=torch.uint8, device=device)
+
+
+def aldi(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
+         gen_user: torch.Tensor, gen_pos: torch.Tensor, gen_neg: torch.Tensor, item_weight: torch.Tensor, alpha: float,
+         beta: float, gamma: float, scale: float = 1.0, want_user: bool = True, want_pos: bool = True,
+         want_neg: bool = True, grad_user=None, grad_pos=None, grad_neg=None, loss=None, workspace=None, id_range=None):
+    """ALDI's loss and its three gradients in one call (crh_aldi_f32).  user_table (nu, d), item_table (ni, d): the frozen
+    teacher; users, pos, neg (B,) integer ids; gen_user, gen_pos, gen_neg (B, d): the student towers' outputs; item_weight
+    (ni,); fp32 contiguous, d % 4 == 0 <= 256.  Returns (loss5 = [L_bpr, L_rate, L_rank, L_iden, total], d_gen_user,
+    d_gen_pos, d_gen_neg); gradients are d total / d gen_* * scale; one that is neither given nor wanted is not computed
+    (None).  id_range = ((user min, user max), (item min, item max)) when the caller knows them (a trainer that sampled the
+    ids on the host); measured here otherwise, which waits for the device."""
+    _need_cuda(user_table, item_table, users, pos, neg, gen_user, gen_pos, gen_neg, item_weight, grad_user, grad_pos,
+               grad_neg, loss, workspace)
+    dev = user_table.device
+    for t in (user_table, item_table, gen_user, gen_pos, gen_neg):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise RuntimeError("aldi: tables and tower outputs must be contiguous 2-D float32 tensors")
+    d = user_table.shape[1]
+    if d % 4 != 0 or d < 4 or d > 256:
+        raise RuntimeError(f"aldi: width {d} must be a multiple of 4 in [4, 256]")
+    B = users.shape[0] if users.dim() == 1 else 0
+    if B < 1 or pos.shape != (B,) or neg.shape != (B,):
+        raise RuntimeError("aldi: users, pos, neg must be (B,) with B >= 1")
+    if item_table.shape[1] != d or any(t.shape != (B, d) for t in (gen_user, gen_pos, gen_neg)):
+        raise RuntimeError("aldi: the tower outputs must be (B, d) of the tables' width")
+    if item_weight.dtype != torch.float32 or not item_weight.is_contiguous() or item_weight.shape != (item_table.shape[0],):
+        raise RuntimeError("aldi: item_weight must be a contiguous float32 vector with one entry per item")
+    ids = (users, pos, neg)
+    if any(t.dtype.is_floating_point for t in ids):
+        raise RuntimeError("aldi: users, pos, neg must be integer tensors")
+    for t in (item_table, *ids, gen_user, gen_pos, gen_neg, item_weight, grad_user, grad_pos, grad_neg, loss, workspace):
+        if t is not None and t.device != dev:
+            raise RuntimeError("aldi: every tensor must be on the tables' device")
+    if id_range is None:
+        items = torch.cat([pos.reshape(-1), neg.reshape(-1)])
+        id_range = ((int(users.min()), int(users.max())), (int(items.min()), int(items.max())))
+    (u_lo, u_hi), (i_lo, i_hi) = id_range
+    if u_lo < 0 or u_hi >= user_table.shape[0] or i_lo < 0 or i_hi >= item_table.shape[0]:
+        raise RuntimeError("aldi: ids lie outside the tables")
+    users, pos, neg = (t.to(torch.int32).contiguous() for t in ids)
+
+    def grad_buffer(g, want):
+        if g is None:
+            return torch.empty_like(gen_user) if want else None
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != gen_user.shape:
+            raise RuntimeError("aldi: gradient buffers must be contiguous float32 tensors of the tower outputs' shape")
+        return g
+
+    grad_user, grad_pos, grad_neg = grad_buffer(grad_user, want_user), grad_buffer(grad_pos, want_pos), \
+        grad_buffer(grad_neg, want_neg)
+    if loss is None:
+        loss = torch.empty(5, dtype=torch.float32, device=dev)
+    elif loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 5:
+        raise RuntimeError("aldi: loss must be a contiguous float32 buffer of at least five elements")
+    if workspace is None:
+        workspace = aldi_workspace(B, d, dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise RuntimeError("aldi: workspace must be a contiguous uint8 tensor")
+    _lib.check(_lib.lib().crh_aldi_f32(
+        _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]), _lib.ptr(users),
+        _lib.ptr(pos), _lib.ptr(neg), int(u_lo), int(u_hi), int(i_lo), int(i_hi), _lib.ptr(gen_user), _lib.ptr(gen_pos),
+        _lib.ptr(gen_neg), _lib.ptr(item_weight), int(B), int(d), float(alpha), float(beta), float(gamma), float(scale),
+        _lib.ptr(grad_user), _lib.ptr(grad_pos), _lib.ptr(grad_neg), _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(),
+        _lib.current_stream()), "crh_aldi_f32")
+    return loss, grad_user, grad_pos, grad_neg
+
+
 # ---- SimGCL / XSimGCL layer perturbation (perturb.hip) ---------------------------------------------------------------
 
 def _perturb_checks(what: str, y: torch.Tensor, *others) -> None:

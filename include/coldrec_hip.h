@@ -610,6 +610,38 @@ int crh_ccfcrec_f32(const float* user_table, int64_t user_rows, const float* ite
                     float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The loss of ALDI (reference model/ALDI.py:47-82), forward and backward in one call.  B records, each the user users[b],
+ * the positive pos[b] and the negative neg[b]; the frozen teacher rows Ur = U[users[b]], Pr = V[pos[b]], Nr = V[neg[b]];
+ * gen_user, gen_pos, gen_neg (B, d) = the student towers' outputs; wi = item_weight[pos[b]] (item_rows floats).  With
+ * sp = <gu, gp>, sn = <gu, gn>, tp = <Ur, Pr>, tn = <Ur, Nr>, bce(x, z) = max(x, 0) - x z + log1p(exp(-|x|)) and every
+ * mean over the B records:
+ *     L_bpr  = mean(-log(1e-5 + sigmoid(sp - sn)))
+ *     L_rate = gamma mean(|tp - sp| + |tn - sn|)                         (the derivative of |x| at 0 is 0)
+ *     L_rank = alpha mean(wi bce(sp - sn, sigmoid(tp - tn)))
+ *     L_iden = beta  mean(wi bce(|gp|^2 - <gp, mean_j gn_j>, sigmoid(|Pr|^2 - <Pr, mean_j Nr_j>)))
+ *     total  = L_bpr + L_rate + L_rank + L_iden
+ * (the reference's (gp gn^T).mean(1) is the product with the column mean; no B x B block is formed).
+ *   user_rows, item_rows  the tables' row counts; user_min .. item_max = the smallest and largest id of users and of
+ *                  pos + neg, as the caller states them: a range that leaves its table is an argument error (a record
+ *                  whose id leaves its table all the same contributes nothing and gets zero gradient rows)
+ *   grad_user, grad_pos, grad_neg  (B, d): d total / d gen_* * scale, every row.  Any may be NULL: it is neither written
+ *                  nor required and the others keep their bits.  The teacher tables get no gradient
+ *   loss_out       5 device floats: L_bpr, L_rate, L_rank, L_iden, total (not scaled); NULL = not written
+ *   workspace      crh_aldi_workspace_bytes(batch, d) bytes (0 = a refused shape), 256-byte aligned
+ * d % 4 == 0, 4 <= d <= 256; 1 <= batch < 2^31; tables, tower outputs and gradients 16-byte aligned.  No atomics, every
+ * sum in an order fixed by batch and d: two identical calls give identical bits.  Five launches on the stream: the column
+ * means (chunk partials, then one workgroup), one wave per record, the cross-record vector and the loss sums (one
+ * workgroup), and its addition to every row of grad_neg.
+ */
+size_t crh_aldi_workspace_bytes(int64_t batch, int d);
+int crh_aldi_f32(const float* user_table, int64_t user_rows, const float* item_table, int64_t item_rows,
+                 const int32_t* users, const int32_t* pos, const int32_t* neg, int user_min, int user_max, int item_min,
+                 int item_max, const float* gen_user, const float* gen_pos, const float* gen_neg,
+                 const float* item_weight, int64_t batch, int d, float alpha, float beta, float gamma, float scale,
+                 float* grad_user, float* grad_pos, float* grad_neg, float* loss_out, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
+/*
  * The layer perturbation of SimGCL / XSimGCL (model/SimGCL.py:106-108), in place on one (n_rows, d) fp32 layer output
  * of the propagation, d % 4 == 0, 4 <= d <= 256, every pointer 16-byte aligned.  Per row, r = the row's d uniforms:
  *     nrm = max(sqrt(sum r^2), 1e-12)                       (F.normalize's clamp)

@@ -1,0 +1,236 @@
+"""CPU-only: ALDI's registry entry, flags and refusals, the kernel's workspace query, the weight table, and the restatement
+of a whole run pinned to G22 (the reference's own MF.run() + ALDI.run() on the toy item-cold split), which makes the
+restatement the oracle of the GPU tests.  The distances of plain float32 torch from the float64 formula and from G22 --
+the figures the GPU tests' bars are 8x of -- are measured, printed and checked here.
+
+Measured (one and eight CPU threads give the same figures):
+    float32 formula against float64 at the GPU cases: loss terms 7.76e-8 of the total at worst (B2-d4; 1.3e-8 .. 6.0e-8
+        elsewhere), gradients 2.60e-7 of their maximum at worst (B2-d4, d gp; 1.3e-7 .. 2.1e-7 elsewhere);
+    min(|tp - sp|, |tn - sn|) over a case's records: 1.5e-5 at B257-d64 (inputs of scale 0.05), 1.1e-4 and more elsewhere;
+    float32 run against G22: loss terms 8.76e-8 of the total; tables 0 / 1.45e-2 / 5.62e-4 of their scale; cold metrics
+        3.95e-3 (see test_float32_restatement_ends_near_g22 and tests/test_aldi_gpu.py's RUN_TABLE_BARS).
+"""
+import argparse
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from tests import aldi_restate
+from tests.conftest import load_golden
+from tests.test_aldi_gpu import (CASES, COLD_METRIC_BAR, F32_RUN_COLD_METRIC, F32_RUN_TABLES, GRAD_BAR, IDS, LOSS_BAR,
+                                 RUN_LOSS_BAR, RUN_TABLE_BARS, _inputs, distances, lists_vs_reference,
+                                 metrics_vs_reference, run_distances)
+from tests.test_host_logic import builder
+
+
+def _cfg(data, device="cpu", **kw):
+    a = dict(dataset="toy", model="ALDI", epochs=2, layers=2, topN="10,20", bs=512, emb_size=64, lr=0.001, reg=0.0001,
+             runs=1, seed=2024, use_gpu=False, save_emb=False, gpu_id=0, cold_object="item", backbone="MF", early_stop=10,
+             eval_every=1, alpha=0.9, beta=0.05, gamma=0.1, tws=1, freq_coef_M=4.0, aldi_hidden=200)
+    a.update(kw)
+    return types.SimpleNamespace(args=argparse.Namespace(**a), data=data, device=torch.device(device))
+
+
+def _write_teacher(fx, where):
+    (where / "emb").mkdir(exist_ok=True)
+    torch.save(torch.from_numpy(fx["teacher_U"]), where / "emb" / "toy_cold_item_MF_user_emb.pt")
+    torch.save(torch.from_numpy(fx["teacher_V"]), where / "emb" / "toy_cold_item_MF_item_emb.pt")
+
+
+def test_registry_resolves_aldi_without_changing_the_listings():
+    from coldrec_amd.model import AVAILABLE_MODELS, resolvable
+    from coldrec_amd.model.BaseRecommender import BaseColdStartTrainer
+    keys, names = list(AVAILABLE_MODELS.keys()), list(AVAILABLE_MODELS.names())
+    assert "ALDI" in AVAILABLE_MODELS
+    cls = AVAILABLE_MODELS["ALDI"]
+    assert issubclass(cls, BaseColdStartTrainer) and AVAILABLE_MODELS.get("ALDI") is cls
+    assert list(AVAILABLE_MODELS.keys()) == keys and list(AVAILABLE_MODELS.names()) == names
+    assert "ALDI" not in keys and "ALDI" not in names and "ALDI" in resolvable()
+    assert cls._eval_parts is not BaseColdStartTrainer._eval_parts and BaseColdStartTrainer._eval_parts(None) is None
+
+
+def test_cli_carries_the_reference_defaults():
+    from coldrec_amd.main import parse_args
+    a = parse_args(["--model", "ALDI"])
+    assert (a.alpha, a.beta, a.gamma, a.tws, a.freq_coef_M, a.aldi_hidden) == (0.9, 0.05, 0.1, 0, 4, 200)
+    b = parse_args(["--model", "ALDI", "--tws", "1", "--aldi_hidden", "64"])
+    assert b.tws == 1 and b.aldi_hidden == 64
+    with pytest.raises(SystemExit):
+        parse_args(["--model", "ALDI", "--tws", "2"])
+
+
+def test_refusals(tmp_path, monkeypatch):
+    from coldrec_amd.model import AVAILABLE_MODELS
+    _, data = builder()
+    new = AVAILABLE_MODELS["ALDI"]
+    monkeypatch.chdir(tmp_path)
+    with pytest.raises(Exception, match="Cold user is not supported in ALDI"):
+        new(_cfg(data, cold_object="user"))
+    with pytest.raises(ValueError, match="multiple of 4"):
+        new(_cfg(data, emb_size=50))
+    with pytest.raises(ValueError, match="multiple of 4"):
+        new(_cfg(data, emb_size=260))
+    with pytest.raises(FileNotFoundError, match=r"ALDI requires ./emb/toy_cold_item_MF_user_emb.pt. Train the backbone "
+                                                r"first"):
+        new(_cfg(data))
+    fx = load_golden("g22_aldi.npz")
+    _write_teacher(fx, tmp_path)
+    with pytest.raises(ValueError, match="do not fit this dataset"):
+        new(_cfg(data, emb_size=32))
+    tr = new(_cfg(data))
+    assert not any(p.requires_grad for p in (tr.model.user_emb, tr.model.item_emb))          # the teacher stays frozen
+    assert {n.split(".")[0] for n, _ in tr.model.named_parameters()} == {"user_tower", "item_tower"}
+    groups = tr.model.param_groups(1e-4)
+    assert [len(g["params"]) for g in groups] == [4, 8] and [g["weight_decay"] for g in groups] == [0.0, 1e-4]
+    with pytest.raises(RuntimeError, match="MI355X only"):
+        tr.train()
+    import coldrec_amd.model.ALDI as mod
+    monkeypatch.setattr(mod, "dp_from_env", lambda: object())  # a data-parallel launch is refused before anything runs
+    tr.device = torch.device("cuda:0")
+    with pytest.raises(RuntimeError, match="data-parallel"):
+        tr.train()
+
+
+def test_queries_without_gpu():
+    from coldrec_amd import _lib
+    L = _lib.lib()
+    assert L.crh_aldi_workspace_bytes(4096, 64) > 0 and L.crh_aldi_workspace_bytes(1, 4) > 0
+    assert L.crh_aldi_workspace_bytes(512, 6) == 0 and L.crh_aldi_workspace_bytes(512, 260) == 0       # width
+    assert L.crh_aldi_workspace_bytes(0, 64) == 0                                                       # B
+
+
+@pytest.mark.parametrize("tws", [0, 1])
+def test_weight_table_equals_the_fixture(tws):
+    """The trainer's table (from the builder's arrays) and the restatement's (from its dicts) against the reference's.
+    The frequencies -- sums formed in the reference's order -- must be the same floats; the weights go through torch's
+    float32 tanh, which may round its last bit differently on another CPU: two units in the last place."""
+    from coldrec_amd.model.ALDI import item_frequency, pos_item_weights
+    fx = load_golden("g22_aldi.npz")
+    _, data = builder()
+    assert np.array_equal(item_frequency(data), fx["item_freq"])
+    assert np.array_equal(aldi_restate.item_weights(data, 4.0, tws)[0], fx["item_freq"])
+    want = fx[f"weights_tws{tws}"]
+    for got in (pos_item_weights(data, 4.0, tws).numpy(), aldi_restate.item_weights(data, 4.0, tws)[1]):
+        assert got.dtype == np.float32 and got.shape == want.shape
+        print(f"tws={tws}: {int((got != want).sum())} of {want.size} weights differ in their bits from the fixture's")
+        np.testing.assert_allclose(got, want, rtol=2.0 ** -22, atol=0)
+    assert (want == 1).all() if tws == 0 else (0 < want.min() < want.max() <= np.float32(np.tanh(4.0)))
+
+
+def test_learner_draws_the_restatement_towers(tmp_path, monkeypatch):
+    """The package's learner and the restatement's: the same towers from the same seed."""
+    from coldrec_amd.model.ALDI import ALDI_Learner
+    from coldrec_amd.util.utils import set_seed
+    _, data = builder()
+    _write_teacher(load_golden("g22_aldi.npz"), tmp_path)
+    monkeypatch.chdir(tmp_path)
+    set_seed(2024, False)
+    m = ALDI_Learner(_cfg(data).args, data, 64, torch.device("cpu"))
+    set_seed(2024, False)
+    ut, it = aldi_restate.Tower(64, 200, 64), aldi_restate.Tower(data.item_content_dim, 200, 64)
+    for a, b in ((m.user_tower, ut), (m.item_tower, it)):
+        for (na, pa), (nb, pb) in zip(a.named_parameters(), b.named_parameters()):
+            assert na == nb and torch.equal(pa, pb)
+    assert float(m.user_tower.fc1.weight.detach().abs().max()) < 0.1 and not m.user_tower.fc1.bias.any()
+
+
+@pytest.fixture(scope="module")
+def restated():
+    """The float64 and the float32 restatement of the G22 run, each on a fresh builder (the sampler shuffles in place)."""
+    fx, out = load_golden("g22_aldi.npz"), {}
+    for name, dt in (("f64", torch.float64), ("f32", torch.float32)):
+        _, data = builder()
+        out[name] = aldi_restate.run(data, fx["teacher_U"], fx["teacher_V"], dt)
+        out[name]["cold_idx"] = np.asarray(data.mapped_cold_item_idx)
+    return out
+
+
+def _best_tables(fx, r):
+    """The tables the trainer would report: the teacher's users and the snapshot of the fixture's best epoch."""
+    cold_users, items = r["snaps"][int(fx["best_epoch"]) - 1]
+    return fx["teacher_U"], cold_users, items
+
+
+def test_float64_restatement_of_a_run_matches_reference_g22(restated):
+    """Measured: loss terms 1.6e-7 of the total, tables 0 / 8.2e-3 / 4.2e-4 of their scale (why the generated tables are
+    not closer in any arithmetic: tests/test_aldi_gpu.py, above RUN_TABLE_BARS)."""
+    fx, r = load_golden("g22_aldi.npz"), restated["f64"]
+    assert r["losses"].shape == fx["losses"].shape == (16, 5)
+    rel, errs = run_distances(fx, r["losses"], _best_tables(fx, r))
+    print(f"float64 restatement: worst loss-term difference to G22 over the total {rel:.2e}; best-epoch tables differ by "
+          f"{errs[0]:.2e} / {errs[1]:.2e} / {errs[2]:.2e} of their scale")
+    assert rel <= RUN_LOSS_BAR and all(e <= bar for e, bar in zip(errs, RUN_TABLE_BARS))
+
+
+def test_float32_restatement_ends_near_g22(restated):
+    """How far plain float32 torch (towers and formula, the B x B product included) ends from the reference's own float32
+    run.  Measured: loss terms 8.76e-8 of the total -- 8x that lies below CLCRec's 1e-5, so the GPU run is held to it;
+    tables 0 / 1.45e-2 / 5.62e-4 of their scale -- 8x those exceed CLCRec's 2e-4, so the GPU run's bars are 8x the
+    measured figures (tests/test_aldi_gpu.py says why no arithmetic comes closer).  Asserted: the figures are the
+    recorded ones within a factor of 2 (another CPU's rounding moves them), so the bars stay what they claim to be."""
+    fx, r = load_golden("g22_aldi.npz"), restated["f32"]
+    rel, errs = run_distances(fx, r["losses"], _best_tables(fx, r))
+    print(f"float32 restatement: loss terms differ from G22 by {rel:.2e} of the total, best-epoch tables by "
+          f"{errs[0]:.2e} / {errs[1]:.2e} / {errs[2]:.2e} of their scale")
+    assert 8 * rel <= RUN_LOSS_BAR
+    assert errs[0] == 0 and all(e <= 2 * m for e, m in zip(errs[1:], F32_RUN_TABLES[1:]))
+
+
+def _host_lists_and_metrics(fx, tables, data):
+    """The three settings' top-20 lists of ``tables``, ranked here in float64, and their 5-dp metrics."""
+    from coldrec_amd.util.evaluator import ranking_metrics, truth_csr
+    Uw, Uc, V = (np.asarray(t, np.float64) for t in tables)
+    is_cold = np.zeros(V.shape[0], bool)
+    is_cold[np.asarray(data.mapped_cold_item_idx)] = True
+    lists, results = {}, {}
+    for t, name, truth in (("all", "overall", data.overall_test_set), ("cold", "cold", data.cold_test_set),
+                           ("warm", "warm", data.warm_test_set)):
+        users, rp, rc = fx[f"{t}_users_int"], fx[f"{t}_rated_rowptr"], fx[f"{t}_rated_col"]
+        S = np.where(is_cold[None, :], Uc[users] @ V.T, Uw[users] @ V.T)
+        for r in range(len(users)):
+            S[r, rc[rp[r]:rp[r + 1]]] = -1e9
+        if fx[f"{t}_cand"].size:
+            S[:, fx[f"{t}_cand"]] = -1e9
+        lists[t] = np.argsort(-S, axis=1, kind="stable")[:, :20]
+        _, gt_rowptr, gt_items = truth_csr(truth, item_of=data.item)
+        results[name] = ranking_metrics(gt_rowptr, gt_items, lists[t], [10, 20])
+    return lists, results
+
+
+def test_float32_restatement_keeps_the_reference_lists_and_metrics(restated):
+    """The list condition of the GPU run (at least half of the lists with a determined ranking) holds for plain float32
+    torch, so it can be relied on there; and the metrics: the all and warm settings equal G22's, the cold setting's
+    differ by 3.95e-3 at worst (float64: 3.5e-3) -- the figure COLD_METRIC_BAR is 8x of."""
+    fx, r = load_golden("g22_aldi.npz"), restated["f32"]
+    _, data = builder()
+    tables = _best_tables(fx, r)
+    lists, results = _host_lists_and_metrics(fx, tables, data)
+    same, det, total = lists_vs_reference(fx, tables, r["cold_idx"], lists, min_frac=0.5)
+    print(f"float32 restatement: {same} of {total} lists identical to G22's ({det} with a determined ranking)")
+    cold = np.abs(np.array(results["cold"]) - fx["test_cold"]).max()
+    print(f"float32 restatement: cold metrics differ from G22's by {cold:.2e}")
+    assert cold <= 2 * F32_RUN_COLD_METRIC < COLD_METRIC_BAR
+    metrics_vs_reference(results, fx, same == total)
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_float32_formula_stays_within_the_kernel_bars(case):
+    """The measurement behind LOSS_BAR / GRAD_BAR of tests/test_aldi_gpu.py, repeated: float32 torch against float64
+    torch at the GPU test's cases must itself lie within the bars (they are 8x its worst distance); and the two signs of
+    L_rate are the same in every precision: min(|tp - sp|, |tn - sn|) >= 1e-5."""
+    inp = _inputs(case)
+    want = aldi_restate.step(*inp, *case[5])
+    rel, errs = distances(aldi_restate.step(*inp, *case[5], dtype=torch.float32), want)
+    gap = aldi_restate.min_rate_gap(*inp[:8])
+    print(f"{IDS(case)}: float32 torch: loss err / total {rel:.2e}, gradient err / max {errs[0]:.2e} {errs[1]:.2e} "
+          f"{errs[2]:.2e}; min(|tp - sp|, |tn - sn|) {gap:.1e}; terms {want[0]}")
+    assert rel <= LOSS_BAR and max(errs) <= GRAD_BAR
+    assert gap >= 1e-5
+
+
+def test_one_case_has_an_unsaturated_identification_term():
+    case = CASES[5]
+    terms = aldi_restate.step(*_inputs(case), *case[5])[0]
+    assert case[5] == (0.0, 1.0, 0.0) and terms[3] > 0.1 and terms[3] == pytest.approx(terms[4] - terms[0])
