@@ -59,10 +59,10 @@ __device__ __forceinline__ void mma_f32_hooked(f32x16 (&acc)[UW], const f32x4& c
 // (Measured and not kept, round 5: one LDS round trip per candidate -- the whole list, its fill and the filter word
 // requested together, the insert and the user's new threshold computed from those registers -- ran 2.7 % SLOWER on the
 // same box, 0.5316 vs 0.5457 of 2.5 PF: most events end at the "cannot enter" test after three scalar reads.)
-// ONE_TRIP (fp32): the candidate's list rides the first batch of LDS reads (fill, list, filter word: one wait) and the insert works
-// out of those registers -- at fp32 a candidate above its user's threshold does enter (no rounding ties), so the second round trip
-// of the two-step form (fill and list read again by the insert) is paid by nearly every event; at fp16 most events end at the
-// "cannot enter" test and the lean first batch wins (the round-5 measurement above).
+// ONE_TRIP (fp32, and the screen's fp16 pass): the candidate's list rides the first batch of LDS reads (fill, list, filter word: one
+// wait) and the insert works out of those registers -- at fp32 a candidate above its user's threshold does enter (no rounding ties), so the second round trip
+// of the two-step form (fill and list read again by the insert) is paid by nearly every event; on the unseeded public fp16 routes
+// most events end at the "cannot enter" test and the lean first batch wins (the round-5 measurement above).
 #ifdef CRH_DMA_TWO_TRIP                      // (variant build: the two-step form for fp32 too, tools/ab_lib.sh)
 constexpr bool DMA_ONE_TRIP_F32 = false;
 #else
@@ -72,7 +72,10 @@ constexpr bool DMA_ONE_TRIP_F32 = true;
 // test, the rated filter with its bounded search, the insert and the user's new threshold out of registers.  sc / gi = the
 // candidate's score and id, bm_masked = its candidate-bitmap bit, ul / slot = its user's column in the wave and slot in the call,
 // mine = "this lane holds that user's threshold" (the caller's accumulator layout decides which lanes those are).
-template <bool ONE_TRIP>
+// LANE_READ (ONE_TRIP, the 16x16 event): lane l reads entry l whatever K -- lanes >= K read the LDS words behind the user's list (the
+// wave's own lists, ids and fills: K + 64 words stay inside them) and nobody uses them; the clamp and the select that blanks the
+// lanes >= n cost the event two registers that the 16x16 form does not have.
+template <bool ONE_TRIP, bool LANE_READ = false>
 __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, int ul, int64_t slot, float* ls, int* li, int* cnt, int K,
                                               const ScoreArgs& a, int lane, const unsigned* rfilter, bool mine, float& tau_reg) {
     float* lsu = ls + ul * K;
@@ -80,7 +83,7 @@ __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, 
     // one batch of LDS reads: fill, tail entry, filter word
     const unsigned hsh = rated_hash192(gi);
     const int n_raw = cnt[ul];
-    const int le = ONE_TRIP ? (lane < K ? lane : K - 1) : K - 1;   // (ONE_TRIP: lane l reads entry l; the others the tail entry)
+    const int le = ONE_TRIP ? (LANE_READ ? lane : (lane < K ? lane : K - 1)) : K - 1;   // (ONE_TRIP: lane l reads entry l; the others the tail entry)
     const float ks_raw = lsu[le];
     const int ki_raw = liu[le];
     const unsigned fw_raw = a.rated_rowptr ? rfilter[ul * DMA_FW + (hsh >> 5)] : 0u;
@@ -106,7 +109,10 @@ __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, 
     // holds -- the k-th entry after the insert is the old (k-1)-th or the candidate -- instead of reading it back
     float es = CRH_NEG_INF;
     int ei = CRH_PAD_IDX;
-    if constexpr (ONE_TRIP) {
+    if constexpr (ONE_TRIP && LANE_READ) {
+        es = ks_raw;       // (lanes >= n hold whatever lies behind the list: every use below is under lane < n, or reads a lane < n)
+        ei = ki_raw;
+    } else if constexpr (ONE_TRIP) {
         if (lane < n) {
             es = ks_raw;
             ei = ki_raw;
@@ -137,6 +143,20 @@ __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, 
     }
 }
 
+// The event of the 16x16 form (the screen's pass), round 15.  It walks its eight user blocks by the masks the common path has just
+// computed; -DCRH_DMA_EVENT_REBALLOT (variant build, tools/ab_lib.sh) compares every block again, as before.
+#ifdef CRH_DMA_EVENT_REBALLOT
+constexpr bool DMA_EVENT_REBALLOT = true;
+#else
+constexpr bool DMA_EVENT_REBALLOT = false;
+#endif
+// Its candidate takes the one-trip form of the fp32 kernels: the screen's lists are seeded and the threshold in the register is the
+// exact K'-th score, so a candidate above it enters unless it is rated, and the two-step form reads fill and list twice for it.
+#ifdef CRH_DMA_SCREEN_TWO_TRIP               // (variant build: the two-step form, as before round 15, tools/ab_lib.sh)
+constexpr bool DMA_SCREEN_ONE_TRIP = false;
+#else
+constexpr bool DMA_SCREEN_ONE_TRIP = true;
+#endif
 // MFMA shape of the screen's two launches (fp16 d=128; M16 of the kernel): v_mfma_f32_16x16x32_f16, which holds a higher clock on
 // this power-limited stream than 32x32x16 at the same cycles per flop (round 11).  The approximate scores differ in their last
 // bits (32 products per instruction instead of 16); the screen's certificate covers any fp32 accumulation order.
@@ -254,7 +274,7 @@ __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& ta
             int gi;
             if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, row);
             else gi = (int)(a.item_base + il);
-            dma_candidate<false>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg);
+            dma_candidate<DMA_SCREEN_ONE_TRIP, true>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg);
         }
     }
 }
@@ -492,7 +512,10 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         static_assert(CPW <= 4, "pieces beyond the immediate offset range");
     };
     // candidate bits of the 64 tiles of block blk (tile >> 6) -> tbits[blk & 1].  Issued by EVERY wave with EVERY tile (a
-    // 256-byte piece; the waves write identical bytes): no branch inside the MFMA stream, one more DMA on everybody's counter
+    // 256-byte piece; the waves write identical bytes): no branch inside the MFMA stream, one more DMA on everybody's counter.
+    // (Round 15 measured the thinned form -- one wave, only where a new piece is due: the stream with no such DMA at all is 1.0 %
+    // shorter in cycles per tile, and the scalar branches that thinning needs cost more than that; the headline ran 9 ms slower.
+    // DESIGN 4.1.5, profiles/r15_ids_dma_probe.log)
     auto dma_tbits = [&](int64_t blk) __attribute__((always_inline)) {
         int t = ((int)blk << 6) + lane;
         t = t < n_tiles32 ? t : n_tiles32 - 1;
@@ -740,9 +763,13 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 for (int u = 0; u < UW; ++u) m[u] = acc_max(acc[Q][u]);
             }
             unsigned long long hitm = 0ull;
+            unsigned long long hitb[NU];         // M16: the blocks' own masks, kept for the event (which used to compare again)
             if constexpr (M16 && g == TG) {      // the compares ride the group's MFMAs too (behind them they are paid in full)
 #pragma unroll
-                for (int u = 0; u < NU; ++u) hitm |= __ballot(m[u] > tau[u]);
+                for (int u = 0; u < NU; ++u) {
+                    hitb[u] = __ballot(m[u] > tau[u]);
+                    hitm |= hitb[u];
+                }
 #pragma unroll
                 for (int q = 0; q < NU; ++q) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
@@ -768,7 +795,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
 #pragma unroll
                     for (int u = 0; u < NU; ++u)
-                        if (__ballot(m[u] > tau[u]) != 0ull) {
+                        // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
+                        if ((M16 && !DMA_EVENT_REBALLOT) ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull) {
                             if constexpr (M16)
                                 tile_slow_path_dma16<CM>(acc[Q][u], tau[u], ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, lane, tb,
                                                          rfilter, idv);
