@@ -23,9 +23,11 @@ def crc(*arrays) -> int:
     return c
 
 
-def loss_terms(U, V, feat_rows, users, items, rand_index, temp, lam, reg):
+def loss_terms(U, V, feat_rows, users, items, rand_index, temp, lam, reg, zero_rows=None):
     """U (nu, d), V (ni, d), feat_rows (B (1 + G), d) = the encoder output of every flat row, users (B,), items (B, 1 + G)
-    int64, rand_index int64 (with duplicates).  Returns (L1, L2, R, total)."""
+    int64, rand_index int64 (with duplicates).  Returns (L1, L2, R, total).  ``zero_rows`` = (user ids, item ids) whose
+    table rows are all zeros: their norms (0) are left out of R's two sums, the means keep their denominators -- the
+    same value, and the gradient 0 the kernel documents for such a row where autograd's sqrt at 0 gives NaN."""
     B, G1 = items.shape
     flat = items.reshape(-1)
     u = U[users].repeat_interleave(G1, 0)
@@ -40,17 +42,22 @@ def loss_terms(U, V, feat_rows, users, items, rand_index, temp, lam, reg):
 
     L1 = softmax_loss(F.normalize(pos, dim=1), F.normalize(feat_rows, dim=1))
     L2 = softmax_loss(u, x)
-    R = (torch.sqrt((u ** 2).sum(1)).mean() + torch.sqrt((allv ** 2).sum(1)).mean()) / 2
+    if zero_rows is None:
+        R = (torch.sqrt((u ** 2).sum(1)).mean() + torch.sqrt((allv ** 2).sum(1)).mean()) / 2
+    else:
+        zu, zi = (torch.as_tensor(z, dtype=torch.long, device=users.device) for z in zero_rows)
+        ku, ki = ~torch.isin(users, zu).repeat_interleave(G1), ~torch.isin(flat, zi)
+        R = (torch.sqrt((u[ku] ** 2).sum(1)).sum() / u.shape[0] + torch.sqrt((allv[ki] ** 2).sum(1)).sum() / flat.shape[0]) / 2
     return L1, L2, R, lam * L1 + (1 - lam) * L2 + reg * R
 
 
-def step(U, V, E, users, items, rand_index, temp, lam, reg, dtype=torch.float64):
+def step(U, V, E, users, items, rand_index, temp, lam, reg, dtype=torch.float64, zero_rows=None):
     """One step on leaf copies of the fp32 inputs in ``dtype``; E (n_slots, d) is the encoder output per DISTINCT item
-    (ascending item id).  Returns (terms (4,), dU, dV, dE) as numpy float64."""
+    (ascending item id).  Returns (terms (4,), dU, dV, dE) as numpy float64.  ``zero_rows``: see ``loss_terms``."""
     U, V, E = (t.detach().cpu().to(dtype).requires_grad_() for t in (U, V, E))
     users, items = users.cpu().long(), items.cpu().long()
     slot_item, slot = torch.unique(items.reshape(-1), return_inverse=True)
-    terms = loss_terms(U, V, E[slot], users, items, rand_index.cpu().long(), temp, lam, reg)
+    terms = loss_terms(U, V, E[slot], users, items, rand_index.cpu().long(), temp, lam, reg, zero_rows)
     gU, gV, gE = torch.autograd.grad(terms[3], (U, V, E), allow_unused=True)
     z = lambda g, t: (torch.zeros_like(t) if g is None else g).double().numpy()
     return np.array([float(t.detach()) for t in terms]), z(gU, U), z(gV, V), z(gE, E)

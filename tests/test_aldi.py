@@ -234,3 +234,26 @@ def test_one_case_has_an_unsaturated_identification_term():
     case = CASES[5]
     terms = aldi_restate.step(*_inputs(case), *case[5])[0]
     assert case[5] == (0.0, 1.0, 0.0) and terms[3] > 0.1 and terms[3] == pytest.approx(terms[4] - terms[0])
+
+
+def test_float32_formula_at_the_edge_cases_sets_their_bars():
+    """The measurement behind ALD_LOSS_BAR / ALD_GRAD_BAR of tests/test_loss_edges_gpu.py: float32 torch against float64
+    torch at every new edge case, printed; the bars are 8x the worst of them or this file's own bars, whichever is larger,
+    and the recorded worst figures must be the measured ones within a factor of 2 (another CPU's rounding moves them).
+    At every case min(|tp - sp|, |tn - sn|) >= 1e-5: the two signs of L_rate are the same in every precision."""
+    from tests import test_loss_edges_gpu as edges
+    worst = [0.0, 0.0]
+    for tag, case, inp in edges.ald_edge_cases():
+        want = aldi_restate.step(*inp, *case[5])
+        rel, errs = distances(aldi_restate.step(*inp, *case[5], dtype=torch.float32), want)
+        gap = aldi_restate.min_rate_gap(*inp[:8])
+        print(f"{tag}: float32 torch: loss err / total {rel:.2e}, gradient err / max {errs[0]:.2e} {errs[1]:.2e} "
+              f"{errs[2]:.2e}; min(|tp - sp|, |tn - sn|) {gap:.1e}; terms {want[0]}")
+        worst = [max(worst[0], rel), max(worst[1], max(errs))]
+        assert rel <= edges.ALD_LOSS_BAR and max(errs) <= edges.ALD_GRAD_BAR
+        assert gap >= 1e-5
+    print(f"worst over the edge cases: loss err / total {worst[0]:.2e}, gradient err / max {worst[1]:.2e}")
+    assert edges.ALD_F32_LOSS_WORST / 2 <= worst[0] <= 2 * edges.ALD_F32_LOSS_WORST
+    assert edges.ALD_F32_GRAD_WORST / 2 <= worst[1] <= 2 * edges.ALD_F32_GRAD_WORST
+    assert edges.ALD_LOSS_BAR == max(8 * edges.ALD_F32_LOSS_WORST, LOSS_BAR)
+    assert edges.ALD_GRAD_BAR == max(8 * edges.ALD_F32_GRAD_WORST, GRAD_BAR)

@@ -208,3 +208,22 @@ def test_float32_formula_stays_within_the_kernel_bars(case):
     rel, errs = distances(ccfcrec_restate.step(*inp, case[7], case[8], dtype=torch.float32), want)
     print(f"{IDS(case)}: float32 torch: loss rel {rel:.2e}, gradient err / max {errs[0]:.2e} {errs[1]:.2e} {errs[2]:.2e}")
     assert rel <= LOSS_BAR and max(errs) <= GRAD_BAR
+
+
+def test_float32_formula_at_the_edge_cases_sets_their_bars():
+    """The measurement behind CCF_LOSS_BAR / CCF_GRAD_BAR of tests/test_loss_edges_gpu.py: float32 torch against float64
+    torch at every new edge case, printed; the bars are 8x the worst of them or this file's own bars, whichever is larger,
+    and the recorded worst figures must be the measured ones within a factor of 2 (another CPU's rounding moves them)."""
+    from tests import test_loss_edges_gpu as edges
+    worst = [0.0, 0.0]
+    for tag, case, inp in edges.ccf_edge_cases():
+        want = ccfcrec_restate.step(*inp, case[7], case[8])
+        rel, errs = distances(ccfcrec_restate.step(*inp, case[7], case[8], dtype=torch.float32), want)
+        print(f"{tag}: float32 torch: loss rel {rel:.2e}, gradient err / max {errs[0]:.2e} {errs[1]:.2e} {errs[2]:.2e}")
+        worst = [max(worst[0], rel), max(worst[1], max(errs))]
+        assert rel <= edges.CCF_LOSS_BAR and max(errs) <= edges.CCF_GRAD_BAR
+    print(f"worst over the edge cases: loss rel {worst[0]:.2e}, gradient err / max {worst[1]:.2e}")
+    assert edges.CCF_F32_LOSS_WORST / 2 <= worst[0] <= 2 * edges.CCF_F32_LOSS_WORST
+    assert edges.CCF_F32_GRAD_WORST / 2 <= worst[1] <= 2 * edges.CCF_F32_GRAD_WORST
+    assert edges.CCF_LOSS_BAR == max(8 * edges.CCF_F32_LOSS_WORST, LOSS_BAR)
+    assert edges.CCF_GRAD_BAR == max(8 * edges.CCF_F32_GRAD_WORST, GRAD_BAR)

@@ -96,3 +96,20 @@ def test_float32_restatement_ends_near_g20(restated):
     ev = np.abs(V - fx["V"]).max() / np.abs(fx["V"]).max()
     print(f"float32 restatement: final tables differ from G20 by {eu:.2e} / {ev:.2e} of their scale")
     assert eu < 2e-4 and ev < 2e-4
+
+
+def test_float32_formula_at_the_large_logit_cases_stays_within_the_bars():
+    """tests/test_loss_edges_gpu.py holds the kernel to this file's fixed bars (1e-5 of a loss term, 1e-4 of a gradient's
+    maximum) where the second softmax's scores are hundreds apart: float32 torch against float64 torch there, printed.
+    Measured: loss terms 5.0e-8 / 8.1e-8, gradients 3.0e-6 / 1.8e-5."""
+    from tests import test_loss_edges_gpu as edges
+    from tests.test_clcrec_gpu import REG
+    for scales in edges.CLC_LOGIT_SCALES:
+        case, inp = edges.clc_big_logit_inputs(*scales)
+        want = clcrec_restate.step(*inp, case[5], case[6], REG)
+        got = clcrec_restate.step(*inp, case[5], case[6], REG, dtype=torch.float32)
+        rel = (np.abs(got[0] - want[0]) / np.abs(want[0])).max()
+        errs = [np.abs(g - w).max() / np.abs(w).max() for g, w in zip(got[1:], want[1:])]
+        print(f"U, V, feat, T = {scales}: float32 torch: loss rel {rel:.2e}, gradient err / max {errs[0]:.2e} {errs[1]:.2e} "
+              f"{errs[2]:.2e}; terms {want[0]}")
+        assert np.isfinite(want[0]).all() and rel <= 1e-5 and max(errs) <= 1e-4
