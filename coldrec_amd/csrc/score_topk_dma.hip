@@ -165,6 +165,14 @@ constexpr bool DMA_SCREEN_M16 = false;
 #else
 constexpr bool DMA_SCREEN_M16 = true;
 #endif
+// The common path of the 16x16 form's tile body is placed by hand (round 16, body16 in the kernel): one explicit slot behind each of a
+// tile's 64 MFMAs.  -DCRH_DMA_M16_BODY_OLD (variant build, tools/ab_lib.sh) keeps the body that left the placement to hipcc's
+// sched_group_barrier pipelines.
+#ifdef CRH_DMA_M16_BODY_OLD
+constexpr bool DMA_M16_HOOKED = false;
+#else
+constexpr bool DMA_M16_HOOKED = true;
+#endif
 // CM (compacted stream): row q of the stream is the q-th unmasked item; idv = the ids of this tile's rows (lane l: row l & 31),
 // read from LDS once per event by the caller.  item0 and split_end stay row numbers; there are no masked rows (tb = 0).
 template <bool ONE_TRIP, bool CM>
@@ -340,6 +348,12 @@ __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& ta
 //   * a 16-cycle MFMA hides two other instructions, a 32-cycle one six, so the threshold test is spread: the maxima in group 0,
 //     the barrier and the DMA issue in group 1, the compares and the events behind group 2.  (An event reads registers, the id
 //     slots and the tile bits of tile j-1, all of which outlive body j: its place inside the body is free.)
+//   * since round 16 the common path of this form is `body16` below, placed by hand: one explicit slot behind each MFMA, body 0
+//     peeled out of the loop, `live` folded into the thresholds, the ring slot taken from the tile counter.  `body` with M16 is what
+//     -DCRH_DMA_M16_BODY_OLD builds: it asks hipcc for the same spread by sched_group_barrier pipelines, which do not count the
+//     inline-asm maxima as VALU -- in its listing four maxima stand in front of group 0's first MFMA, eight gaps carry four each,
+//     the second half of group 2 and all of group 3 are bare, and the loop edge, the ring-slot chain through a spilled SGPR and the
+//     tail's `j > 0` / `live` tests (about 25 instructions per tile) stand between the groups, hidden by no MFMA.
 // The approximate scores differ from the 32x32 form's in their last bits (another accumulation order); the screen's results do not
 // (stage 2 rescores, and its bound covers any fp32 accumulation order).  The public fp16 routes never run this kernel at d=128.
 template <typename T, int D, int R, bool FL, bool CM = false, bool M16 = false>
@@ -470,6 +484,14 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         for (int q = 0; q < BQ; ++q) {
             b[q][u] = load16(up + (M16 ? 64 : 32) * q);      // M16: lane (c, g) holds halfs 32 q + 8 g .. + 7 of user 16 u + c
             if constexpr (Elem<T>::kSwap) chunk_swap(b[q][u]);
+        }
+    }
+    // the hooked 16x16 body tests no `live` per tile: a dead wave walks, synchronises and fetches like any other, and with +inf for
+    // every threshold none of its maxima is a hit (it has no list to insert into and stores nothing)
+    if constexpr (M16 && DMA_M16_HOOKED) {
+        if (!live) {
+#pragma unroll
+            for (int u = 0; u < NU; ++u) tau[u] = __builtin_inff();
         }
     }
     // the user fragments live in AGPRs from here on (and have landed: nothing of theirs is left on the VM counter)
@@ -746,9 +768,10 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     Elem<T>::template mma<UW>(acc[P], c[g & 3][jj], b[g * GR + jj]);
                 }
             }
-            // the maxima of tile j-1's accumulators.  M16: a 16-cycle MFMA hides two instructions where a 32-cycle one hides six, so the
-            // test is spread over three groups -- the maxima in group 0, which carries nothing else (two per MFMA), the barrier and
-            // the DMA issue in group 1 as ever, the compares and the event in group 2 (TG)
+            // the maxima of tile j-1's accumulators.  M16 (the old body; body16 places them by hand): a 16-cycle MFMA hides two instructions
+            // where a 32-cycle one hides six, so the test is spread over three groups -- the maxima in group 0 (two per MFMA are asked
+            // for; the pipeline below does not see the asm statements as VALU, and hipcc puts up to four into a gap and four in front
+            // of the group), the barrier and the DMA issue in group 1 as ever, the compares and the event in group 2 (TG)
             if constexpr (M16 && g == 0) {
 #pragma unroll
                 for (int u = 0; u < NU; ++u) m[u] = acc_max(acc[Q][u]);
@@ -821,6 +844,162 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         }(std::make_integer_sequence<int, NG>{});
     };
 
+    // ---- M16: the hand-placed body (round 16).  The same tile as `body` above -- the same 64 MFMAs in the same order, ring, id slots,
+    // barrier, DMAs and event -- but every MFMA is followed by ONE slot (hook(g, n), n = the MFMA just issued, fenced by
+    // sched_barrier(0)), so what the source puts into a gap stands there in the listing.  A 16-cycle MFMA holds vector issue for 8 of its
+    // cycles: a gap hides two 4-cycle vector instructions, or one vector and one or two scalar; a ds_read_b128 or a DMA has a gap to itself.
+    //   group 0   gaps 0..15  two of tile j-1's 32 maxima each (user block n >> 1)
+    //   group 1   in front: vmcnt, barrier, the counted fragment wait.  gap 0 the tile index, 1 the side-band address, 2 the side-band DMA
+    //             (ids, or tile bits), 3 the tile's address, 4 / 5 its two pieces, 8 / 9 the fragment reads of group 3, 10 the ring base
+    //   group 2   gaps 0..7 one compare and its s_or each, 8 / 9 the fragment reads of tile j+1's group 0
+    //   group 3   gaps 0 / 1 and 6 / 7 the fragment reads of tile j+1's groups 1 and 2
+    // The fragment reads are issued in the order g0, g1, g2 (tile j+1), g3 (tile j), two each, every one behind the barrier that publishes
+    // its tile and at least 22 MFMAs in front of its group: the counted waits in front of groups 0..3 are lgkmcnt(4), (2), (2), (2).
+    // Tile j lives in ring slot j & 3.  ring_a = the LDS base of slot j & 2 of the pair (even tile, odd tile) being multiplied; the odd
+    // body moves it on behind its last use, and every other slot is an immediate offset.  Body 0 is peeled (FIRST: no tile in front of
+    // it to test, so no `j > 0` in the tail), `live` is folded into the thresholds: the tail is one compare and one branch.
+    uint32_t ring_a = ring_lds;
+    int next_sync = 0;           // first tile of the next lockstep window (wave 0; beyond the range elsewhere), set in front of the loop
+    bool sync_due = false;       // the even body's trip head has a window to report: worked out in a gap of the odd body in front of it
+    auto lds_read1 = [&](f32x4& dst, uint32_t addr, auto Oc) __attribute__((always_inline)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(decltype(Oc)::value));
+#endif
+    };
+    auto body16 = [&](auto Pc, auto Fc, int j) __attribute__((always_inline)) {
+        constexpr int P = decltype(Pc)::value, Q = 1 - P;
+        constexpr bool FIRST = decltype(Fc)::value;
+        constexpr int LA = P ? 0 : TILE_B;      // tile j+1 from ring_a: the even body's partner slot, the odd body's moved-on base
+        static_assert(CPW == 2 || !M16, "two pieces per wave");
+        float m[NU], a0[NU], a1[NU], a2[NU];
+        unsigned long long hitm = 0ull;
+        unsigned long long hitb[NU];
+        int tc = 0, tf = 0;
+        const unsigned* side = nullptr;
+        const char* gt = nullptr;
+        auto hook = [&](auto Gc, auto Nc) __attribute__((always_inline)) {
+            constexpr int g = decltype(Gc)::value, n = decltype(Nc)::value;
+            if constexpr (g == 0 && !FIRST) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                constexpr int u = n >> 1;
+                const AccT& v = acc[Q][u];
+                if constexpr ((n & 1) == 0) {
+                    asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(a0[u]) : "v"(v[0]), "v"(v[1]), "v"(v[2]));
+                    asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(a1[u]) : "v"(v[3]), "v"(v[4]), "v"(v[5]));
+                } else {
+                    asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(a2[u]) : "v"(v[6]), "v"(v[7]), "v"(a0[u]));
+                    asm volatile("v_max_f32 %0, %1, %2" : "=v"(m[u]) : "v"(a1[u]), "v"(a2[u]));
+                }
+#endif
+            }
+            if constexpr (g == BG) {
+                // tile j+3 into the slot tile j-1 left, and its side band, in the issue order of `body`: side band, piece 0, piece 1
+                if constexpr (n == 0) {
+                    tc = (int)t0 + j + 3;
+                    tc = tc < n_tiles32 ? tc : n_tiles32 - 1;
+                    tf = (CRH_ABLATE(a.ablate) & 2) ? 0 : tc;
+                }
+                if constexpr (n == 1) {
+                    if constexpr (CM) {
+                        unsigned e = ((unsigned)tc << 5) + (unsigned)lane;
+                        const unsigned e_max = ((unsigned)n_tiles32 << 5) - 1u;
+                        e = e < e_max ? e : e_max;
+                        side = reinterpret_cast<const unsigned*>(a.idmap) + e;
+                    } else {
+                        int t = ((int)((t0 + j + 32) >> 6) << 6) + lane;
+                        t = t < n_tiles32 ? t : n_tiles32 - 1;
+                        side = reinterpret_cast<const unsigned*>(a.tile_bits) + (unsigned)t;
+                    }
+                }
+                if constexpr (n == 2) {
+                    unsigned* dst = CM ? tbits + ((j + 3) & (IDS_SLOTS - 1)) * 32 : tbits + (((t0 + j + 32) >> 6) & 1) * 64;
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)side,
+                                                     (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
+                }
+                if constexpr (n == 3) gt = my_pieces + (int64_t)tf * TILE_B;
+                if constexpr (n == 4 || n == 5) {
+                    char* l = ring + ((j + 3) & (R - 1)) * TILE_B + (wave * CPW) * 1024;
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gt,
+                                                     (__attribute__((address_space(3))) void*)l, 16, (n - 4) * 1024, 0);
+                }
+                if constexpr (n == 8) lds_read1(c[3][0], ring_a, std::integral_constant<int, P * TILE_B + 3 * 2048>{});
+                if constexpr (n == 9) lds_read1(c[3][1], ring_a, std::integral_constant<int, P * TILE_B + 3 * 2048 + 256>{});
+                // odd body: that was the pair's last read; the next pair (and this body's look-ahead) starts at slot (j + 1) & 2
+                if constexpr (n == 10 && P == 1) ring_a = ring_lds + (unsigned)((j + 1) & 2) * TILE_B;
+            }
+            if constexpr (g == TG) {
+                if constexpr (n < NU && !FIRST) {
+                    hitb[n] = __ballot(m[n] > tau[n]);
+                    hitm |= hitb[n];
+                }
+                if constexpr (n == 8) lds_read1(c[0][0], ring_a, std::integral_constant<int, LA>{});
+                if constexpr (n == 9) lds_read1(c[0][1], ring_a, std::integral_constant<int, LA + 256>{});
+            }
+            if constexpr (g == 3) {
+                if constexpr (n == 0) lds_read1(c[1][0], ring_a, std::integral_constant<int, LA + 2048>{});
+                if constexpr (n == 1) lds_read1(c[1][1], ring_a, std::integral_constant<int, LA + 2048 + 256>{});
+                if constexpr (n == 6) lds_read1(c[2][0], ring_a, std::integral_constant<int, LA + 2 * 2048>{});
+                if constexpr (n == 7) lds_read1(c[2][1], ring_a, std::integral_constant<int, LA + 2 * 2048 + 256>{});
+                if constexpr (n == 8 && P == 1) sync_due = (j + 1 >= next_sync) & (j + 1 < n_steps);
+            }
+        };
+        auto group = [&](auto Gc) __attribute__((always_inline)) {
+            constexpr int g = decltype(Gc)::value;
+            if constexpr (g == BG) {
+                dma_wait_but_newest_tile();             // my pieces of tile j+1 (issued two tiles ago) have landed
+                if (!(CRH_ABLATE(a.ablate) & 4)) __builtin_amdgcn_s_barrier();
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (g == 0) lds_wait(c[g], std::integral_constant<int, 4>{});
+            else lds_wait(c[g], std::integral_constant<int, 2>{});
+            __builtin_amdgcn_sched_barrier(0);
+            [&]<int... N>(std::integer_sequence<int, N...>) __attribute__((always_inline)) {
+                (([&]() __attribute__((always_inline)) {
+                     constexpr int mb = N >> 3, u = N & 7;
+                     AccT& x = acc[P][u];
+                     f32x4 t = mb ? f32x4{x[4], x[5], x[6], x[7]} : f32x4{x[0], x[1], x[2], x[3]};
+                     if constexpr (g == 0) t = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                     t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, c[g][mb]), __builtin_bit_cast(f16x8, b[g][u]), t, 0, 0, 0);
+#pragma unroll
+                     for (int r = 0; r < 4; ++r) x[4 * mb + r] = t[r];
+                     __builtin_amdgcn_sched_barrier(0);
+                     hook(Gc, std::integral_constant<int, N>{});
+                     __builtin_amdgcn_sched_barrier(0);
+                 }()),
+                 ...);
+            }(std::make_integer_sequence<int, 16>{});
+            if constexpr (g == TG && !FIRST) {
+                if (hitm != 0ull && !(CRH_ABLATE(a.ablate) & 1)) {
+#ifdef CRH_PROFILE
+                    const unsigned long long ev_t0 = a.wave_clock != nullptr ? __builtin_amdgcn_s_memtime() : 0ull;
+#endif
+                    const int64_t ts = t0 + j - 1;                                      // the tile being selected
+                    const unsigned tb = has_bits ? tbits[((ts >> 6) & 1) * 64 + (ts & 63)] : 0u;
+                    int idv = 0;                     // CM: the selected tile's ids, one LDS read per event (where tb's was)
+                    if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
+#pragma unroll
+                    for (int u = 0; u < NU; ++u)
+                        // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
+                        if (!DMA_EVENT_REBALLOT ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull)
+                            if constexpr (M16)       // (the other forms never call this body, but they parse it)
+                                tile_slow_path_dma16<CM>(acc[Q][u], tau[u], ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, lane, tb,
+                                                     rfilter, idv);
+                    // the list stores of the inserts are drained HERE (as in `body`); the fragment reads in flight land with them
+                    __builtin_amdgcn_s_waitcnt(0xc07f);
+#ifdef CRH_PROFILE
+                    if (a.wave_clock != nullptr) {      // CRH_SCORE_TIMING: cycles spent in events and their number, per wave
+                        ev_ticks += __builtin_amdgcn_s_memtime() - ev_t0;
+                        ev_count += 1;
+                    }
+#endif
+                }
+            }
+        };
+        [&]<int... Gs>(std::integer_sequence<int, Gs...>) __attribute__((always_inline)) {
+            (group(std::integral_constant<int, Gs>{}), ...);
+        }(std::make_integer_sequence<int, NG>{});
+    };
+
     if (n_steps > 0) {
         if constexpr (CM) {
             dma_ids(0);                                   // tiles 0 .. 3; body j brings tile j + 3 (and j + 4)
@@ -840,7 +1019,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         // XCD soft lockstep (see xcd_window_sync): wave 0 reports / waits for the workgroup, the others meet it at the
         // tile's barrier
         unsigned* sync_cnt = nullptr;
-        int win_steps = 0, next_sync = n_steps + 4;
+        int win_steps = 0;
+        next_sync = n_steps + 4;
         if (a.xcd_sync && wave == 0) {
             const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7u;   // HW_REG_XCC_ID
             sync_cnt = a.xcd_sync + (int64_t)xcc * a.sync_stride;
@@ -852,7 +1032,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 #ifdef CRH_PROFILE
         unsigned long long t_prev = 0;                  // CRH_SCORE_TIMING: duration of every PAIR of tiles, histogrammed per wave
 #endif
-        for (int j = 0; j <= n_steps; j += 2) {
+        // the head of a loop trip: the CRH_SCORE_TIMING stamp (profile build only) and the lockstep window
+        auto trip_head = [&](int j, bool due) __attribute__((always_inline)) {
 #ifdef CRH_PROFILE
             if (a.wave_clock != nullptr && blockIdx.x < 16) {
                 const unsigned long long t_now = __builtin_amdgcn_s_memtime();
@@ -865,7 +1046,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 t_prev = t_now;
             }
 #endif
-            if (j >= next_sync && j < n_steps) {       // wave 0 only (next_sync stays beyond the range elsewhere)
+            if (due) {       // j >= next_sync && j < n_steps: wave 0 only (next_sync stays beyond the range elsewhere)
                 const int win = j / win_steps;
                 if (xcd_window_sync(sync_cnt, win, lane)) {
                     next_sync += win_steps;
@@ -877,12 +1058,29 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                             __hip_atomic_fetch_add(sync_cnt + 1 + wdw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
-            const int s1 = (s0 + 1) & (R - 1), s2 = (s0 + 2) & (R - 1);
-            // barrier form: tile j+3 -> slot of tile j-1 = s0 + 3, tile j+4 -> slot of tile j; flag form: tile j + PF -> its own slot
-            body(std::integral_constant<int, 0>{}, j, s0, s1, (s0 + PF) & (R - 1));
-            if (j + 1 > n_steps) break;
-            body(std::integral_constant<int, 1>{}, j + 1, s1, s2, (s1 + PF) & (R - 1));
-            s0 = s2;
+        };
+        if constexpr (M16 && DMA_M16_HOOKED) {
+            // body 0 peeled; a trip is then the odd body and the even one behind it, with the trip's head (an even j, as ever) between them
+            lds_group(c[2], ring_lds, std::integral_constant<int, 2>{});
+            trip_head(0, 0 >= next_sync);
+            body16(std::integral_constant<int, 0>{}, std::true_type{}, 0);
+            for (int j = 1;; j += 2) {                    // (n_steps >= 1: body 1 always runs)
+                body16(std::integral_constant<int, 1>{}, std::false_type{}, j);
+                if (j + 1 > n_steps) break;
+                trip_head(j + 1, sync_due);
+                body16(std::integral_constant<int, 0>{}, std::false_type{}, j + 1);
+                if (j + 2 > n_steps) break;
+            }
+        } else {
+            for (int j = 0; j <= n_steps; j += 2) {
+                trip_head(j, j >= next_sync && j < n_steps);
+                const int s1 = (s0 + 1) & (R - 1), s2 = (s0 + 2) & (R - 1);
+                // barrier form: tile j+3 -> slot of tile j-1 = s0 + 3, tile j+4 -> slot of tile j; flag form: tile j + PF -> its own slot
+                body(std::integral_constant<int, 0>{}, j, s0, s1, (s0 + PF) & (R - 1));
+                if (j + 1 > n_steps) break;
+                body(std::integral_constant<int, 1>{}, j + 1, s1, s2, (s1 + PF) & (R - 1));
+                s0 = s2;
+            }
         }
         dma_wait_all();   // the prefetches of the last bodies must not outlive the workgroup's LDS ...
 #if defined(__HIP_DEVICE_COMPILE__)
