@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Randomised parity fuzzing of the three fused loss kernels (csrc/clcrec.hip, csrc/ccfcrec.hip, csrc/aldi.hip) against
-their float64 restatements (tests/clcrec_restate.py, tests/ccfcrec_restate.py, tests/aldi_restate.py).
+"""Randomised parity fuzzing of the four fused loss kernels (csrc/clcrec.hip, csrc/ccfcrec.hip, csrc/aldi.hip,
+csrc/infonce.hip) against their float64 restatements (tests/clcrec_restate.py, tests/ccfcrec_restate.py,
+tests/aldi_restate.py, tests/infonce_restate.py).
 
-Per case: a width from every multiple of 4 in [4, 256], small B, G, P, N and S (now and then a batch long enough for an
+CLCRec, CCFCRec, ALDI, per case: a width from every multiple of 4 in [4, 256], small B, G, P, N and S (now and then a batch long enough for an
 owner to split into chunks), an id pattern per id tensor from {uniform, a few hot ids, one owner}, a scale per table from
 {0.05, 0.3, 1.5} and temperatures / coefficients the trainers accept.  Then
   * the kernel against the float64 restatement.  The bar of a case is 8x the distance of the float32 restatement from the
@@ -12,9 +13,21 @@ owner to split into chunks), an id pattern per id tensor from {uniform, a few ho
     rounding noise in any float32 evaluation; ALDI's, as in its file, over the total); gradients: error over the table's
     maximum; a gradient the restatement leaves all zero must be all zero;
   * a second, identical call: every output bit-equal.
-On a mismatch the seed and the drawn parameters are printed and the exit status is 1.
+InfoNCE (kind ``infonce``), per case: a width from every multiple of 4 in [4, 256]; N mostly in [1, 700] with extra weight
+on 32 k - 1, 32 k, 32 k + 1 and 128 k +- 1, one case in ten in [1000, 2100]; tau from {0.05, 0.2, 1.0}; b_cos on or off
+(rows of length ~scale then, at most sqrt(10 tau)); a scale from the same three; a share of near-duplicate rows
+v2 = v1 + 2 % noise from {0, 1/4, all}, the other rows augmented (v1 + 70 % noise) or independent; now and then a zero
+row; a mode from {the whole view, row ids, row ids with a device count n_dev < n_max, row ids with scale + accumulate
+on pre-filled tables}.  Row ids are permutations (the op wants them unique).  Then
+  * the kernel against the float64 restatement: the loss's relative error within max(8x the float32 restatement's, 1e-5),
+    no absolute floor; each gradient row by row, rho = max over rows of max|row error| / max|reference row|, within
+    max(8x the float32 restatement's rho, 1e-4); a row the restatement leaves all zero must be all zero;
+  * a second, identical call bit-equal; every table row outside the batch untouched; scale (a power of two) + accumulate
+    equal to pre + scale * g bit for bit.
+On a mismatch the seed and the drawn parameters are printed and the exit status is 1.  Without --only every case draws its
+kind from all four; with it, from the kinds named, in the order named.
 
-    python tests/fuzz/fuzz_loss_ops.py --cases 200 [--seed 0] [--only clcrec,ccfcrec,aldi]
+    python tests/fuzz/fuzz_loss_ops.py --cases 200 [--seed 0] [--only clcrec,ccfcrec,aldi,infonce]
 """
 import argparse
 import os
@@ -26,7 +39,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from coldrec_amd import ops  # noqa: E402
-from tests import aldi_restate, ccfcrec_restate, clcrec_restate  # noqa: E402
+from tests import aldi_restate, ccfcrec_restate, clcrec_restate, infonce_restate  # noqa: E402
 from tests import test_aldi_gpu as ald  # noqa: E402
 from tests import test_ccfcrec_gpu as ccf  # noqa: E402
 
@@ -165,7 +178,108 @@ def case_aldi(rng):
     judge("aldi", params, lambda: ops.aldi(*dev, *coef), want, f32, (ald.LOSS_BAR, ald.GRAD_BAR), over_total=True)
 
 
-KINDS = {"clcrec": case_clcrec, "ccfcrec": case_ccfcrec, "aldi": case_aldi}
+def draw_nce_rows(rng):
+    """The batch size: mostly 1 .. 700 with extra weight beside the wave (32 k) and workgroup (128 k) edges; one case in
+    ten 1000 .. 2100, where the column splits hold more than one tile and some hold none."""
+    u = rng.random()
+    if u < 0.10:
+        return int(rng.integers(1000, 2101))
+    if u < 0.40:
+        return 32 * int(rng.integers(1, 22)) + int(rng.integers(-1, 2))
+    if u < 0.55:
+        return 128 * int(rng.integers(1, 6)) + int(rng.choice([-1, 1]))
+    return int(rng.integers(1, 701))
+
+
+def case_infonce(rng):
+    d = 4 * int(rng.integers(1, 65))
+    n = draw_nce_rows(rng)
+    tau, b_cos = float(rng.choice([0.05, 0.2, 1.0])), bool(rng.random() < 0.7)
+    scale = float(rng.choice(SCALES))
+    # raw dot products: rows of length ~scale, and no longer than sqrt(10 tau), so that |v|^2 / tau stays within the ~87
+    # nats of fp32's exp at the narrow widths too (beyond it every float32 evaluation flushes the off-diagonal terms)
+    row_scale = scale if b_cos else min(scale, float(np.sqrt(10.0 * tau))) / np.sqrt(d)
+    mode = str(rng.choice(["whole", "rows", "n_dev", "accumulate"]))
+    near = float(rng.choice([0.0, 0.25, 1.0]))
+    rest = str(rng.choice(["augmented", "independent"]))
+    zero_row = bool(rng.random() < 0.15)
+    extra = 0 if mode == "whole" else int(rng.integers(1, 41))
+    r1n, r2n = n + extra + (0 if mode == "whole" else int(rng.integers(0, 30))), n + extra + (0 if mode == "whole" else 5)
+    params = dict(d=d, n=n, tau=tau, b_cos=b_cos, scale=scale, mode=mode, near=near, rest=rest, zero_row=zero_row,
+                  tables=(r1n, r2n))
+    # the batch, then its rows scattered into the tables
+    v1 = table(rng, n, d, row_scale)
+    k = int(round(n * near))
+    v2 = v1 + table(rng, n, d, row_scale) * 0.7 if rest == "augmented" else table(rng, n, d, row_scale)
+    v2[:k] = v1[:k] + table(rng, k, d, row_scale) * 0.02
+    if zero_row:
+        which, at = int(rng.integers(0, 3)), int(rng.integers(0, n))
+        if which != 1:
+            v1[at] = 0.0
+        if which != 0:
+            v2[at] = 0.0
+    want = [t.numpy() for t in infonce_restate.infonce(v1, v2, tau, b_cos)[1:]]
+    f32 = [t.numpy() for t in infonce_restate.infonce(v1, v2, tau, b_cos, dtype=torch.float32)[1:]]
+    if mode == "whole":
+        T1, T2, rows1, rows2 = v1.to(DEV), v2.to(DEV), None, None
+    else:
+        T1, T2 = table(rng, r1n, d, row_scale), table(rng, r2n, d, row_scale)
+        p1, p2 = rng.permutation(r1n), rng.permutation(r2n)
+        T1[torch.from_numpy(p1[:n])], T2[torch.from_numpy(p2[:n])] = v1, v2
+        T1, T2 = T1.to(DEV), T2.to(DEV)
+        m = n + extra if mode == "n_dev" else n          # n_dev < n_max: the row ids go on past the batch
+        rows1, rows2 = (torch.from_numpy(p[:m].astype(np.int32)).to(DEV) for p in (p1, p2))
+    n_dev = torch.tensor([n], dtype=torch.int32, device=DEV) if mode == "n_dev" else None
+
+    def fused():
+        if mode == "whole":
+            return ops.infonce(T1, T2, tau, b_cos)
+        G1, G2 = torch.full_like(T1, 3.0), torch.full_like(T2, 3.0)
+        loss, _, _ = ops.infonce(T1, T2, tau, b_cos, rows1=rows1, rows2=rows2, n_dev=n_dev, grad1=G1, grad2=G2)
+        return loss, G1, G2
+
+    a, b = fused(), fused()
+    torch.cuda.synchronize()
+    if not all(torch.equal(x, y) for x, y in zip(a, b)):
+        fail("infonce: two identical calls differ in their bits", **params)
+    loss, g1, g2 = a
+    if mode != "whole":
+        for G, r in ((g1, rows1), (g2, rows2)):
+            untouched = torch.ones(G.shape[0], dtype=torch.bool, device=DEV)
+            untouched[r[:n].long()] = False
+            if not (G[untouched] == 3.0).all():
+                fail("infonce: a row outside the batch was written", **params)
+        if mode == "accumulate":                         # a power of two: pre + scale * g holds bit for bit
+            s = float(rng.choice([0.25, 0.5, 2.0]))
+            P1, P2 = torch.from_numpy(rng.standard_normal((r1n, d)).astype(np.float32)).to(DEV), \
+                torch.from_numpy(rng.standard_normal((r2n, d)).astype(np.float32)).to(DEV)
+            A1, A2 = P1.clone(), P2.clone()
+            la, _, _ = ops.infonce(T1, T2, tau, b_cos, rows1=rows1, rows2=rows2, scale=s, accumulate=True, grad1=A1, grad2=A2)
+            for A, P, G, r in ((A1, P1, g1, rows1), (A2, P2, g2, rows2)):
+                E = P.clone()
+                E[r.long()] += s * G[r.long()]
+                if not torch.equal(A, E):
+                    fail("infonce: scale + accumulate is not pre + scale * g bit for bit", accumulate_scale=s, **params)
+            if not torch.equal(la, loss):
+                fail("infonce: scale + accumulate changed the loss", accumulate_scale=s, **params)
+        g1, g2 = g1[rows1[:n].long()], g2[rows2[:n].long()]
+    got = [t.cpu().numpy() for t in (loss[0], g1, g2)]
+    if not all(np.isfinite(t).all() for t in got):
+        fail("infonce: output not finite", **params)
+    # loss: relative, no absolute floor (a batch of one has the loss 0: then exactly); gradients: row by row
+    top = abs(float(want[0]))
+    rel, rel32 = (abs(float(x[0]) - float(want[0])) / top if top > 0 else abs(float(x[0])) for x in (got, f32))
+    rho = [infonce_restate.row_rho(g, w) for g, w in zip(got[1:], want[1:])]
+    rho32 = [infonce_restate.row_rho(g, w) for g, w in zip(f32[1:], want[1:])]
+    for g, w in zip(got[1:], want[1:]):
+        if g[(w == 0).all(1)].any():
+            fail("infonce: gradient not zero where the restatement's row is", **params)
+    bars = (max(8 * rel32, 1e-5), max(8 * rho32[0], 1e-4), max(8 * rho32[1], 1e-4))
+    if not (rel <= bars[0] and rho[0] <= bars[1] and rho[1] <= bars[2]):
+        fail("infonce against the float64 restatement", loss=rel, rho=rho, bars=bars, float32=(rel32, rho32), **params)
+
+
+KINDS = {"clcrec": case_clcrec, "ccfcrec": case_ccfcrec, "aldi": case_aldi, "infonce": case_infonce}
 
 
 def main():

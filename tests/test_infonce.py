@@ -1,12 +1,16 @@
 """CPU-only checks of crh_infonce_f32 (include/coldrec_hip.h): argument errors without a GPU, the workspace formula, and a
 float64 restatement of InfoNCE's loss and closed-form gradients that reproduces G18(i), the reference's own autograd numbers.
 The restatement pins the math the kernel implements (P - I, F.normalize's clamped backward) to the reference; the GPU tests
-check the kernel against G18(i) directly and against float64 torch autograd of the formula."""
+check the kernel against G18(i) directly and against float64 torch autograd of the formula.  tests/infonce_restate.py restates
+the same loss in the form that does not cancel where P_ii ~ 1 (the reference of tests/test_infonce_edges_gpu.py and of the
+fuzzer): it is pinned here to G18(i), to float64 autograd, and -- in float32 -- shown to hold the row-by-row bar that plain
+float32 autograd misses."""
 import numpy as np
 import pytest
 import torch
 
 from coldrec_amd import _lib, ops
+from tests import infonce_restate
 from tests.conftest import load_golden
 
 
@@ -57,6 +61,73 @@ def test_float64_restatement_reproduces_the_references_infonce_g18():
             for sel in (zero, ~zero):
                 if sel.any():
                     assert np.abs(got[sel] - ref[sel]).max() <= 1e-10 * max(np.abs(ref[sel]).max(), 1e-30), name
+
+
+def test_cancellation_free_restatement_reproduces_g18():
+    """tests/infonce_restate.py in float64 against the reference's own numbers, to the bars infonce64 is held to above."""
+    g = load_golden("g18_infonce.npz")
+    for name in g["cases"]:
+        name = str(name)
+        b_cos = bool(g[f"{name}_bcos"])
+        term, loss, g1, g2 = infonce_restate.infonce(g[f"{name}_v1"], g[f"{name}_v2"], float(g[f"{name}_tau"]), b_cos)
+        want = float(g[f"{name}_loss"])
+        assert abs(float(loss) - want) <= 1e-12 * max(1.0, abs(want)), name
+        assert term.shape == (g[f"{name}_v1"].shape[0],)
+        for v, got, ref in ((g[f"{name}_v1"], g1.numpy(), g[f"{name}_g1"]), (g[f"{name}_v2"], g2.numpy(), g[f"{name}_g2"])):
+            zero = (np.abs(v).sum(1) == 0) & b_cos
+            for sel in (zero, ~zero):
+                if sel.any():
+                    assert np.abs(got[sel] - ref[sel]).max() <= 1e-10 * max(np.abs(ref[sel]).max(), 1e-30), name
+
+
+def _plain_views(n, d, seed, scale):
+    g = torch.Generator().manual_seed(seed)
+    v1 = torch.randn(n, d, generator=g) * scale
+    return v1, v1 + torch.randn(n, d, generator=g) * (scale * 0.7)
+
+
+def test_cancellation_free_restatement_agrees_with_float64_autograd():
+    """Row by row, to 1e-8 of each row's own maximum, wherever float64 autograd of the formula is itself good: inputs whose
+    smallest 1 - P_ii is >= 1e-7 (asserted).  Closer to 1 autograd's (P - I) cancels in float64 too -- 6e-10 at 7e-8 on
+    mixed-256x64, about 3e-7 at 1e-10 -- and stops being a reference; the restatement does not cancel there."""
+    cases = {k: v[:3] + (True,) for k, v in infonce_restate.peaked_cases().items() if k in ("mixed-130x132", "peaked-64x32",
+                                                                                          "anti-64x32")}
+    for tau in (0.05, 0.2, 1.0):
+        for b_cos in (True, False):
+            cases[f"plain-{tau}-{int(b_cos)}"] = _plain_views(97, 36, 11, 0.3 if b_cos else 0.08) + (tau, b_cos)
+    worst = 0.0
+    for name, (v1, v2, tau, b_cos) in cases.items():
+        assert infonce_restate.one_minus_pii(v1, v2, tau, b_cos).min() >= 1e-7, name
+        _, loss, g1, g2 = infonce_restate.infonce(v1, v2, tau, b_cos)
+        l64, a64, b64 = infonce_restate.autograd(v1, v2, tau, b_cos)
+        assert abs(float(loss) - float(l64)) <= 1e-12 * max(1.0, abs(float(l64))), name
+        rho = max(infonce_restate.row_rho(g1, a64), infonce_restate.row_rho(g2, b64))
+        worst = max(worst, rho)
+        assert rho <= 1e-8, (name, rho)
+    print(f"restatement vs float64 autograd, worst row-relative distance: {worst:.1e}")
+
+
+def test_peaked_cases_tell_the_stable_float32_form_from_the_naive_one():
+    """The teeth of tests/test_infonce_edges_gpu.py's row-by-row bars, on the CPU.  On every peaked case the float32
+    restatement lies within 1e-4 / 8 of the float64 one, row by row (so the GPU bar max(8 x that, 1e-4) is 1e-4 and a
+    correct float32 evaluation meets it), and within 1e-5 / 8 on the loss; plain float32 autograd of the formula is off by
+    >= 1e-3 on g1 of every case with peaked rows (so a kernel that fell back to the naive diagonal could not pass).
+    Measured: restatement 3.7e-6 .. 8.3e-6 (gradients), 5e-9 .. 6.5e-7 (loss); plain autograd 5.6e-3 .. 1.3e-1 on g1."""
+    for name, (v1, v2, tau, peaked) in infonce_restate.peaked_cases().items():
+        _, l64, a64, b64 = infonce_restate.infonce(v1, v2, tau)
+        _, l32, a32, b32 = infonce_restate.infonce(v1, v2, tau, dtype=torch.float32)
+        _, an, _ = infonce_restate.autograd(v1, v2, tau, dtype=torch.float32)
+        rho = max(infonce_restate.row_rho(a32, a64), infonce_restate.row_rho(b32, b64))
+        rel = abs(float(l32) - float(l64)) / abs(float(l64))
+        naive = infonce_restate.row_rho(an, a64)
+        print(f"{name}: float32 restatement rho {rho:.2e} loss {rel:.2e}; plain float32 autograd rho(g1) {naive:.2e}")
+        assert rho <= 1e-4 / 8, (name, rho)
+        assert rel <= 1e-5 / 8, (name, rel)
+        if peaked.any():
+            assert infonce_restate.one_minus_pii(v1, v2, tau)[peaked.numpy()].max() <= 1e-3, name
+            assert naive >= 1e-3, (name, naive)
+    anti = infonce_restate.peaked_cases()["anti-64x32"]
+    assert (infonce_restate.diag_binades_under_max(*anti[:3]) > 100).sum() >= 8
 
 
 def test_g18_covers_the_cases_the_issue_names():

@@ -448,10 +448,11 @@ FUZZ_CASES, FUZZ_SEED = 60, 2025
 
 
 def test_loss_fuzzer_short_run():
-    """tests/fuzz/fuzz_loss_ops.py --cases 60 --seed 2025 in a child process: 60 random cases over the three kernels.
+    """tests/fuzz/fuzz_loss_ops.py --only clcrec,ccfcrec,aldi --cases 60 --seed 2025 in a child process: 60 random cases
+    over the three kernels (--only keeps the fuzzer's later kinds out of the draw: the same 60 cases as before them).
     Measured on the MI355X: 3.1 s for the whole child, the interpreter's start and the library's load included."""
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "fuzz", "fuzz_loss_ops.py"), "--cases", str(FUZZ_CASES), "--seed",
-           str(FUZZ_SEED)]
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "fuzz", "fuzz_loss_ops.py"), "--only", "clcrec,ccfcrec,aldi",
+           "--cases", str(FUZZ_CASES), "--seed", str(FUZZ_SEED)]
     t0 = time.time()
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     print(f"fuzzer: {time.time() - t0:.1f} s; {out.stdout.strip().splitlines()[-1:]}")
