@@ -981,7 +981,7 @@ int64_t seed_route(int esz, int64_t n_users, int64_t n_items, int d) {
 
 // The screened route (score_screen.hip): fp16 screen of K' candidates per user by the LDS-DMA kernel, exact
 // rescoring, a per-user certificate, exact fallback for the users without one.  Its workspace, front to back.
-constexpr int SCREEN_KP = 28;                   // K': k <= 28 lists fit beside the DMA kernel's four slots of 256-byte rows
+// (K' = SCREEN_KP: score_topk_common.h -- the 16x16 form of the DMA kernel is compiled for it)
 constexpr int64_t SCREEN_SEED_ITEMS = 8192;     // fp16 prefix ranked first (as the exact headline route seeds its lists)
 int64_t screen_prefix(int64_t n_items) { return n_items >= 8 * SCREEN_SEED_ITEMS ? SCREEN_SEED_ITEMS : 0; }
 // item-range cuts of the stage-1 DMA launch (as plan_splits for a DMA route of 128-user waves, four to a workgroup)

@@ -387,6 +387,9 @@ constexpr int WG_RING = 3;   // item-tile slots in LDS (workgroup kernels)
 
 // score_topk_dma.hip (built with -mllvm -amdgpu-mfma-vgpr-form): the LDS-DMA workgroup kernel for 512- and 256-byte rows
 // (mode = CRH_SCORE_DMA: 1 default, 3 = barrier form for fp32 too)
+// K' of the screened route: k <= 28 lists fit beside the DMA kernel's four slots of 256-byte rows.  The 16x16 form of the DMA kernel
+// (both launches of the screen's pass, and nothing else) is compiled for this list length: launch_score_dma refuses another k there.
+constexpr int SCREEN_KP = 28;
 __attribute__((visibility("hidden"))) int launch_score_dma(int esz, int d, int mode, const ScoreArgs& a, hipStream_t stream);
 __attribute__((visibility("hidden"))) size_t score_dma_lds_bytes(int row_bytes, int k, int ring_slots, bool flags, bool compact = false);
 __attribute__((visibility("hidden"))) int score_dma_ring_slots(int esz, int d, int k, int mode);

@@ -173,6 +173,39 @@ constexpr bool DMA_M16_HOOKED = false;
 #else
 constexpr bool DMA_M16_HOOKED = true;
 #endif
+// What the 16x16 event executes was shortened once more in round 17; the protocol, the inserts and their order are the same.  Each
+// step has a switch that builds the form before it (variant build, tools/ab_lib.sh):
+//   -DCRH_DMA_EVENT_RUNTIME_K    K' read from the launch's arguments.  Without it the 16x16 kernels are compiled for K' = SCREEN_KP (only
+//                                the screen launches them): list addresses, the tail entry's lane and the fill tests are immediates
+//   -DCRH_DMA_EVENT_SLOT_TEST    the per-lane test `slot >= n_users`.  It never fires: a padding column's threshold is +inf from the start
+//                                and a dead wave's are all +inf (where `tau` is set up in the kernel), and an insert moves its own user's only
+//   -DCRH_DMA_EVENT_TAIL64       the per-candidate 64-bit test `item0 + row >= split_end`; without it the rows left in the selected tile
+//                                are one scalar per event
+//   -DCRH_DMA_EVENT_MASK8_SPLIT  gt_mask8 as eight asm statements
+// (Measured and not kept, round 17: the candidate's list reads -- fill, entry `lane` of scores and of ids -- issued by asm statements at
+// the head of its iteration, in flight under the score's select tree, the id and the hash, with the filter word behind them and one
+// wait in front of the first use.  Nothing at the headline, 202.77 against 202.67 ms per step, and +1.4 ms without a bitmap, 249.34
+// against 247.91: HISTORY.md, profiles/r17_event_steps_ab.log.)
+#ifdef CRH_DMA_EVENT_RUNTIME_K
+constexpr int DMA_EVENT_KC = 0;
+#else
+constexpr int DMA_EVENT_KC = SCREEN_KP;
+#endif
+#ifdef CRH_DMA_EVENT_SLOT_TEST
+constexpr bool DMA_EVENT_SLOT_TEST = true;
+#else
+constexpr bool DMA_EVENT_SLOT_TEST = false;
+#endif
+#ifdef CRH_DMA_EVENT_TAIL64
+constexpr bool DMA_EVENT_TAIL64 = true;
+#else
+constexpr bool DMA_EVENT_TAIL64 = false;
+#endif
+#ifdef CRH_DMA_EVENT_MASK8_SPLIT
+[[maybe_unused]] constexpr bool DMA_EVENT_MASK8_SPLIT = true;
+#else
+[[maybe_unused]] constexpr bool DMA_EVENT_MASK8_SPLIT = false;
+#endif
 // CM (compacted stream): row q of the stream is the q-th unmasked item; idv = the ids of this tile's rows (lane l: row l & 31),
 // read from LDS once per event by the caller.  item0 and split_end stay row numbers; there are no masked rows (tb = 0).
 template <bool ONE_TRIP, bool CM>
@@ -235,9 +268,19 @@ __device__ __forceinline__ float acc_max(const f32x16& v) { return max16(v); }
 __device__ __forceinline__ unsigned gt_mask8(const f32x8& v, float t) {   // as gt_mask16
     unsigned m = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (DMA_EVENT_MASK8_SPLIT) {
 #pragma unroll
-    for (int r = 7; r >= 0; --r)
-        asm("v_cmp_gt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m) : "v"(v[r]), "v"(t) : "vcc");
+        for (int r = 7; r >= 0; --r)
+            asm("v_cmp_gt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m) : "v"(v[r]), "v"(t) : "vcc");
+    } else {
+        // one statement (round 17): behind each of eight separate ones hipcc puts an s_nop, 24 instructions where these 16 do
+#define CRH_GT8(R) "v_cmp_gt_f32 vcc, %" #R ", %9\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+        asm(CRH_GT8(8) CRH_GT8(7) CRH_GT8(6) CRH_GT8(5) CRH_GT8(4) CRH_GT8(3) CRH_GT8(2) "v_cmp_gt_f32 vcc, %1, %9\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc"
+            : "+v"(m)
+            : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(t)
+            : "vcc");
+#undef CRH_GT8
+    }
 #endif
     return m;
 }
@@ -250,10 +293,13 @@ __device__ __forceinline__ float pick8u(const f32x8& v, int r) {
     const float q0 = b1 ? p1 : p0, q1 = b1 ? p3 : p2;
     return b2 ? q1 : q0;
 }
-template <bool CM>
-__device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& tau_reg, float* ls, int* li, int* cnt, int K, int ucol0,
-                                                     int64_t slot0, const ScoreArgs& a, int64_t item0, int64_t split_end, int lane,
-                                                     unsigned tb, const unsigned* rfilter, int idv) {
+// KC = the compile-time K' (0: K is the launch's); rows_left = the rows of the selected tile inside the cut, 1 .. 32, and gi0 = the id
+// of its row 0 (stream in id order), both worked out once per event by the caller.
+template <bool CM, int KC>
+__device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& tau_reg, float* ls, int* li, int* cnt, int Krt, int ucol0,
+                                                     int64_t slot0, const ScoreArgs& a, int64_t item0, int64_t split_end, int rows_left,
+                                                     int gi0, int lane, unsigned tb, const unsigned* rfilter, int idv) {
+    const int K = KC ? KC : Krt;
     unsigned cm = gt_mask8(acc, tau_reg);
     unsigned m8 = 0u;                                             // masked rows of this lane, as in the 32x32 form
     if (tb != 0u && __ballot(tau_reg < 0.0f) != 0ull) {           // wave-uniform
@@ -270,18 +316,26 @@ __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& ta
         const unsigned bmL = __builtin_amdgcn_readlane(bm, L);
         const int jl = L & 15, g = L >> 4;
         const int64_t slot = slot0 + jl;
-        if (slot >= a.n_users) continue;
+        if constexpr (DMA_EVENT_SLOT_TEST) {
+            if (slot >= a.n_users) continue;
+        }
         const int ul = ucol0 + jl;
         while (cmL) {
             const int r = __builtin_ctz(cmL);
             cmL &= cmL - 1;
             const int row = 16 * (r >> 2) + 4 * g + (r & 3);
             const int64_t il = item0 + row;
-            if (il >= split_end) continue;   // clamped duplicate rows of the tail tile
+            // clamped duplicate rows of the tail tile
+            if constexpr (DMA_EVENT_TAIL64) {
+                if (il >= split_end) continue;
+            } else {
+                if (row >= rows_left) continue;
+            }
             const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pick8u(acc, r)), L));
             int gi;
             if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, row);
-            else gi = (int)(a.item_base + il);
+            else if constexpr (DMA_EVENT_TAIL64) gi = (int)(a.item_base + il);
+            else gi = gi0 + row;
             dma_candidate<DMA_SCREEN_ONE_TRIP, true>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg);
         }
     }
@@ -386,7 +440,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     const int64_t ug_raw = (int64_t)(blockIdx.x / S) * NW + wave;
     const bool live = ug_raw < a.n_ugroups;            // a dead wave still fetches and synchronises
     const int64_t ug = live ? ug_raw : a.n_ugroups - 1;
-    const int K = a.k;
+    constexpr int KC = M16 ? DMA_EVENT_KC : 0;          // the 16x16 form is compiled for the screen's K' (launch_score_dma checks a.k)
+    const int K = KC ? KC : a.k;
     const int i = lane & (M16 ? 15 : 31), h = lane >> (M16 ? 4 : 5);   // user column in its block, k-group (M16: c and g of the 16x16x32 layout)
 
     char* ring = smem;                                  // [R][TILE_B]
@@ -475,7 +530,9 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
         int64_t slot = slot0w + UB * u + i;
-        tau[u] = slot < a.n_users ? CRH_NEG_INF : __builtin_inff();      // padding columns never take a candidate
+        // padding columns never take a candidate.  The 16x16 event RELIES on this +inf (and on the dead wave's below): it no longer tests
+        // `slot < n_users` per hit lane, so nothing but these thresholds keeps a padding column out of a hit mask
+        tau[u] = slot < a.n_users ? CRH_NEG_INF : __builtin_inff();
         if (a.seed_score && slot < a.n_users) tau[u] = wave_list_tau(ls + (UB * u + i) * K, cnt[UB * u + i], K);
         if (slot >= a.n_users) slot = a.n_users - 1;
         const int64_t row = a.users ? (int64_t)a.users[slot] : a.user_base + slot;
@@ -487,7 +544,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         }
     }
     // the hooked 16x16 body tests no `live` per tile: a dead wave walks, synchronises and fetches like any other, and with +inf for
-    // every threshold none of its maxima is a hit (it has no list to insert into and stores nothing)
+    // every threshold none of its maxima is a hit (it has no list to insert into and stores nothing).  The event relies on it as well:
+    // it has no test of its own that would keep a dead wave's lanes out
     if constexpr (M16 && DMA_M16_HOOKED) {
         if (!live) {
 #pragma unroll
@@ -816,13 +874,18 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     const unsigned tb = has_bits ? tbits[((ts >> 6) & 1) * 64 + (ts & 63)] : 0u;
                     int idv = 0;                     // CM: the selected tile's ids, one LDS read per event (where tb's was)
                     if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
+                    // M16: the rows of the selected tile inside the cut (the clamped last tile of a cut holds fewer than 32) and the id of
+                    // its first row, once per event
+                    const int64_t rl64 = split_end - (ts << 5);
+                    const int rows_left = rl64 < 32 ? (int)rl64 : 32;
+                    const int gi0 = (int)(a.item_base + (ts << 5));
 #pragma unroll
                     for (int u = 0; u < NU; ++u)
                         // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
                         if ((M16 && !DMA_EVENT_REBALLOT) ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull) {
                             if constexpr (M16)
-                                tile_slow_path_dma16<CM>(acc[Q][u], tau[u], ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, lane, tb,
-                                                         rfilter, idv);
+                                tile_slow_path_dma16<CM, KC>(acc[Q][u], tau[u], ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end,
+                                                             rows_left, gi0, lane, tb, rfilter, idv);
                             else
                                 tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32, CM>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a,
                                                                                             ts << 5, split_end, lane, tb, rfilter, idv);
@@ -977,13 +1040,18 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     const unsigned tb = has_bits ? tbits[((ts >> 6) & 1) * 64 + (ts & 63)] : 0u;
                     int idv = 0;                     // CM: the selected tile's ids, one LDS read per event (where tb's was)
                     if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
+                    // the rows of the selected tile inside the cut (the clamped last tile of a cut holds fewer than 32) and the id of its
+                    // first row, once per event
+                    const int64_t rl64 = split_end - (ts << 5);
+                    const int rows_left = rl64 < 32 ? (int)rl64 : 32;
+                    const int gi0 = (int)(a.item_base + (ts << 5));
 #pragma unroll
                     for (int u = 0; u < NU; ++u)
                         // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
                         if (!DMA_EVENT_REBALLOT ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull)
                             if constexpr (M16)       // (the other forms never call this body, but they parse it)
-                                tile_slow_path_dma16<CM>(acc[Q][u], tau[u], ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, lane, tb,
-                                                     rfilter, idv);
+                                tile_slow_path_dma16<CM, KC>(acc[Q][u], tau[u], ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end,
+                                                             rows_left, gi0, lane, tb, rfilter, idv);
                     // the list stores of the inserts are drained HERE (as in `body`); the fragment reads in flight land with them
                     __builtin_amdgcn_s_waitcnt(0xc07f);
 #ifdef CRH_PROFILE
@@ -1142,6 +1210,8 @@ int score_dma_ring_slots(int esz, int d, int k, int mode) {
 // width, main.py:97 --emb_size 64 = configs[0]; fp16 d=128: the screen of the screened route, score_screen.hip): half the tile,
 // half the B registers, the same loop.  mode: 2 = the flag form (fp32 d=128 only), anything else the barrier form.
 int launch_score_dma(int esz, int d, int mode, const ScoreArgs& a, hipStream_t stream) {
+    // both fp16 d=128 launches are the screen's: their 16x16 form is compiled for its K' and takes no other list length
+    if (esz == 2 && d == 128 && DMA_SCREEN_M16 && DMA_EVENT_KC != 0 && a.k != DMA_EVENT_KC) return CRH_ERR_ARG;
     if (esz == 2 && d == 128 && a.idmap != nullptr) {     // the compacted stream of the screened route
         if (score_dma_lds_bytes(d * esz, a.k, 4, false, true) > 160 * 1024) return CRH_ERR_ARG;
         return launch_score_dma_t<_Float16, 128, 4, false, true, DMA_SCREEN_M16>(a, stream);
