@@ -23,26 +23,12 @@
 //   neg add       d gn += G, every row (skipped without d gn).
 #include <math.h>
 
-#include "crh_common.h"
+#include "loss_common.h"
 
 namespace {
 
 constexpr int ALDI_CHUNK = 16;          // records per workgroup: 4 waves x ALDI_PER_WAVE
 constexpr int ALDI_PER_WAVE = 4;
-
-__device__ __forceinline__ float aldi_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ f32x4 aldi_load4(const float* p, bool ok) {
-    return ok ? *reinterpret_cast<const f32x4*>(p) : f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-__device__ __forceinline__ float aldi_dot4(const f32x4& a, const f32x4& b) {
-    return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]);
-}
 
 // sigmoid(x), 1 - sigmoid(x) (formed without the subtraction) and log1p(exp(-|x|))
 __device__ __forceinline__ void aldi_sigmoid(float x, float* s, float* one_minus, float* softplus_tail) {
@@ -96,8 +82,8 @@ __global__ __launch_bounds__(256) void aldi_mean_part_kernel(const float* __rest
         const int64_t b = b0 + j;
         if (b >= batch) break;
         const int64_t n = neg[b];
-        sg += aldi_load4(gn + b * d + col, ok);
-        sv += aldi_load4(vt + n * d + col, ok && n >= 0 && n < item_rows);
+        sg += lg_load4(gn + b * d + col, ok);
+        sv += lg_load4(vt + n * d + col, ok && n >= 0 && n < item_rows);
     }
     sg = aldi_block_sum(sg, red, wave, lane);
     sv = aldi_block_sum(sv, red, wave, lane);
@@ -132,7 +118,7 @@ __global__ __launch_bounds__(256) void aldi_record_kernel(
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = 4 * lane;
     const bool ok = col < d;
     const int64_t b0 = (int64_t)blockIdx.x * ALDI_CHUNK + wave * ALDI_PER_WAVE;
-    const f32x4 mg = aldi_load4(mean + col, ok), mv = aldi_load4(mean + d + col, ok);
+    const f32x4 mg = lg_load4(mean + col, ok), mv = lg_load4(mean + d + col, ok);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, terms = acc;
 #pragma unroll 1
     for (int j = 0; j < ALDI_PER_WAVE; ++j) {
@@ -142,14 +128,14 @@ __global__ __launch_bounds__(256) void aldi_record_kernel(
         // (uniform: a record whose ids leave the tables contributes nothing instead of reading wild)
         const bool in = u >= 0 && u < user_rows && p >= 0 && p < item_rows && n >= 0 && n < item_rows;
         const bool on = ok && in;
-        const f32x4 ur = aldi_load4(ut + u * d + col, on), pr = aldi_load4(vt + p * d + col, on);
-        const f32x4 nr = aldi_load4(vt + n * d + col, on);
-        const f32x4 xu = aldi_load4(gu + o, on), xp = aldi_load4(gp + o, on), xn = aldi_load4(gn + o, on);
+        const f32x4 ur = lg_load4(ut + u * d + col, on), pr = lg_load4(vt + p * d + col, on);
+        const f32x4 nr = lg_load4(vt + n * d + col, on);
+        const f32x4 xu = lg_load4(gu + o, on), xp = lg_load4(gp + o, on), xn = lg_load4(gn + o, on);
         const float wi = in ? w[p] : 0.f;
-        const float sp = aldi_wave_sum(aldi_dot4(xu, xp)), sn = aldi_wave_sum(aldi_dot4(xu, xn));
-        const float tp = aldi_wave_sum(aldi_dot4(ur, pr)), tn = aldi_wave_sum(aldi_dot4(ur, nr));
-        const float pp = aldi_wave_sum(aldi_dot4(xp, xp)), pm = aldi_wave_sum(aldi_dot4(xp, mg));
-        const float tpp = aldi_wave_sum(aldi_dot4(pr, pr)), tpm = aldi_wave_sum(aldi_dot4(pr, mv));
+        const float sp = lg_wave_sum(lg_dot4(xu, xp)), sn = lg_wave_sum(lg_dot4(xu, xn));
+        const float tp = lg_wave_sum(lg_dot4(ur, pr)), tn = lg_wave_sum(lg_dot4(ur, nr));
+        const float pp = lg_wave_sum(lg_dot4(xp, xp)), pm = lg_wave_sum(lg_dot4(xp, mg));
+        const float tpp = lg_wave_sum(lg_dot4(pr, pr)), tpm = lg_wave_sum(lg_dot4(pr, mv));
 
         const float x = sp - sn;
         float s, oms, tail;
@@ -220,24 +206,18 @@ struct AldiWs {
 int64_t aldi_chunks(int64_t batch) { return (batch + ALDI_CHUNK - 1) / ALDI_CHUNK; }
 
 bool aldi_shape_ok(int64_t batch, int d) {
-    return batch >= 1 && batch < ((int64_t)1 << 31) && d >= 4 && d <= 256 && d % 4 == 0;
+    return batch >= 1 && batch < ((int64_t)1 << 31) && lg_width_ok(d);
 }
 
 AldiWs aldi_layout(void* base, int64_t batch, int d) {
     const int64_t n = aldi_chunks(batch);
     AldiWs w;
-    char* p = reinterpret_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](int64_t floats) {
-        float* r = reinterpret_cast<float*>(p + off);
-        off += (size_t)((floats * 4 + 255) & ~(int64_t)255);
-        return r;
-    };
-    w.mean_part = take(n * 2 * d);
-    w.mean = take(2 * d);
-    w.part = take(n * (d + 4));
-    w.gvec = take(d);
-    w.bytes = off;
+    WsCarver c(base);
+    w.mean_part = c.take(n * 2 * d);
+    w.mean = c.take(2 * d);
+    w.part = c.take(n * (d + 4));
+    w.gvec = c.take(d);
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -258,27 +238,16 @@ extern "C" int crh_aldi_f32(const float* user_table, int64_t user_rows, const fl
     CRH_CHECK_ARG(users && pos && neg, "crh_aldi_f32: NULL id pointer");
     CRH_CHECK_ARG(gen_user && gen_pos && gen_neg, "crh_aldi_f32: NULL tower output pointer");
     CRH_CHECK_ARG(grad_user || grad_pos || grad_neg || loss_out, "crh_aldi_f32: NULL gradients and loss: nothing to compute");
-    CRH_CHECK_ARG(d >= 4 && d <= 256 && d % 4 == 0, "crh_aldi_f32: d = %d must be a multiple of 4 in [4, 256]", d);
+    LG_CHECK_WIDTH("crh_aldi_f32", d);
     CRH_CHECK_ARG(batch >= 1 && batch < ((int64_t)1 << 31), "crh_aldi_f32: batch = %lld must lie in [1, 2^31)",
                   (long long)batch);
-    CRH_CHECK_ARG(user_min >= 0 && user_min <= user_max && user_max < user_rows,
-                  "crh_aldi_f32: user ids [%d, %d] outside the user table of %lld rows", user_min, user_max,
-                  (long long)user_rows);
-    CRH_CHECK_ARG(item_min >= 0 && item_min <= item_max && item_max < item_rows,
-                  "crh_aldi_f32: item ids [%d, %d] outside the item table of %lld rows", item_min, item_max,
-                  (long long)item_rows);
+    LG_CHECK_IDS("crh_aldi_f32", "user", user_min, user_max, user_rows);
+    LG_CHECK_IDS("crh_aldi_f32", "item", item_min, item_max, item_rows);
     CRH_CHECK_ARG(isfinite(alpha) && isfinite(beta) && isfinite(gamma) && isfinite(scale),
                   "crh_aldi_f32: alpha, beta, gamma and scale must be finite");
-    CRH_CHECK_ARG(((reinterpret_cast<uintptr_t>(user_table) | reinterpret_cast<uintptr_t>(item_table) |
-                    reinterpret_cast<uintptr_t>(gen_user) | reinterpret_cast<uintptr_t>(gen_pos) |
-                    reinterpret_cast<uintptr_t>(gen_neg) | reinterpret_cast<uintptr_t>(grad_user) |
-                    reinterpret_cast<uintptr_t>(grad_pos) | reinterpret_cast<uintptr_t>(grad_neg)) & 15) == 0,
+    CRH_CHECK_ARG(lg_aligned16(user_table, item_table, gen_user, gen_pos, gen_neg, grad_user, grad_pos, grad_neg),
                   "crh_aldi_f32: tables, tower outputs and gradients must be 16-byte aligned");
-    const size_t need = crh_aldi_workspace_bytes(batch, d);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        crh_set_error("crh_aldi_f32: workspace %zu < %zu bytes (or not 256-byte aligned)", workspace_bytes, need);
-        return CRH_ERR_WS;
-    }
+    LG_CHECK_WS("crh_aldi_f32", workspace, workspace_bytes, crh_aldi_workspace_bytes(batch, d));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const AldiWs w = aldi_layout(workspace, batch, d);
     const int64_t n_chunks = aldi_chunks(batch);

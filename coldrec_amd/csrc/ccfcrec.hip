@@ -23,58 +23,12 @@
 //   loss     one workgroup adds the B records' terms in a fixed order.
 #include <math.h>
 
-#include "crh_common.h"
+#include "loss_common.h"
 
 namespace {
 
 constexpr int CCF_MAX_ROWS = 4096;  // R: three LDS arrays of R floats per record (dynamic LDS, 48 KiB at the limit)
 constexpr int CCF_CHUNK = 256;      // occurrences of one owner summed by one wave
-
-__device__ __forceinline__ float ccf_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ float ccf_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-
-// sum over the LPR lanes of a row's group / over the 64 / LPR groups (same column of every group)
-template <int LPR>
-__device__ __forceinline__ float ccf_group_sum(float v) {
-#pragma unroll
-    for (int off = LPR / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-template <int LPR>
-__device__ __forceinline__ float ccf_cross_sum1(float v) {
-#pragma unroll
-    for (int off = 32; off >= LPR; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-template <int LPR>
-__device__ __forceinline__ f32x4 ccf_cross_sum(f32x4 v) {
-#pragma unroll
-    for (int off = 32; off >= LPR; off >>= 1) {
-        const float x = __shfl_xor(v[0], off), y = __shfl_xor(v[1], off);
-        const float z = __shfl_xor(v[2], off), w = __shfl_xor(v[3], off);
-        v += f32x4{x, y, z, w};
-    }
-    return v;
-}
-
-__device__ __forceinline__ f32x4 ccf_load4(const float* p, bool ok) {
-    return ok ? *reinterpret_cast<const f32x4*>(p) : f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-__device__ __forceinline__ float ccf_dot4(const f32x4& a, const f32x4& b) {
-    return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]);
-}
 
 // softplus(-z) and its derivative by z, -sigmoid(-z), from e = exp(-|z|)
 __device__ __forceinline__ float ccf_softplus_neg(float z, float* dz) {
@@ -98,12 +52,12 @@ __global__ __launch_bounds__(64) void ccf_record_kernel(const float* __restrict_
     extern __shared__ float ccf_lds[];                 // 3 R floats: score -> coefficient, cosine, 1 / |v|
     float *sc = ccf_lds, *cs = ccf_lds + rows, *inv = ccf_lds + 2 * rows;
     const int64_t b = blockIdx.x;
-    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR, col = 4 * cl;
+    const auto [lane, cl, grp, col] = lg_coords<LPR>();
     const bool ok = col < d;
     const int64_t row0 = b * rows;
 
-    const f32x4 qv = ccf_load4(q + b * d + col, ok);
-    const float inv_nq = 1.f / sqrtf(ccf_group_sum<LPR>(ccf_dot4(qv, qv)));
+    const f32x4 qv = lg_load4(q + b * d + col, ok);
+    const float inv_nq = 1.f / sqrtf(lg_group_sum<LPR>(lg_dot4(qv, qv)));
     const f32x4 qh = qv * inv_nq;
 
     // pass A: cosines and inverse norms of the R rows
@@ -112,8 +66,8 @@ __global__ __launch_bounds__(64) void ccf_record_kernel(const float* __restrict_
         const bool on = r < rows && ok;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (on) v = *reinterpret_cast<const f32x4*>(vt + (int64_t)items[row0 + r] * d + col);
-        const float ss = ccf_group_sum<LPR>(ccf_dot4(v, v));
-        const float qd = ccf_group_sum<LPR>(ccf_dot4(qh, v));
+        const float ss = lg_group_sum<LPR>(lg_dot4(v, v));
+        const float qd = lg_group_sum<LPR>(lg_dot4(qh, v));
         if (cl == 0 && r < rows) {
             const float iv = 1.f / sqrtf(ss), c = qd * iv;
             inv[r] = iv;
@@ -132,10 +86,10 @@ __global__ __launch_bounds__(64) void ccf_record_kernel(const float* __restrict_
         const float cp = sc[pr];
         float m = cp;
         for (int j = lane; j < cnt; j += 64) m = fmaxf(m, sc[nb + j]);
-        m = ccf_wave_max(m);
+        m = lg_wave_max(m);
         float l_off = 0.f;
         for (int j = lane; j < cnt; j += 64) l_off += expf(sc[nb + j] - m);
-        l_off = ccf_wave_sum(l_off);
+        l_off = lg_wave_sum(l_off);
         const float e0 = expf(cp - m), l = l_off + e0, inv_l = 1.f / l;
         // lse - c_pos = log(l / e0): log1p while e0 is representable, else from the max
         const float term = e0 > 1e-30f ? log1pf(l_off / e0) : (m - cp) + logf(l);
@@ -153,7 +107,7 @@ __global__ __launch_bounds__(64) void ccf_record_kernel(const float* __restrict_
         x2o[row0 + r] = ac * inv_t;
         sac += ac;
     }
-    sac = ccf_wave_sum(sac);
+    sac = lg_wave_sum(sac);
 
     // pass B: sum_r a_r v_r / |v_r|
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -164,14 +118,14 @@ __global__ __launch_bounds__(64) void ccf_record_kernel(const float* __restrict_
             acc += v * (sc[r] * inv[r]);
         }
     }
-    if constexpr (LPR < 64) acc = ccf_cross_sum<LPR>(acc);
+    if constexpr (LPR < 64) acc = lg_cross_sum<LPR>(acc);
 
     // the rank losses
-    const f32x4 uu = ccf_load4(ut + (int64_t)users[b] * d + col, ok);
-    const f32x4 uk = ccf_load4(ut + (int64_t)neg_users[b] * d + col, ok);
-    const f32x4 vi = ccf_load4(vt + (int64_t)items[row0] * d + col, ok);
-    const float z1 = ccf_group_sum<LPR>(ccf_dot4(vi, uu)) - ccf_group_sum<LPR>(ccf_dot4(vi, uk));
-    const float z2 = ccf_group_sum<LPR>(ccf_dot4(qv, uu)) - ccf_group_sum<LPR>(ccf_dot4(qv, uk));
+    const f32x4 uu = lg_load4(ut + (int64_t)users[b] * d + col, ok);
+    const f32x4 uk = lg_load4(ut + (int64_t)neg_users[b] * d + col, ok);
+    const f32x4 vi = lg_load4(vt + (int64_t)items[row0] * d + col, ok);
+    const float z1 = lg_group_sum<LPR>(lg_dot4(vi, uu)) - lg_group_sum<LPR>(lg_dot4(vi, uk));
+    const float z2 = lg_group_sum<LPR>(lg_dot4(qv, uu)) - lg_group_sum<LPR>(lg_dot4(qv, uk));
     float d1, d2;
     const float r1 = ccf_softplus_neg(z1, &d1), r2 = ccf_softplus_neg(z2, &d2);
     d1 *= w_r;
@@ -204,7 +158,7 @@ __global__ __launch_bounds__(64) void ccf_item_chunk_kernel(const int32_t* __res
                                                             const float* __restrict__ gi, float* __restrict__ part) {
     constexpr int RG = 64 / LPR;
     const int64_t ch = blockIdx.x;
-    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR, col = 4 * cl;
+    const auto [lane, cl, grp, col] = lg_coords<LPR>();
     const bool ok = col < d;
     const int s = chunk_own[ch];
     f32x4 acc_q = {0.f, 0.f, 0.f, 0.f}, acc_r = acc_q;
@@ -229,9 +183,9 @@ __global__ __launch_bounds__(64) void ccf_item_chunk_kernel(const int32_t* __res
         }
     }
     if constexpr (LPR < 64) {
-        acc_q = ccf_cross_sum<LPR>(acc_q);
-        acc_r = ccf_cross_sum<LPR>(acc_r);
-        acc_x = ccf_cross_sum1<LPR>(acc_x);
+        acc_q = lg_cross_sum<LPR>(acc_q);
+        acc_r = lg_cross_sum<LPR>(acc_r);
+        acc_x = lg_cross_sum1<LPR>(acc_x);
     }
     if (grp == 0 && ok) {
         float* p = part + ch * (2 * d + 4);
@@ -249,7 +203,7 @@ __global__ __launch_bounds__(64) void ccf_item_finish_kernel(const float* __rest
                                                              const float* __restrict__ part,
                                                              float* __restrict__ grad_item) {
     constexpr int RG = 64 / LPR;
-    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR, col = 4 * cl;
+    const auto [lane, cl, grp, col] = lg_coords<LPR>();
     const int64_t s = (int64_t)blockIdx.x * RG + grp;
     const bool ok = col < d && s < n_own;
     f32x4 pq = {0.f, 0.f, 0.f, 0.f}, pr = pq, v = pq;
@@ -265,7 +219,7 @@ __global__ __launch_bounds__(64) void ccf_item_finish_kernel(const float* __rest
         item = own_ids[s];
         v = *reinterpret_cast<const f32x4*>(vt + item * d + col);
     }
-    const float ss = ccf_group_sum<LPR>(ccf_dot4(v, v));
+    const float ss = lg_group_sum<LPR>(lg_dot4(v, v));
     if (!ok) return;
     *reinterpret_cast<f32x4*>(grad_item + item * d + col) = (pq * (1.f / sqrtf(ss)) - v * (px / ss)) + pr;
 }
@@ -280,7 +234,7 @@ __global__ __launch_bounds__(64) void ccf_user_chunk_kernel(const int32_t* __res
                                                             float* __restrict__ part) {
     constexpr int RG = 64 / LPR;
     const int64_t ch = blockIdx.x;
-    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR, col = 4 * cl;
+    const auto [lane, cl, grp, col] = lg_coords<LPR>();
     const bool ok = col < d;
     const int s = chunk_own[ch];
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -300,7 +254,7 @@ __global__ __launch_bounds__(64) void ccf_user_chunk_kernel(const int32_t* __res
             }
         }
     }
-    if constexpr (LPR < 64) acc = ccf_cross_sum<LPR>(acc);
+    if constexpr (LPR < 64) acc = lg_cross_sum<LPR>(acc);
     if (grp == 0 && ok) *reinterpret_cast<f32x4*>(part + ch * d + col) = acc;
 }
 
@@ -310,7 +264,7 @@ __global__ __launch_bounds__(64) void ccf_user_finish_kernel(const int32_t* __re
                                                              const float* __restrict__ part,
                                                              float* __restrict__ grad_user) {
     constexpr int RG = 64 / LPR;
-    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR, col = 4 * cl;
+    const auto [lane, cl, grp, col] = lg_coords<LPR>();
     const int64_t s = (int64_t)blockIdx.x * RG + grp;
     if (col >= d || s >= n_own) return;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -322,16 +276,7 @@ __global__ __launch_bounds__(64) void ccf_user_finish_kernel(const int32_t* __re
 __global__ __launch_bounds__(256) void ccf_loss_kernel(const float* __restrict__ rec, int64_t batch, int n_pos, float lam,
                                                        float* __restrict__ loss) {
     __shared__ float red[4][4];
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t b = threadIdx.x; b < batch; b += 256)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[k] += rec[b * 4 + k];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        s[k] = ccf_wave_sum(s[k]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s[k];
-    }
-    __syncthreads();
+    lg_record_sums(rec, batch, red);
     if (threadIdx.x == 0) {
         float t[4];
 #pragma unroll
@@ -355,7 +300,7 @@ int64_t ccf_rows(int n_pos, int n_neg, int n_self) { return 1 + (int64_t)n_pos +
 int64_t ccf_max_chunks(int64_t occurrences, int64_t n_own) { return n_own + occurrences / CCF_CHUNK; }
 
 bool ccf_shape_ok(int64_t batch, int n_pos, int n_neg, int n_self, int d, int64_t n_items, int64_t n_users) {
-    if (batch < 1 || n_pos < 1 || n_neg < 1 || n_self < 1 || d < 4 || d > 256 || d % 4 != 0) return false;
+    if (batch < 1 || n_pos < 1 || n_neg < 1 || n_self < 1 || !lg_width_ok(d)) return false;
     const int64_t rows = ccf_rows(n_pos, n_neg, n_self);
     return rows <= CCF_MAX_ROWS && batch * rows < ((int64_t)1 << 31) && n_items >= 1 && n_items <= batch * rows &&
            n_users >= 1 && n_users <= 2 * batch;
@@ -364,22 +309,16 @@ bool ccf_shape_ok(int64_t batch, int n_pos, int n_neg, int n_self, int d, int64_
 CcfWs ccf_layout(void* base, int64_t batch, int64_t rows, int d, int64_t n_items, int64_t n_users) {
     const int64_t m = batch * rows;
     CcfWs w;
-    char* p = reinterpret_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](int64_t floats) {
-        float* r = reinterpret_cast<float*>(p + off);
-        off += (size_t)((floats * 4 + 255) & ~(int64_t)255);
-        return r;
-    };
-    w.x1 = take(m);
-    w.x2 = take(m);
-    w.qh = take(batch * d);
-    w.gi = take(batch * d);
-    w.gu = take(batch * d);
-    w.rec = take(batch * 4);
-    w.part_i = take(ccf_max_chunks(m, n_items) * (2 * d + 4));
-    w.part_u = take(ccf_max_chunks(2 * batch, n_users) * d);
-    w.bytes = off;
+    WsCarver c(base);
+    w.x1 = c.take(m);
+    w.x2 = c.take(m);
+    w.qh = c.take(batch * d);
+    w.gi = c.take(batch * d);
+    w.gu = c.take(batch * d);
+    w.rec = c.take(batch * 4);
+    w.part_i = c.take(ccf_max_chunks(m, n_items) * (2 * d + 4));
+    w.part_u = c.take(ccf_max_chunks(2 * batch, n_users) * d);
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -443,7 +382,7 @@ extern "C" int crh_ccfcrec_f32(const float* user_table, int64_t user_rows, const
                       user_chunk_ptr && user_chunk_own,
                   "crh_ccfcrec_f32: NULL inverse-index pointer");
     CRH_CHECK_ARG(grad_user || grad_item || grad_q || loss_out, "crh_ccfcrec_f32: NULL gradients and loss: nothing to compute");
-    CRH_CHECK_ARG(d >= 4 && d <= 256 && d % 4 == 0, "crh_ccfcrec_f32: d = %d must be a multiple of 4 in [4, 256]", d);
+    LG_CHECK_WIDTH("crh_ccfcrec_f32", d);
     CRH_CHECK_ARG(n_pos >= 1 && n_neg >= 1 && n_self >= 1, "crh_ccfcrec_f32: n_pos = %d, n_neg = %d, n_self = %d must be >= 1",
                   n_pos, n_neg, n_self);
     const int64_t rows = ccf_rows(n_pos, n_neg, n_self);
@@ -461,23 +400,14 @@ extern "C" int crh_ccfcrec_f32(const float* user_table, int64_t user_rows, const
     CRH_CHECK_ARG(n_user_chunks >= n_users && n_user_chunks <= ccf_max_chunks(2 * batch, n_users),
                   "crh_ccfcrec_f32: n_user_chunks = %lld out of [n_users, n_users + 2 batch / %d]", (long long)n_user_chunks,
                   CCF_CHUNK);
-    CRH_CHECK_ARG(user_min >= 0 && user_min <= user_max && user_max < user_rows,
-                  "crh_ccfcrec_f32: user ids [%d, %d] outside the user table of %lld rows", user_min, user_max,
-                  (long long)user_rows);
-    CRH_CHECK_ARG(item_min >= 0 && item_min <= item_max && item_max < item_rows,
-                  "crh_ccfcrec_f32: item ids [%d, %d] outside the item table of %lld rows", item_min, item_max,
-                  (long long)item_rows);
+    LG_CHECK_IDS("crh_ccfcrec_f32", "user", user_min, user_max, user_rows);
+    LG_CHECK_IDS("crh_ccfcrec_f32", "item", item_min, item_max, item_rows);
     CRH_CHECK_ARG(tau > 0.f && isfinite(tau), "crh_ccfcrec_f32: tau must be finite and > 0");
     CRH_CHECK_ARG(isfinite(lambda1) && isfinite(scale), "crh_ccfcrec_f32: lambda1 and scale must be finite");
-    CRH_CHECK_ARG(((reinterpret_cast<uintptr_t>(user_table) | reinterpret_cast<uintptr_t>(item_table) |
-                    reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(grad_user) |
-                    reinterpret_cast<uintptr_t>(grad_item) | reinterpret_cast<uintptr_t>(grad_q)) & 15) == 0,
+    CRH_CHECK_ARG(lg_aligned16(user_table, item_table, q, grad_user, grad_item, grad_q),
                   "crh_ccfcrec_f32: tables and gradients must be 16-byte aligned");
-    const size_t need = crh_ccfcrec_workspace_bytes(batch, n_pos, n_neg, n_self, d, n_items, n_users);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        crh_set_error("crh_ccfcrec_f32: workspace %zu < %zu bytes (or not 256-byte aligned)", workspace_bytes, need);
-        return CRH_ERR_WS;
-    }
+    LG_CHECK_WS("crh_ccfcrec_f32", workspace, workspace_bytes,
+                crh_ccfcrec_workspace_bytes(batch, n_pos, n_neg, n_self, d, n_items, n_users));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const CcfWs w = ccf_layout(workspace, batch, rows, d, n_items, n_users);
     CcfArgs a;
@@ -492,14 +422,7 @@ extern "C" int crh_ccfcrec_f32(const float* user_table, int64_t user_rows, const
     a.inv_t = 1.f / tau;
     a.w_c = scale * lambda1 / (float)n_pos, a.w_s = scale * lambda1, a.w_r = scale * (1.f - lambda1);
     a.grad_user = grad_user, a.grad_item = grad_item, a.grad_q = grad_q;
-    const int lanes = d / 4;
-    if (lanes <= 1) ccf_launch<1>(w, a, st);
-    else if (lanes <= 2) ccf_launch<2>(w, a, st);
-    else if (lanes <= 4) ccf_launch<4>(w, a, st);
-    else if (lanes <= 8) ccf_launch<8>(w, a, st);
-    else if (lanes <= 16) ccf_launch<16>(w, a, st);
-    else if (lanes <= 32) ccf_launch<32>(w, a, st);
-    else ccf_launch<64>(w, a, st);
+    lg_dispatch_lpr(d, [&](auto lpr) { ccf_launch<decltype(lpr)::value>(w, a, st); });
     if (loss_out) hipLaunchKernelGGL(ccf_loss_kernel, dim3(1), dim3(256), 0, st, w.rec, batch, n_pos, lambda1, loss_out);
     CRH_HIP(hipGetLastError());
     return CRH_OK;

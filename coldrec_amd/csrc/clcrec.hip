@@ -23,7 +23,7 @@
 //   loss     one workgroup adds the B records' terms in a fixed order.
 #include <math.h>
 
-#include "crh_common.h"
+#include "loss_common.h"
 
 namespace {
 
@@ -31,57 +31,16 @@ constexpr int CLC_MAX_NEG = 1024;   // G: three LDS arrays of 1 + G floats per r
 constexpr int CLC_CHUNK = 256;      // occurrences of one slot summed by one wave
 constexpr float CLC_EPS = 1e-12f;   // F.normalize's clamp_min
 
-__device__ __forceinline__ float clc_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ float clc_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-
-// sum over the LPR lanes of a row's group / over the 64 / LPR groups (same column of every group)
-template <int LPR>
-__device__ __forceinline__ float clc_group_sum(float v) {
-#pragma unroll
-    for (int off = LPR / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-template <int LPR>
-__device__ __forceinline__ f32x4 clc_cross_sum(f32x4 v) {
-    if constexpr (LPR < 64) {                          // (one group per wave: nothing to add)
-#pragma unroll
-        for (int off = 32; off >= LPR; off >>= 1) {
-            const float x = __shfl_xor(v[0], off), y = __shfl_xor(v[1], off);
-            const float z = __shfl_xor(v[2], off), w = __shfl_xor(v[3], off);
-            v += f32x4{x, y, z, w};
-        }
-    }
-    return v;
-}
-
-__device__ __forceinline__ f32x4 clc_load4(const float* p, bool ok) {
-    return ok ? *reinterpret_cast<const f32x4*>(p) : f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-__device__ __forceinline__ float clc_dot4(const f32x4& a, const f32x4& b) {
-    return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]);
-}
-
 // softmax statistics of 1 + G scores held in LDS: returns the row's loss term lse - s_0 and turns every score into its
 // coefficient coef * (p_g - [g = 0]) in place
 __device__ __forceinline__ float clc_softmax_coef(float* s, int g1, float coef, int lane) {
     float m = CRH_NEG_INF;
     for (int g = lane; g < g1; g += 64) m = fmaxf(m, s[g]);
-    m = clc_wave_max(m);
+    m = lg_wave_max(m);
     float l_off = 0.f;
     for (int g = lane; g < g1; g += 64)
         if (g > 0) l_off += expf(s[g] - m);
-    l_off = clc_wave_sum(l_off);
+    l_off = lg_wave_sum(l_off);
     const float s0 = s[0];
     const float e0 = expf(s0 - m), l = l_off + e0, inv_l = 1.f / l;
     __syncthreads();                                   // every lane has read s[0]
@@ -105,14 +64,14 @@ __global__ __launch_bounds__(64) void clc_record_kernel(const float* __restrict_
     extern __shared__ float clc_lds[];                 // 3 (1 + G) floats: both softmaxes' scores, the item norms
     float *s1 = clc_lds, *s2 = clc_lds + g1, *nvs = clc_lds + 2 * g1;
     const int64_t b = blockIdx.x;
-    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR, col = 4 * cl;
+    const auto [lane, cl, grp, col] = lg_coords<LPR>();
     const bool ok = col < d;
     const int64_t row0 = b * g1;
 
-    const f32x4 u = clc_load4(ut + (int64_t)users[b] * d + col, ok);
-    const f32x4 vp = clc_load4(vt + (int64_t)items[row0] * d + col, ok);
-    const float nu = sqrtf(clc_group_sum<LPR>(clc_dot4(u, u)));
-    const float np = sqrtf(clc_group_sum<LPR>(clc_dot4(vp, vp)));
+    const f32x4 u = lg_load4(ut + (int64_t)users[b] * d + col, ok);
+    const f32x4 vp = lg_load4(vt + (int64_t)items[row0] * d + col, ok);
+    const float nu = sqrtf(lg_group_sum<LPR>(lg_dot4(u, u)));
+    const float np = sqrtf(lg_group_sum<LPR>(lg_dot4(vp, vp)));
     const float inv_np = 1.f / fmaxf(np, CLC_EPS);
     const f32x4 h = vp * inv_np;
 
@@ -127,10 +86,10 @@ __global__ __launch_bounds__(64) void clc_record_kernel(const float* __restrict_
             v = *reinterpret_cast<const f32x4*>(vt + (int64_t)items[row0 + g] * d + col);
             f = *reinterpret_cast<const f32x4*>(feat + (int64_t)slot[row0 + g] * d + col);
         }
-        const float ssf = clc_group_sum<LPR>(clc_dot4(f, f));
-        const float ssv = clc_group_sum<LPR>(clc_dot4(v, v));
-        const float hf = clc_group_sum<LPR>(clc_dot4(h, f));
-        const float ux = clc_group_sum<LPR>(c > 0 ? clc_dot4(u, f) : clc_dot4(u, v));
+        const float ssf = lg_group_sum<LPR>(lg_dot4(f, f));
+        const float ssv = lg_group_sum<LPR>(lg_dot4(v, v));
+        const float hf = lg_group_sum<LPR>(lg_dot4(h, f));
+        const float ux = lg_group_sum<LPR>(c > 0 ? lg_dot4(u, f) : lg_dot4(u, v));
         if (cl == 0 && g < g1) {
             s1[g] = (hf / fmaxf(sqrtf(ssf), CLC_EPS)) * inv_t;
             s2[g] = ux * inv_t;
@@ -140,7 +99,7 @@ __global__ __launch_bounds__(64) void clc_record_kernel(const float* __restrict_
     __syncthreads();
     float nv = 0.f;
     for (int g = lane; g < g1; g += 64) nv += nvs[g];
-    nv = clc_wave_sum(nv);
+    nv = lg_wave_sum(nv);
     const float l1 = clc_softmax_coef(s1, g1, coef1, lane);
     const float l2 = clc_softmax_coef(s2, g1, coef2, lane);
     __syncthreads();
@@ -169,17 +128,17 @@ __global__ __launch_bounds__(64) void clc_record_kernel(const float* __restrict_
             x = f;
             if (mix[row0 + g] == 0) x = *reinterpret_cast<const f32x4*>(vt + (int64_t)items[row0 + g] * d + col);
         }
-        const float inv_nf = 1.f / fmaxf(sqrtf(clc_group_sum<LPR>(clc_dot4(f, f))), CLC_EPS);
+        const float inv_nf = 1.f / fmaxf(sqrtf(lg_group_sum<LPR>(lg_dot4(f, f))), CLC_EPS);
         acc_h += f * (a1 * inv_nf);
         acc_u += x * a2;
     }
     if constexpr (LPR < 64) {                          // (kept at the call site: hipcc 7.2 crashes on the no-op call)
-        acc_u = clc_cross_sum<LPR>(acc_u);
-        acc_h = clc_cross_sum<LPR>(acc_h);
+        acc_u = lg_cross_sum<LPR>(acc_u);
+        acc_h = lg_cross_sum<LPR>(acc_h);
     }
     if (nu > 0.f) acc_u += u * (reg_u / nu);
     // normalize's backward: (g - h <h, g>) / |v| above the clamp, g / eps below it (torch's clamp_min mask)
-    const float hd = clc_group_sum<LPR>(clc_dot4(h, acc_h));
+    const float hd = lg_group_sum<LPR>(lg_dot4(h, acc_h));
     const f32x4 gp = (np >= CLC_EPS ? acc_h - h * hd : acc_h) * inv_np;
     if (grp == 0 && ok) {
         const int64_t o = b * d + col;
@@ -203,7 +162,7 @@ __global__ __launch_bounds__(64) void clc_slot_kernel(const int32_t* __restrict_
                                                       float* __restrict__ part) {
     constexpr int R = 64 / LPR;
     const int64_t ch = blockIdx.x;
-    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR, col = 4 * cl;
+    const auto [lane, cl, grp, col] = lg_coords<LPR>();
     const bool ok = col < d;
     const int s = chunk_slot[ch];
     f32x4 acc_a = {0.f, 0.f, 0.f, 0.f}, acc_c = acc_a, acc_d = acc_a, acc_p = acc_a;
@@ -230,10 +189,10 @@ __global__ __launch_bounds__(64) void clc_slot_kernel(const int32_t* __restrict_
             }
         }
     }
-    acc_a = clc_cross_sum<LPR>(acc_a);
-    acc_c = clc_cross_sum<LPR>(acc_c);
-    acc_d = clc_cross_sum<LPR>(acc_d);
-    acc_p = clc_cross_sum<LPR>(acc_p);
+    acc_a = lg_cross_sum<LPR>(acc_a);
+    acc_c = lg_cross_sum<LPR>(acc_c);
+    acc_d = lg_cross_sum<LPR>(acc_d);
+    acc_p = lg_cross_sum<LPR>(acc_p);
     if (grp == 0 && ok) {
         float* p = part + ch * 4 * d + col;
         *reinterpret_cast<f32x4*>(p) = acc_a;
@@ -252,7 +211,7 @@ __global__ __launch_bounds__(64) void clc_finish_kernel(const float* __restrict_
                                                         const float* __restrict__ part, float reg_v,
                                                         float* __restrict__ grad_item, float* __restrict__ grad_feat) {
     constexpr int R = 64 / LPR;
-    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR, col = 4 * cl;
+    const auto [lane, cl, grp, col] = lg_coords<LPR>();
     const int64_t s = (int64_t)blockIdx.x * R + grp;
     const bool ok = col < d && s < n_slots;
     f32x4 pa = {0.f, 0.f, 0.f, 0.f}, pc = pa, pd = pa, pp = pa, f = pa, v = pa;
@@ -271,11 +230,11 @@ __global__ __launch_bounds__(64) void clc_finish_kernel(const float* __restrict_
         f = *reinterpret_cast<const f32x4*>(feat + s * d + col);
         v = *reinterpret_cast<const f32x4*>(vt + item * d + col);
     }
-    const float nf = sqrtf(clc_group_sum<LPR>(clc_dot4(f, f)));
-    const float nv = sqrtf(clc_group_sum<LPR>(clc_dot4(v, v)));
+    const float nf = sqrtf(lg_group_sum<LPR>(lg_dot4(f, f)));
+    const float nv = sqrtf(lg_group_sum<LPR>(lg_dot4(v, v)));
     const float inv_nf = 1.f / fmaxf(nf, CLC_EPS);
     const f32x4 z = f * inv_nf;
-    const float zd = clc_group_sum<LPR>(clc_dot4(z, pa));
+    const float zd = lg_group_sum<LPR>(lg_dot4(z, pa));
     if (!ok) return;
     if (grad_feat) *reinterpret_cast<f32x4*>(grad_feat + s * d + col) = (nf >= CLC_EPS ? pa - z * zd : pa) * inv_nf + pc;
     if (grad_item) {
@@ -293,7 +252,7 @@ __global__ __launch_bounds__(64) void clc_user_kernel(const int32_t* __restrict_
                                                       const float* __restrict__ gu, float* __restrict__ grad_user) {
     constexpr int R = 64 / LPR;
     const int64_t j = blockIdx.x;
-    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR, col = 4 * cl;
+    const auto [lane, cl, grp, col] = lg_coords<LPR>();
     const bool ok = col < d;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     const int64_t k_begin = user_ptr[j], k_end = user_ptr[j + 1];
@@ -306,7 +265,7 @@ __global__ __launch_bounds__(64) void clc_user_kernel(const int32_t* __restrict_
             acc += *reinterpret_cast<const f32x4*>(gu + (int64_t)b * d + col);
         }
     }
-    acc = clc_cross_sum<LPR>(acc);
+    acc = lg_cross_sum<LPR>(acc);
     if (grp == 0 && ok) *reinterpret_cast<f32x4*>(grad_user + (int64_t)user_ids[j] * d + col) = acc;
 }
 
@@ -314,16 +273,7 @@ __global__ __launch_bounds__(64) void clc_user_kernel(const int32_t* __restrict_
 __global__ __launch_bounds__(256) void clc_loss_kernel(const float* __restrict__ rec, int64_t batch, int g1, float lam,
                                                        float reg, float* __restrict__ loss) {
     __shared__ float red[4][4];
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t b = threadIdx.x; b < batch; b += 256)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] += rec[b * 4 + q];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        s[q] = clc_wave_sum(s[q]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = s[q];
-    }
-    __syncthreads();
+    lg_record_sums(rec, batch, red);
     if (threadIdx.x == 0) {
         float t[4];
 #pragma unroll
@@ -349,27 +299,21 @@ int64_t clc_max_chunks(int64_t batch, int n_neg, int64_t n_slots) {
 ClcWs clc_layout(void* base, int64_t batch, int n_neg, int d, int64_t n_slots) {
     const int64_t m = batch * (n_neg + 1);
     ClcWs w;
-    char* p = reinterpret_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](int64_t floats) {
-        float* r = reinterpret_cast<float*>(p + off);
-        off += (size_t)((floats * 4 + 255) & ~(int64_t)255);
-        return r;
-    };
-    w.a1 = take(m);
-    w.a2 = take(m);
-    w.hn = take(batch * d);
-    w.ub = take(batch * d);
-    w.gu = take(batch * d);
-    w.gh = take(batch * d);
-    w.rec = take(batch * 4);
-    w.part = take(clc_max_chunks(batch, n_neg, n_slots) * 4 * d);
-    w.bytes = off;
+    WsCarver c(base);
+    w.a1 = c.take(m);
+    w.a2 = c.take(m);
+    w.hn = c.take(batch * d);
+    w.ub = c.take(batch * d);
+    w.gu = c.take(batch * d);
+    w.gh = c.take(batch * d);
+    w.rec = c.take(batch * 4);
+    w.part = c.take(clc_max_chunks(batch, n_neg, n_slots) * 4 * d);
+    w.bytes = c.bytes;
     return w;
 }
 
 bool clc_shape_ok(int64_t batch, int n_neg, int d, int64_t n_slots) {
-    return batch >= 1 && n_neg >= 1 && n_neg <= CLC_MAX_NEG && d >= 4 && d <= 256 && d % 4 == 0 && n_slots >= 1 &&
+    return batch >= 1 && n_neg >= 1 && n_neg <= CLC_MAX_NEG && lg_width_ok(d) && n_slots >= 1 &&
            batch * (int64_t)(n_neg + 1) < ((int64_t)1 << 31) && n_slots <= batch * (int64_t)(n_neg + 1);
 }
 
@@ -419,7 +363,7 @@ extern "C" int crh_clcrec_f32(const float* user_table, const float* item_table, 
                   "crh_clcrec_f32: NULL inverse-index pointer");
     CRH_CHECK_ARG(grad_user || grad_item || grad_feat || loss_out,
                   "crh_clcrec_f32: NULL gradients and loss: nothing to compute");
-    CRH_CHECK_ARG(d >= 4 && d <= 256 && d % 4 == 0, "crh_clcrec_f32: d = %d must be a multiple of 4 in [4, 256]", d);
+    LG_CHECK_WIDTH("crh_clcrec_f32", d);
     CRH_CHECK_ARG(n_neg >= 1 && n_neg <= CLC_MAX_NEG, "crh_clcrec_f32: n_neg = %d out of [1, %d]", n_neg, CLC_MAX_NEG);
     CRH_CHECK_ARG(batch >= 1 && batch * (int64_t)(n_neg + 1) < ((int64_t)1 << 31),
                   "crh_clcrec_f32: batch = %lld: batch * (1 + n_neg) must lie in [1, 2^31)", (long long)batch);
@@ -431,15 +375,9 @@ extern "C" int crh_clcrec_f32(const float* user_table, const float* item_table, 
                   (long long)n_chunks, CLC_CHUNK);
     CRH_CHECK_ARG(temp > 0.f && isfinite(temp), "crh_clcrec_f32: temp must be finite and > 0");
     CRH_CHECK_ARG(isfinite(lr_lambda) && isfinite(reg) && isfinite(scale), "crh_clcrec_f32: lr_lambda, reg and scale must be finite");
-    CRH_CHECK_ARG(((reinterpret_cast<uintptr_t>(user_table) | reinterpret_cast<uintptr_t>(item_table) |
-                    reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(grad_user) |
-                    reinterpret_cast<uintptr_t>(grad_item) | reinterpret_cast<uintptr_t>(grad_feat)) & 15) == 0,
+    CRH_CHECK_ARG(lg_aligned16(user_table, item_table, feat, grad_user, grad_item, grad_feat),
                   "crh_clcrec_f32: tables and gradients must be 16-byte aligned");
-    const size_t need = crh_clcrec_workspace_bytes(batch, n_neg, d, n_slots);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        crh_set_error("crh_clcrec_f32: workspace %zu < %zu bytes (or not 256-byte aligned)", workspace_bytes, need);
-        return CRH_ERR_WS;
-    }
+    LG_CHECK_WS("crh_clcrec_f32", workspace, workspace_bytes, crh_clcrec_workspace_bytes(batch, n_neg, d, n_slots));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const ClcWs w = clc_layout(workspace, batch, n_neg, d, n_slots);
     const int g1 = n_neg + 1;
@@ -448,19 +386,12 @@ extern "C" int crh_clcrec_f32(const float* user_table, const float* item_table, 
     const float coef1 = lr_lambda * per, coef2 = (1.f - lr_lambda) * per;
     const float reg_u = reg * scale / (2.f * (float)batch);
     const float reg_v = reg * scale / (2.f * (float)batch * (float)g1);
-#define CLC_GO(L)                                                                                                       \
-    clc_launch<L>(w, user_table, item_table, feat, users, items, slot, slot_item, mix_count, slot_ptr, slot_rows,      \
-                  chunk_ptr, chunk_slot, n_chunks, user_ids, user_ptr, user_recs, n_users, batch, g1, d, n_slots, inv_t, \
-                  coef1, coef2, reg_u, reg_v, grad_user, grad_item, grad_feat, st)
-    const int lanes = d / 4;
-    if (lanes <= 1) CLC_GO(1);
-    else if (lanes <= 2) CLC_GO(2);
-    else if (lanes <= 4) CLC_GO(4);
-    else if (lanes <= 8) CLC_GO(8);
-    else if (lanes <= 16) CLC_GO(16);
-    else if (lanes <= 32) CLC_GO(32);
-    else CLC_GO(64);
-#undef CLC_GO
+    lg_dispatch_lpr(d, [&](auto lpr) {
+        clc_launch<decltype(lpr)::value>(w, user_table, item_table, feat, users, items, slot, slot_item, mix_count, slot_ptr,
+                                         slot_rows, chunk_ptr, chunk_slot, n_chunks, user_ids, user_ptr, user_recs, n_users,
+                                         batch, g1, d, n_slots, inv_t, coef1, coef2, reg_u, reg_v, grad_user, grad_item,
+                                         grad_feat, st);
+    });
     if (loss_out)
         hipLaunchKernelGGL(clc_loss_kernel, dim3(1), dim3(256), 0, st, w.rec, batch, g1, lr_lambda, reg, loss_out);
     CRH_HIP(hipGetLastError());

@@ -20,7 +20,7 @@
 // finish to the loss terms (a loss-only call, e.g. under torch.no_grad).
 #include <math.h>
 
-#include "crh_common.h"
+#include "loss_common.h"
 
 namespace {
 
@@ -36,12 +36,6 @@ __device__ __forceinline__ int read_n(const int32_t* n_dev, int64_t n_max) {
     if (!n_dev) return (int)n_max;
     const int n = n_dev[0];
     return n < 0 ? 0 : (n > n_max ? (int)n_max : n);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 // row of the accumulator register r in lane half h (C/D map of the 32x32 MFMA shapes)
@@ -70,7 +64,7 @@ __global__ __launch_bounds__(256) void nce_prep_kernel(const float* __restrict__
     const float* src = v + (int64_t)(rows ? rows[r] : r) * d;
     float ss = 0.f;
     for (int c = lane; c < d; c += 64) ss += src[c] * src[c];
-    const float nr = sqrtf(wave_sum(ss));
+    const float nr = sqrtf(lg_wave_sum(ss));
     const float den = fmaxf(nr, NCE_EPS);
     for (int c = lane; c < dp; c += 64) z[c] = c < d ? (b_cos ? src[c] / den : src[c]) : 0.f;
     if (lane == 0) (view ? nrm2 : nrm1)[r] = nr;
@@ -302,7 +296,7 @@ __global__ __launch_bounds__(256) void nce_finish_kernel(const float* __restrict
     }
     float inv_den = 1.f, nr = 1.f;
     if (b_cos) {
-        dot = wave_sum(dot);
+        dot = lg_wave_sum(dot);
         nr = nrm[i];
         inv_den = 1.f / fmaxf(nr, NCE_EPS);
     }
@@ -324,7 +318,7 @@ __global__ __launch_bounds__(256) void nce_loss_kernel(const float* __restrict__
     const int n = read_n(n_dev, n_max);
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += lrow[i];
-    s = wave_sum(s);
+    s = lg_wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) loss[0] = n > 0 ? ((red[0] + red[1]) + (red[2] + red[3])) / (float)n : 0.f;
@@ -346,24 +340,18 @@ struct NceWs {
 NceWs nce_layout(void* base, int64_t n_max, int d) {
     const int64_t n_pad = ceil32(n_max), dp = ceil32(d), splits = nce_splits(n_max);
     NceWs w;
-    char* p = reinterpret_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](int64_t floats) {
-        float* r = reinterpret_cast<float*>(p + off);
-        off += (size_t)((floats * 4 + 255) & ~(int64_t)255);
-        return r;
-    };
-    w.z1 = take(n_pad * dp);
-    w.z2 = take(n_pad * dp);
-    w.nrm1 = take(n_pad);
-    w.nrm2 = take(n_pad);
-    w.diag = take(n_pad);
-    w.dlse2 = take(n_pad);
-    w.lrow = take(n_pad);
-    w.part_m = take(splits * n_pad);
-    w.part_l = take(splits * n_pad);
-    w.part_acc = take(splits * n_pad * dp);
-    w.bytes = off;
+    WsCarver c(base);
+    w.z1 = c.take(n_pad * dp);
+    w.z2 = c.take(n_pad * dp);
+    w.nrm1 = c.take(n_pad);
+    w.nrm2 = c.take(n_pad);
+    w.diag = c.take(n_pad);
+    w.dlse2 = c.take(n_pad);
+    w.lrow = c.take(n_pad);
+    w.part_m = c.take(splits * n_pad);
+    w.part_l = c.take(splits * n_pad);
+    w.part_acc = c.take(splits * n_pad * dp);
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -409,15 +397,11 @@ extern "C" int crh_infonce_f32(const float* view1, const int32_t* rows1, const f
     CRH_CHECK_ARG(view1 && view2, "crh_infonce_f32: NULL view pointer");
     CRH_CHECK_ARG(grad1 || grad2 || loss_out, "crh_infonce_f32: NULL gradients and loss: nothing to compute");
     CRH_CHECK_ARG(n_max >= 1 && n_max <= (1 << 30), "crh_infonce_f32: n_max %lld out of [1, 2^30]", (long long)n_max);
-    CRH_CHECK_ARG(d >= 4 && d <= 256 && d % 4 == 0, "crh_infonce_f32: d = %d must be a multiple of 4 in [4, 256]", d);
+    LG_CHECK_WIDTH("crh_infonce_f32", d);
     CRH_CHECK_ARG(tau > 0.f && isfinite(tau), "crh_infonce_f32: tau must be finite and > 0");
     CRH_CHECK_ARG(((reinterpret_cast<uintptr_t>(view1) | reinterpret_cast<uintptr_t>(view2)) & 3) == 0,
                   "crh_infonce_f32: misaligned view pointer");
-    const size_t need = crh_infonce_workspace_bytes(n_max, d);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        crh_set_error("crh_infonce_f32: workspace %zu < %zu bytes (or not 256-byte aligned)", workspace_bytes, need);
-        return CRH_ERR_WS;
-    }
+    LG_CHECK_WS("crh_infonce_f32", workspace, workspace_bytes, crh_infonce_workspace_bytes(n_max, d));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const NceWs w = nce_layout(workspace, n_max, d);
     const int64_t n_pad = ceil32(n_max);

@@ -1,0 +1,146 @@
+// What the fused loss kernels (infonce.hip, clcrec.hip, ccfcrec.hip, aldi.hip) share: the wave and lane-group sums, the
+// lane-group coordinates, the front of the one-workgroup loss kernels, and on the host the workspace carver, the argument
+// checks with their messages and the dispatch on the lane-group width.
+//
+// A lane group is LPR = pow2(d / 4) lanes that hold one row of d floats, four columns per lane (16-byte loads); a wave
+// holds 64 / LPR rows at a time.
+#pragma once
+#include <type_traits>
+
+#include "crh_common.h"
+
+namespace {
+
+// ---- device ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float lg_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ float lg_wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    return v;
+}
+
+// sum over the LPR lanes of a row's group / over the 64 / LPR groups (same column of every group)
+template <int LPR>
+__device__ __forceinline__ float lg_group_sum(float v) {
+#pragma unroll
+    for (int off = LPR / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+template <int LPR>
+__device__ __forceinline__ float lg_cross_sum1(float v) {
+    if constexpr (LPR < 64) {                          // (one group per wave: nothing to add)
+#pragma unroll
+        for (int off = 32; off >= LPR; off >>= 1) v += __shfl_xor(v, off);
+    }
+    return v;
+}
+
+// (a caller that sits next to other LPR < 64 work keeps its own `if constexpr (LPR < 64)` around the call: hipcc 7.2
+// crashes on some of the no-op calls)
+template <int LPR>
+__device__ __forceinline__ f32x4 lg_cross_sum(f32x4 v) {
+    if constexpr (LPR < 64) {
+#pragma unroll
+        for (int off = 32; off >= LPR; off >>= 1) {
+            const float x = __shfl_xor(v[0], off), y = __shfl_xor(v[1], off);
+            const float z = __shfl_xor(v[2], off), w = __shfl_xor(v[3], off);
+            v += f32x4{x, y, z, w};
+        }
+    }
+    return v;
+}
+
+__device__ __forceinline__ f32x4 lg_load4(const float* p, bool ok) {
+    return ok ? *reinterpret_cast<const f32x4*>(p) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+__device__ __forceinline__ float lg_dot4(const f32x4& a, const f32x4& b) {
+    return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]);
+}
+
+// where a lane stands: `const auto [lane, cl, grp, col] = lg_coords<LPR>();` -- the lane, its place in its group, the
+// group (= the row of the pass) and the first of its four columns
+struct LgCoords {
+    int lane, cl, grp, col;
+};
+template <int LPR>
+__device__ __forceinline__ LgCoords lg_coords() {
+    const int lane = threadIdx.x & 63, cl = lane & (LPR - 1), grp = LPR == 64 ? 0 : lane / LPR;
+    return {lane, cl, grp, 4 * cl};
+}
+
+// (A chunk's bounds -- k_begin = ptr[s] + (ch - chunk_ptr[s]) * CHUNK, k_end clamped to ptr[s + 1] -- stay written out in the
+// three chunk kernels: as a function of any shape they changed the code generated around the walk that follows them.)
+
+// the front of a one-workgroup loss kernel (256 threads): red[w][q] = wave w's part of sum_b rec[4 b + q], every thread its
+// records in index order, then the wave; ends with the barrier.  Thread 0 then adds the waves as (0 + 1) + (2 + 3) in the
+// kernel's own body (with that sum in here the compiler contracted the total of ccfcrec's epilogue differently).
+__device__ __forceinline__ void lg_record_sums(const float* rec, int64_t batch, float (*red)[4]) {
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t b = threadIdx.x; b < batch; b += 256)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] += rec[b * 4 + q];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        s[q] = lg_wave_sum(s[q]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][q] = s[q];
+    }
+    __syncthreads();
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------
+// hands out 256-byte aligned float arrays of a workspace one after the other; from a NULL base it only counts the bytes
+struct WsCarver {
+    char* base;
+    size_t bytes = 0;
+    explicit WsCarver(void* b) : base(reinterpret_cast<char*>(b)) {}
+    float* take(int64_t floats) {
+        float* r = reinterpret_cast<float*>(base + bytes);
+        bytes += (size_t)((floats * 4 + 255) & ~(int64_t)255);
+        return r;
+    }
+};
+
+inline bool lg_ws_ok(const char* fn, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (workspace && workspace_bytes >= need && !(reinterpret_cast<uintptr_t>(workspace) & 255)) return true;
+    crh_set_error("%s: workspace %zu < %zu bytes (or not 256-byte aligned)", fn, workspace_bytes, need);
+    return false;
+}
+#define LG_CHECK_WS(fn, workspace, workspace_bytes, need)                       \
+    do {                                                                        \
+        if (!lg_ws_ok(fn, workspace, workspace_bytes, need)) return CRH_ERR_WS; \
+    } while (0)
+
+inline bool lg_width_ok(int d) { return d >= 4 && d <= 256 && d % 4 == 0; }
+#define LG_CHECK_WIDTH(fn, d) CRH_CHECK_ARG(lg_width_ok(d), "%s: d = %d must be a multiple of 4 in [4, 256]", fn, d)
+
+// what: "user" or "item"
+#define LG_CHECK_IDS(fn, what, lo, hi, rows)                                                                       \
+    CRH_CHECK_ARG((lo) >= 0 && (lo) <= (hi) && (hi) < (rows), "%s: %s ids [%d, %d] outside the %s table of %lld rows", \
+                  fn, what, lo, hi, what, (long long)(rows))
+
+template <class... T>
+inline bool lg_aligned16(const T*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+}
+
+// f(std::integral_constant<int, LPR>) with LPR = pow2(d / 4)
+template <class F>
+inline void lg_dispatch_lpr(int d, F&& f) {
+    const int lanes = d / 4;
+    if (lanes <= 1) f(std::integral_constant<int, 1>{});
+    else if (lanes <= 2) f(std::integral_constant<int, 2>{});
+    else if (lanes <= 4) f(std::integral_constant<int, 4>{});
+    else if (lanes <= 8) f(std::integral_constant<int, 8>{});
+    else if (lanes <= 16) f(std::integral_constant<int, 16>{});
+    else if (lanes <= 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+}  // namespace

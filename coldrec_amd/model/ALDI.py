@@ -26,13 +26,7 @@ from .. import ops
 from ..train import dp_from_env
 from ..util.utils import epoch_triples
 from .BaseRecommender import BaseColdStartTrainer
-from .MF import _require_gpu
-
-
-def _check_width(width):
-    if width % 4 != 0 or width < 4 or width > 256:
-        raise ValueError(f'ALDI: --emb_size {width} must be a multiple of 4 in [4, 256] (the fused HIP loss loads rows in '
-                         f'16-byte pieces and keeps at most 256 columns per wave)')
+from .MF import _check_width, _require_gpu
 
 
 def item_frequency(data):
@@ -102,7 +96,7 @@ class ALDI_Learner(nn.Module):
     def __init__(self, args, data, emb_size, device):
         super().__init__()
         self.args, self.data, self.latent_size, self.device = args, data, emb_size, device
-        _check_width(int(emb_size))
+        _check_width('ALDI', '--emb_size', int(emb_size))
         content = torch.as_tensor(np.asarray(data.mapped_item_content), dtype=torch.float32)
         self.register_buffer('item_content', content, persistent=False)
         hidden = int(getattr(args, 'aldi_hidden', 200))

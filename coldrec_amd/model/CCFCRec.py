@@ -16,13 +16,7 @@ import torch.nn as nn
 from .. import ops
 from ..train import dp_from_env
 from .BaseRecommender import BaseColdStartTrainer
-from .MF import _require_gpu
-
-
-def _check_width(width):
-    if width % 4 != 0 or width < 4 or width > 256:
-        raise ValueError(f'CCFCRec: --implicit_dim {width} must be a multiple of 4 in [4, 256] (the fused HIP loss loads '
-                         f'rows in 16-byte pieces and keeps at most 256 columns per wave)')
+from .MF import _check_width, _require_gpu
 
 
 def _check_rows(args):
@@ -92,7 +86,7 @@ class CCFCRec_Learner(nn.Module):
         else:
             self.user_embedding = nn.Parameter(torch.empty(data.user_num, int(args.implicit_dim)))
             self.item_embedding = nn.Parameter(torch.empty(data.item_num, int(args.implicit_dim)))
-        _check_width(self.item_embedding.shape[1])
+        _check_width('CCFCRec', '--implicit_dim', self.item_embedding.shape[1])
         self.gen_layer1 = nn.Linear(A, int(args.cat_implicit_dim))
         self.gen_layer2 = nn.Linear(int(args.cat_implicit_dim), self.item_embedding.shape[1])
         self.h = nn.LeakyReLU()
@@ -146,7 +140,7 @@ class CCFCRec(BaseColdStartTrainer):
         if self.args.cold_object == 'user':
             raise Exception('Cold user is not supported in CCFCRec due to its specific design for item cold-start problem.')
         if not self.args.pretrain:
-            _check_width(int(self.args.implicit_dim))
+            _check_width('CCFCRec', '--implicit_dim', int(self.args.implicit_dim))
         self.shape = _check_rows(self.args)
         self.model = CCFCRec_Learner(self.args, self.data, self.emb_size, self.device)
 

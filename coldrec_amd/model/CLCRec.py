@@ -15,13 +15,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..train import dp_from_env
 from .BaseRecommender import BaseColdStartTrainer
-from .MF import _require_gpu
-
-
-def _check_width(emb_size):
-    if emb_size % 4 != 0 or emb_size < 4 or emb_size > 256:
-        raise ValueError(f'CLCRec: --emb_size {emb_size} must be a multiple of 4 in [4, 256] (the fused HIP loss loads '
-                         f'rows in 16-byte pieces and keeps at most 256 columns per wave)')
+from .MF import _check_width, _require_gpu
 
 
 class _FusedLoss(torch.autograd.Function):
@@ -46,7 +40,7 @@ class _FusedLoss(torch.autograd.Function):
 class CLCRec_Learner(nn.Module):
     def __init__(self, args, data, emb_size, device):
         super().__init__()
-        _check_width(emb_size)
+        _check_width('CLCRec', '--emb_size', emb_size)
         self.args, self.data, self.latent_size, self.device = args, data, emb_size, device
         self.register_buffer('item_content', torch.as_tensor(np.asarray(data.mapped_item_content), dtype=torch.float32),
                              persistent=False)
@@ -108,7 +102,7 @@ class CLCRec(BaseColdStartTrainer):
         super().__init__(config)
         if self.args.cold_object == 'user':
             raise Exception('Cold user is not supported in CLCRec due to its specific design for item cold-start problem.')
-        _check_width(self.emb_size)
+        _check_width('CLCRec', '--emb_size', self.emb_size)
         self.model = CLCRec_Learner(self.args, self.data, self.emb_size, self.device)
 
     def _snapshot(self):

@@ -21,6 +21,13 @@ def _require_gpu(device):
         raise RuntimeError('coldrec_amd trainers run on the MI355X only (--use_gpu true); there is no CPU path')
 
 
+def _check_width(model, flag, width):
+    """The row width the fused HIP losses (ops.clcrec, ops.ccfcrec, ops.aldi) take; ``flag`` is the option that sets it."""
+    if width % 4 != 0 or width < 4 or width > 256:
+        raise ValueError(f'{model}: {flag} {width} must be a multiple of 4 in [4, 256] (the fused HIP loss loads rows in '
+                         f'16-byte pieces and keeps at most 256 columns per wave)')
+
+
 class Matrix_Factorization(object):
     """Two xavier-uniform tables drawn exactly like model/MF.py:72-79 (user table first)."""
 

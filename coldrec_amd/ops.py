@@ -888,6 +888,46 @@ def spmm_csr(rowptr, col, val, x, y=None, acc_in=None, s_in: float = 1.0, acc_ou
     _lib.check(rc, "crh_spmm_csr_f32")
 
 
+# ---- what the fused losses check alike: op = the name in front of a message, what = the noun the message uses ----------
+
+def _check_2d_f32(op: str, what: str, *tensors) -> None:
+    for t in tensors:
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise RuntimeError(f"{op}: {what} must be contiguous 2-D float32 tensors")
+
+
+def _grad_buffer(op: str, what: str, g, like: torch.Tensor, want: bool, overwritten: bool):
+    """The gradient buffer of ``like``: the one given (checked), else a new one when wanted -- ``empty`` when the kernel
+    writes every row, ``zeros`` when rows it does not touch must read zero --, else None."""
+    if g is None:
+        if not want:
+            return None
+        return torch.empty_like(like) if overwritten else torch.zeros_like(like)
+    if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != like.shape:
+        raise RuntimeError(f"{op}: gradient buffers must be contiguous float32 tensors of {what}")
+    return g
+
+
+_AT_LEAST = {1: "one element", 4: "four elements", 5: "five elements"}
+
+
+def _loss_buffer(op: str, loss, n: int, device) -> torch.Tensor:
+    if loss is None:
+        return torch.empty(n, dtype=torch.float32, device=device)
+    if loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < n:
+        raise RuntimeError(f"{op}: loss must be a contiguous float32 buffer of at least {_AT_LEAST[n]}")
+    return loss
+
+
+def _workspace_arg(op: str, workspace, make, *shape) -> torch.Tensor:
+    """The workspace given (checked), else ``make(*shape)``."""
+    if workspace is None:
+        return make(*shape)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise RuntimeError(f"{op}: workspace must be a contiguous uint8 tensor")
+    return workspace
+
+
 # ---- contrastive learning (infonce.hip) ------------------------------------------------------------------------------
 
 def infonce_workspace_bytes(n_max: int, d: int) -> int:
@@ -909,9 +949,7 @@ def infonce(view1: torch.Tensor, view2: torch.Tensor, tau: float, b_cos: bool = 
     computed (None is returned for it; without grad2 the column pass is skipped)."""
     _need_cuda(view1, view2, rows1, rows2, n_dev, grad1, grad2, loss, workspace)
     dev = view1.device
-    for v in (view1, view2):
-        if v.dtype != torch.float32 or not v.is_contiguous() or v.dim() != 2:
-            raise RuntimeError("infonce: views must be contiguous 2-D float32 tensors")
+    _check_2d_f32("infonce", "views", view1, view2)
     if view1.shape[1] != view2.shape[1]:
         raise RuntimeError("infonce: views differ in width")
     for t in (view2, rows1, rows2, n_dev, grad1, grad2, loss, workspace):
@@ -922,8 +960,7 @@ def infonce(view1: torch.Tensor, view2: torch.Tensor, tau: float, b_cos: bool = 
             raise RuntimeError("infonce: row ids must be contiguous 1-D int32")
     if n_dev is not None and (n_dev.dtype != torch.int32 or n_dev.numel() < 1):
         raise RuntimeError("infonce: n_dev must be a device int32 scalar")
-    if loss is not None and (loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 1):
-        raise RuntimeError("infonce: loss must be a contiguous float32 buffer of at least one element")
+    loss = _loss_buffer("infonce", loss, 1, dev)
     d = view1.shape[1]
     if n_max is None:
         n_max = rows1.shape[0] if rows1 is not None else view1.shape[0]
@@ -931,25 +968,12 @@ def infonce(view1: torch.Tensor, view2: torch.Tensor, tau: float, b_cos: bool = 
             or rows1 is not None and rows1.shape[0] < n_max or rows2 is not None and rows2.shape[0] < n_max:
         raise RuntimeError("infonce: fewer rows than n_max")
 
-    def grad_buffer(g, v, rows, want):
-        if g is None:
-            if not want:
-                return None
-            # every row is overwritten only when the batch is the whole view; otherwise untouched rows must read zero
-            whole = rows is None and n_dev is None and not accumulate and v.shape[0] == n_max
-            return torch.empty_like(v) if whole else torch.zeros_like(v)
-        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != v.shape:
-            raise RuntimeError("infonce: gradient buffers must be contiguous float32 tensors of the views' shapes")
-        return g
+    def whole(v, rows):   # every row is overwritten only when the batch is the whole view
+        return rows is None and n_dev is None and not accumulate and v.shape[0] == n_max
 
-    grad1 = grad_buffer(grad1, view1, rows1, want_grad1)
-    grad2 = grad_buffer(grad2, view2, rows2, want_grad2)
-    if loss is None:
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-    if workspace is None:
-        workspace = infonce_workspace(n_max, d, dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise RuntimeError("infonce: workspace must be a contiguous uint8 tensor")
+    grad1 = _grad_buffer("infonce", "the views' shapes", grad1, view1, want_grad1, whole(view1, rows1))
+    grad2 = _grad_buffer("infonce", "the views' shapes", grad2, view2, want_grad2, whole(view2, rows2))
+    workspace = _workspace_arg("infonce", workspace, infonce_workspace, n_max, d, dev)
     _lib.check(_lib.lib().crh_infonce_f32(_lib.ptr(view1), _lib.ptr(rows1), _lib.ptr(view2), _lib.ptr(rows2), _lib.ptr(n_dev),
                                           int(n_max), int(d), float(tau), int(bool(b_cos)), float(scale), int(bool(accumulate)),
                                           _lib.ptr(grad1), _lib.ptr(grad2), _lib.ptr(loss), _lib.ptr(workspace),
@@ -982,6 +1006,17 @@ def _grouped(ids: torch.Tensor):
     return uniq, inv, order, cnt, ptr
 
 
+def _owner_chunks(ids: torch.Tensor, chunk: int):
+    """``_grouped`` with every group cut into chunks of ``chunk`` positions: (distinct ids, grouped positions, offsets,
+    offsets into the chunk list, each chunk's group, every position's index into the distinct ids)."""
+    uniq, inv, order, cnt, ptr = _grouped(ids)
+    nch = (cnt + (chunk - 1)) // chunk
+    chunk_ptr = torch.zeros(uniq.shape[0] + 1, dtype=torch.int64, device=ids.device)
+    torch.cumsum(nch, 0, out=chunk_ptr[1:])
+    chunk_own = torch.repeat_interleave(torch.arange(uniq.shape[0], device=ids.device), nch)
+    return uniq, order, ptr, chunk_ptr, chunk_own, inv
+
+
 def clcrec_plan(users: torch.Tensor, items: torch.Tensor, n_users: Optional[int] = None,
                 n_items: Optional[int] = None) -> dict:
     """The index side of one crh_clcrec_f32 step.  users (B,), items (B, 1 + G): integer device tensors (column 0 = the
@@ -995,7 +1030,6 @@ def clcrec_plan(users: torch.Tensor, items: torch.Tensor, n_users: Optional[int]
         raise RuntimeError("clcrec_plan: users must be (B,) and items (B, 1 + G) with B >= 1, G >= 1")
     if users.dtype.is_floating_point or items.dtype.is_floating_point or users.device != items.device:
         raise RuntimeError("clcrec_plan: users and items must be integer tensors on one device")
-    dev, i32 = users.device, torch.int32
     flat = items.reshape(-1).long()
     ulong = users.long()
     if n_users is not None and (int(ulong.min()) < 0 or int(ulong.max()) >= n_users):
@@ -1003,14 +1037,10 @@ def clcrec_plan(users: torch.Tensor, items: torch.Tensor, n_users: Optional[int]
     if n_items is not None and (int(flat.min()) < 0 or int(flat.max()) >= n_items):
         raise RuntimeError("clcrec_plan: item id outside the item table")
 
-    slot_item, slot, slot_rows, cnt, slot_ptr = _grouped(flat)
     chunk = int(_lib.lib().crh_clcrec_chunk_rows())
-    nch = (cnt + (chunk - 1)) // chunk
-    chunk_ptr = torch.zeros(slot_item.shape[0] + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(nch, 0, out=chunk_ptr[1:])
-    chunk_slot = torch.repeat_interleave(torch.arange(slot_item.shape[0], device=dev), nch)
+    slot_item, slot_rows, slot_ptr, chunk_ptr, chunk_slot, slot = _owner_chunks(flat, chunk)
     user_ids, _, user_recs, _, user_ptr = _grouped(ulong)
-    c = lambda t: t.to(i32).contiguous()
+    c = lambda t: t.to(torch.int32).contiguous()
     return dict(batch=int(users.shape[0]), n_neg=int(items.shape[1] - 1), n_slots=int(slot_item.shape[0]),
                 n_chunks=int(chunk_slot.shape[0]), n_users=int(user_ids.shape[0]),
                 user_range=(int(user_ids[0]), int(user_ids[-1])), item_range=(int(slot_item[0]), int(slot_item[-1])),
@@ -1029,9 +1059,7 @@ def clcrec(user_table: torch.Tensor, item_table: torch.Tensor, feat: torch.Tenso
     is not computed (None)."""
     _need_cuda(user_table, item_table, feat, mix_count, grad_user, grad_item, grad_feat, loss, workspace)
     dev = user_table.device
-    for t in (user_table, item_table, feat):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
-            raise RuntimeError("clcrec: tables and feat must be contiguous 2-D float32 tensors")
+    _check_2d_f32("clcrec", "tables and feat", user_table, item_table, feat)
     d = user_table.shape[1]
     if item_table.shape[1] != d or feat.shape[1] != d:
         raise RuntimeError("clcrec: tables and feat differ in width")
@@ -1049,26 +1077,11 @@ def clcrec(user_table: torch.Tensor, item_table: torch.Tensor, feat: torch.Tenso
         if t is not None and t.device != dev:
             raise RuntimeError("clcrec: every tensor must be on the tables' device")
 
-    def grad_buffer(g, like, want, touched_all):
-        if g is None:
-            if not want:
-                return None
-            return torch.empty_like(like) if touched_all else torch.zeros_like(like)
-        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != like.shape:
-            raise RuntimeError("clcrec: gradient buffers must be contiguous float32 tensors of the tables' shapes")
-        return g
-
-    grad_user = grad_buffer(grad_user, user_table, want_user, False)
-    grad_item = grad_buffer(grad_item, item_table, want_item, False)
-    grad_feat = grad_buffer(grad_feat, feat, want_feat, True)
-    if loss is None:
-        loss = torch.empty(4, dtype=torch.float32, device=dev)
-    elif loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 4:
-        raise RuntimeError("clcrec: loss must be a contiguous float32 buffer of at least four elements")
-    if workspace is None:
-        workspace = clcrec_workspace(B, G, d, S, dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise RuntimeError("clcrec: workspace must be a contiguous uint8 tensor")
+    grad_user = _grad_buffer("clcrec", "the tables' shapes", grad_user, user_table, want_user, False)
+    grad_item = _grad_buffer("clcrec", "the tables' shapes", grad_item, item_table, want_item, False)
+    grad_feat = _grad_buffer("clcrec", "the tables' shapes", grad_feat, feat, want_feat, True)
+    loss = _loss_buffer("clcrec", loss, 4, dev)
+    workspace = _workspace_arg("clcrec", workspace, clcrec_workspace, B, G, d, S, dev)
     p = plan
     _lib.check(_lib.lib().crh_clcrec_f32(
         _lib.ptr(user_table), _lib.ptr(item_table), _lib.ptr(feat), _lib.ptr(p["users"]), _lib.ptr(p["items"]),
@@ -1102,17 +1115,6 @@ def ccfcrec_workspace(batch: int, n_pos: int, n_neg: int, n_self: int, d: int, n
                        dtype=torch.uint8, device=device)
 
 
-def _owner_chunks(ids: torch.Tensor, chunk: int):
-    """``_grouped`` with every group cut into chunks of ``chunk`` positions: (distinct ids, grouped positions, offsets,
-    offsets into the chunk list, each chunk's group)."""
-    uniq, _, order, cnt, ptr = _grouped(ids)
-    nch = (cnt + (chunk - 1)) // chunk
-    chunk_ptr = torch.zeros(uniq.shape[0] + 1, dtype=torch.int64, device=ids.device)
-    torch.cumsum(nch, 0, out=chunk_ptr[1:])
-    chunk_own = torch.repeat_interleave(torch.arange(uniq.shape[0], device=ids.device), nch)
-    return uniq, order, ptr, chunk_ptr, chunk_own
-
-
 def ccfcrec_plan(users: torch.Tensor, items: torch.Tensor, neg_users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
                  self_neg: torch.Tensor, n_users: Optional[int] = None, n_items: Optional[int] = None) -> dict:
     """The index side of one crh_ccfcrec_f32 step.  users, items, neg_users (B,), pos (B, P), neg (B, P, N), self_neg
@@ -1141,8 +1143,8 @@ def ccfcrec_plan(users: torch.Tensor, items: torch.Tensor, neg_users: torch.Tens
     if n_items is not None and (item_range[0] < 0 or item_range[1] >= n_items):
         raise RuntimeError("ccfcrec_plan: item id outside the item table")
     chunk = int(_lib.lib().crh_ccfcrec_chunk_rows())
-    item_ids, item_occ, item_ptr, item_chunk_ptr, item_chunk_own = _owner_chunks(flat, chunk)
-    user_ids, user_occ, user_ptr, user_chunk_ptr, user_chunk_own = _owner_chunks(both, chunk)
+    item_ids, item_occ, item_ptr, item_chunk_ptr, item_chunk_own, _ = _owner_chunks(flat, chunk)
+    user_ids, user_occ, user_ptr, user_chunk_ptr, user_chunk_own, _ = _owner_chunks(both, chunk)
     c = lambda t: t.to(i32).contiguous()
     return dict(batch=B, n_pos=P, n_neg=N, n_self=S, n_items=int(item_ids.shape[0]), n_users=int(user_ids.shape[0]),
                 n_item_chunks=int(item_chunk_own.shape[0]), n_user_chunks=int(user_chunk_own.shape[0]),
@@ -1162,9 +1164,7 @@ def ccfcrec(user_table: torch.Tensor, item_table: torch.Tensor, q: torch.Tensor,
     computed (None).  Rows of zero norm are outside the contract (the reference divides by the norm)."""
     _need_cuda(user_table, item_table, q, grad_user, grad_item, grad_q, loss, workspace)
     dev = user_table.device
-    for t in (user_table, item_table, q):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
-            raise RuntimeError("ccfcrec: tables and q must be contiguous 2-D float32 tensors")
+    _check_2d_f32("ccfcrec", "tables and q", user_table, item_table, q)
     d = user_table.shape[1]
     if item_table.shape[1] != d or q.shape[1] != d:
         raise RuntimeError("ccfcrec: tables and q differ in width")
@@ -1183,26 +1183,12 @@ def ccfcrec(user_table: torch.Tensor, item_table: torch.Tensor, q: torch.Tensor,
         if t is not None and t.device != dev:
             raise RuntimeError("ccfcrec: every tensor must be on the tables' device")
 
-    def grad_buffer(g, like, want, touched_all):
-        if g is None:
-            if not want:
-                return None
-            return torch.empty_like(like) if touched_all else torch.zeros_like(like)
-        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != like.shape:
-            raise RuntimeError("ccfcrec: gradient buffers must be contiguous float32 tensors of the tables' shapes")
-        return g
-
-    grad_user = grad_buffer(grad_user, user_table, want_user, False)
-    grad_item = grad_buffer(grad_item, item_table, want_item, False)
-    grad_q = grad_buffer(grad_q, q, want_q, True)
-    if loss is None:
-        loss = torch.empty(5, dtype=torch.float32, device=dev)
-    elif loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 5:
-        raise RuntimeError("ccfcrec: loss must be a contiguous float32 buffer of at least five elements")
-    if workspace is None:
-        workspace = ccfcrec_workspace(B, P, N, S, d, plan["n_items"], plan["n_users"], dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise RuntimeError("ccfcrec: workspace must be a contiguous uint8 tensor")
+    grad_user = _grad_buffer("ccfcrec", "the tables' shapes", grad_user, user_table, want_user, False)
+    grad_item = _grad_buffer("ccfcrec", "the tables' shapes", grad_item, item_table, want_item, False)
+    grad_q = _grad_buffer("ccfcrec", "the tables' shapes", grad_q, q, want_q, True)
+    loss = _loss_buffer("ccfcrec", loss, 5, dev)
+    workspace = _workspace_arg("ccfcrec", workspace, ccfcrec_workspace, B, P, N, S, d, plan["n_items"], plan["n_users"],
+                               dev)
     p = plan
     _lib.check(_lib.lib().crh_ccfcrec_f32(
         _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]), _lib.ptr(q),
@@ -1239,9 +1225,7 @@ def aldi(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor
     _need_cuda(user_table, item_table, users, pos, neg, gen_user, gen_pos, gen_neg, item_weight, grad_user, grad_pos,
                grad_neg, loss, workspace)
     dev = user_table.device
-    for t in (user_table, item_table, gen_user, gen_pos, gen_neg):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
-            raise RuntimeError("aldi: tables and tower outputs must be contiguous 2-D float32 tensors")
+    _check_2d_f32("aldi", "tables and tower outputs", user_table, item_table, gen_user, gen_pos, gen_neg)
     d = user_table.shape[1]
     if d % 4 != 0 or d < 4 or d > 256:
         raise RuntimeError(f"aldi: width {d} must be a multiple of 4 in [4, 256]")
@@ -1266,23 +1250,10 @@ def aldi(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor
         raise RuntimeError("aldi: ids lie outside the tables")
     users, pos, neg = (t.to(torch.int32).contiguous() for t in ids)
 
-    def grad_buffer(g, want):
-        if g is None:
-            return torch.empty_like(gen_user) if want else None
-        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != gen_user.shape:
-            raise RuntimeError("aldi: gradient buffers must be contiguous float32 tensors of the tower outputs' shape")
-        return g
-
-    grad_user, grad_pos, grad_neg = grad_buffer(grad_user, want_user), grad_buffer(grad_pos, want_pos), \
-        grad_buffer(grad_neg, want_neg)
-    if loss is None:
-        loss = torch.empty(5, dtype=torch.float32, device=dev)
-    elif loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 5:
-        raise RuntimeError("aldi: loss must be a contiguous float32 buffer of at least five elements")
-    if workspace is None:
-        workspace = aldi_workspace(B, d, dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise RuntimeError("aldi: workspace must be a contiguous uint8 tensor")
+    grad_user, grad_pos, grad_neg = (_grad_buffer("aldi", "the tower outputs' shape", g, gen_user, want, True)
+                                     for g, want in ((grad_user, want_user), (grad_pos, want_pos), (grad_neg, want_neg)))
+    loss = _loss_buffer("aldi", loss, 5, dev)
+    workspace = _workspace_arg("aldi", workspace, aldi_workspace, B, d, dev)
     _lib.check(_lib.lib().crh_aldi_f32(
         _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]), _lib.ptr(users),
         _lib.ptr(pos), _lib.ptr(neg), int(u_lo), int(u_hi), int(i_lo), int(i_hi), _lib.ptr(gen_user), _lib.ptr(gen_pos),
