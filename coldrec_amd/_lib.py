@@ -99,6 +99,9 @@ SIGNATURES = {
     "crh_infonce_workspace_bytes": (_sz, [_i64, _i32]),
     "crh_infonce_splits": (_i32, [_i64]),
     "crh_infonce_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "crh_table_nce_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "crh_table_nce_splits": (_i32, [_i64, _i64, _i32]),
+    "crh_table_nce_f32": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "crh_clcrec_max_neg": (_i32, []),
     "crh_clcrec_chunk_rows": (_i32, []),
     "crh_clcrec_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),

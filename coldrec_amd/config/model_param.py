@@ -35,6 +35,16 @@ def model_specific_param(model_name, parser, available_models):
                             help='(addition) where the perturbation noise comes from: device = generated in the kernel '
                                  '(Philox4x32-10 keyed by --seed); host = torch.rand on the CPU generator, uploaded per '
                                  'layer -- the reference\'s own stream, for parity runs')
+    if model_name == 'NCL':      # config/model_param.py:318-324
+        parser.add_argument('--tau', type=float, default=0.2, help='Contrast temperature')
+        parser.add_argument('--ssl_reg', type=float, default=1e-6, help='Weight of the structure contrast')
+        parser.add_argument('--proto_reg', type=float, default=1e-7, help='Weight of the prototype contrast')
+        parser.add_argument('--alpha', type=float, default=1.0, help='Weight of the item side of the structure contrast')
+        parser.add_argument('--hyper_layers', type=int, default=1,
+                            help='The context is GCN layer 2 * hyper_layers; needs hyper_layers * 2 <= layers')
+        parser.add_argument('--num_clusters', type=int, default=20, help='Prototypes (k-means clusters) per table')
+        parser.add_argument('--proto_start', type=int, default=20,
+                            help='(addition) first epoch, 0-based, of the prototype phase; the reference hard-codes 20')
     if model_name == 'CLCRec':      # config/model_param.py:125-129
         parser.add_argument('--num_neg', type=int, default=128, help='Sampled negatives per record')
         parser.add_argument('--temp_value', type=float, default=2.0, help='Contrastive loss temperature')

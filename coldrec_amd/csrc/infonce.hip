@@ -24,22 +24,9 @@
 
 namespace {
 
-constexpr int NCE_WAVES = 4;          // waves per workgroup: 4 row blocks that share one streamed tile in LDS
+// (NCE_WAVES, NCE_EPS, LN2, ceil32, read_n and crow are shared with table_nce.hip: loss_common.h)
 constexpr int NCE_TARGET_WAVES = 2048;  // column splits are added until the grid holds this many waves (2 per SIMD)
 constexpr int NCE_MAX_SPLITS = 32;
-constexpr float NCE_EPS = 1e-12f;     // F.normalize's clamp_min
-constexpr float LN2 = 0.6931471805599453f;
-
-__host__ __device__ inline int64_t ceil32(int64_t x) { return (x + 31) & ~(int64_t)31; }
-
-__device__ __forceinline__ int read_n(const int32_t* n_dev, int64_t n_max) {
-    if (!n_dev) return (int)n_max;
-    const int n = n_dev[0];
-    return n < 0 ? 0 : (n > n_max ? (int)n_max : n);
-}
-
-// row of the accumulator register r in lane half h (C/D map of the 32x32 MFMA shapes)
-__device__ __forceinline__ int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // ---- prep: one wave per padded row of each view ---------------------------------------------------------------------
 __global__ __launch_bounds__(256) void nce_prep_kernel(const float* __restrict__ v1, const int32_t* __restrict__ rows1,

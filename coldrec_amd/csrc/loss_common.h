@@ -1,5 +1,5 @@
-// What the fused loss kernels (infonce.hip, clcrec.hip, ccfcrec.hip, aldi.hip) share: the wave and lane-group sums, the
-// lane-group coordinates, the front of the one-workgroup loss kernels, and on the host the workspace carver, the argument
+// What the fused loss kernels (infonce.hip, table_nce.hip, clcrec.hip, ccfcrec.hip, aldi.hip) share: the wave and
+// lane-group sums, the lane-group coordinates, the front of the one-workgroup loss kernels, and on the host the workspace carver, the argument
 // checks with their messages and the dispatch on the lane-group width.
 //
 // A lane group is LPR = pow2(d / 4) lanes that hold one row of d floats, four columns per lane (16-byte loads); a wave
@@ -93,6 +93,22 @@ __device__ __forceinline__ void lg_record_sums(const float* rec, int64_t batch, 
     }
     __syncthreads();
 }
+
+// ---- what the two streamed-softmax kernels (infonce.hip, table_nce.hip) share ---------------------------------------
+constexpr int NCE_WAVES = 4;          // waves per workgroup: 4 row blocks that share one streamed tile in LDS
+constexpr float NCE_EPS = 1e-12f;     // F.normalize's clamp_min
+constexpr float LN2 = 0.6931471805599453f;
+
+__host__ __device__ inline int64_t ceil32(int64_t x) { return (x + 31) & ~(int64_t)31; }
+
+__device__ __forceinline__ int read_n(const int32_t* n_dev, int64_t n_max) {
+    if (!n_dev) return (int)n_max;
+    const int n = n_dev[0];
+    return n < 0 ? 0 : (n > n_max ? (int)n_max : n);
+}
+
+// row of the accumulator register r in lane half h (C/D map of the 32x32 MFMA shapes)
+__device__ __forceinline__ int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
 // hands out 256-byte aligned float arrays of a workspace one after the other; from a NULL base it only counts the bytes

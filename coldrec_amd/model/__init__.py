@@ -7,15 +7,18 @@ subclasses ``BaseColdStartTrainer`` can be registered with ``register(name, cls)
 ``keys()`` lists the core trainers plus whatever ``register()`` added.  The contrastive trainers (SimGCL, XSimGCL)
 resolve by name through ``[]``, ``.get()`` and ``in`` as well, from a cache of their own: resolving one never changes
 what ``keys()`` reports.  The cold-start trainers CLCRec, CCFCRec and ALDI resolve the same way from a third table and are not part of
-``names()`` either (both listings are pinned); ``resolvable()`` is everything a ``--model`` flag can name.
+``names()`` either (both listings are pinned); NCL, the third graph-contrastive backbone, has a fourth table for the same
+reason.  ``resolvable()`` is everything a ``--model`` flag can name.
 """
 import importlib
 
 _BUILTIN = {'MF': ('.MF', 'MF'), 'LightGCN': ('.LightGCN', 'LightGCN'), 'DropoutNet': ('.DropoutNet', 'DropoutNet')}
 _CONTRASTIVE = {'SimGCL': ('.SimGCL', 'SimGCL'), 'XSimGCL': ('.XSimGCL', 'XSimGCL')}
 _COLD = {'CLCRec': ('.CLCRec', 'CLCRec'), 'CCFCRec': ('.CCFCRec', 'CCFCRec'), 'ALDI': ('.ALDI', 'ALDI')}
+_NCL = {'NCL': ('.NCL', 'NCL')}
 _contrastive_cache = {}
 _cold_cache = {}
+_ncl_cache = {}
 
 
 class _Registry(dict):
@@ -30,6 +33,11 @@ class _Registry(dict):
                 mod, cls = _COLD[name]
                 _cold_cache[name] = getattr(importlib.import_module(mod, __name__), cls)
             return _cold_cache[name]
+        if name in _NCL:
+            if name not in _ncl_cache:
+                mod, cls = _NCL[name]
+                _ncl_cache[name] = getattr(importlib.import_module(mod, __name__), cls)
+            return _ncl_cache[name]
         if name not in _BUILTIN:
             raise KeyError(name)
         mod, cls = _BUILTIN[name]
@@ -43,7 +51,7 @@ class _Registry(dict):
             return default
 
     def __contains__(self, name):
-        return name in _BUILTIN or name in _CONTRASTIVE or name in _COLD or dict.__contains__(self, name)
+        return name in _BUILTIN or name in _CONTRASTIVE or name in _COLD or name in _NCL or dict.__contains__(self, name)
 
     def keys(self):
         return sorted(set(_BUILTIN) | set(dict.keys(self)))
@@ -53,8 +61,8 @@ class _Registry(dict):
         return sorted(set(_BUILTIN) | set(_CONTRASTIVE) | set(dict.keys(self)))
 
     def resolvable(self):
-        """Everything a ``--model`` flag can name: ``names()`` + the cold-start trainers."""
-        return sorted(set(self.names()) | set(_COLD))
+        """Everything a ``--model`` flag can name: ``names()`` + the cold-start trainers + NCL."""
+        return sorted(set(self.names()) | set(_COLD) | set(_NCL))
 
 
 AVAILABLE_MODELS = _Registry()

@@ -981,6 +981,56 @@ def infonce(view1: torch.Tensor, view2: torch.Tensor, tau: float, b_cos: bool = 
     return loss, grad1, grad2
 
 
+# ---- NCL's whole-table contrast (table_nce.hip) ----------------------------------------------------------------------
+
+def table_nce_workspace_bytes(batch_max: int, n_rows: int, d: int) -> int:
+    return int(_lib.lib().crh_table_nce_workspace_bytes(int(batch_max), int(n_rows), int(d)))
+
+
+def table_nce_workspace(batch_max: int, n_rows: int, d: int, device) -> torch.Tensor:
+    """Private scratch of one crh_table_nce_f32 shape: linear in n_rows, nothing of size batch x n_rows."""
+    return torch.empty(max(table_nce_workspace_bytes(batch_max, n_rows, d), 1), dtype=torch.uint8, device=device)
+
+
+def table_nce(ctx: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, tau: float, n_dev=None,
+              batch_max: Optional[int] = None, scale: float = 1.0, accumulate: bool = False, grad_ctx=None, grad_table=None,
+              loss=None, workspace=None, want_grad_ctx: bool = True, want_grad_table: bool = True):
+    """sum_b (logsumexp_j <normalize(ctx[idx_b]), normalize(table[j])> / tau - the same at j = idx_b) and both input
+    gradients in one call (crh_table_nce_f32; reference model/NCL.py:68-94).  ctx / table: fp32 contiguous (n_rows, d),
+    d % 4 == 0 <= 256, possibly the same tensor; idx: int32 row ids in [0, n_rows) -- NOT checked --, duplicates allowed;
+    n_dev: optional device int32 batch size.  Returns (loss, grad_ctx, grad_table): grad_ctx = d loss / d ctx * scale at the
+    batch's rows only (a new buffer is zero elsewhere), grad_table = d loss / d table * scale at every row; ``accumulate``
+    adds into given buffers.  A gradient that is neither given nor wanted is not computed (None is returned for it;
+    without grad_table the column pass is skipped)."""
+    _need_cuda(ctx, table, idx, n_dev, grad_ctx, grad_table, loss, workspace)
+    dev = ctx.device
+    _check_2d_f32("table_nce", "ctx and table", ctx, table)
+    if ctx.shape != table.shape:
+        raise RuntimeError("table_nce: ctx and table differ in shape")
+    for t in (table, idx, n_dev, grad_ctx, grad_table, loss, workspace):
+        if t is not None and t.device != dev:
+            raise RuntimeError("table_nce: every tensor must be on ctx's device")
+    if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.dim() != 1:
+        raise RuntimeError("table_nce: row ids must be contiguous 1-D int32")
+    if n_dev is not None and (n_dev.dtype != torch.int32 or n_dev.numel() < 1):
+        raise RuntimeError("table_nce: n_dev must be a device int32 scalar")
+    loss = _loss_buffer("table_nce", loss, 1, dev)
+    n_rows, d = table.shape
+    if batch_max is None:
+        batch_max = idx.shape[0]
+    if idx.shape[0] < batch_max:
+        raise RuntimeError("table_nce: fewer row ids than batch_max")
+    grad_ctx = _grad_buffer("table_nce", "ctx's shape", grad_ctx, ctx, want_grad_ctx, False)
+    grad_table = _grad_buffer("table_nce", "the table's shape", grad_table, table, want_grad_table,
+                              n_dev is None and not accumulate and batch_max > 0)   # every table row is written
+    workspace = _workspace_arg("table_nce", workspace, table_nce_workspace, batch_max, n_rows, d, dev)
+    _lib.check(_lib.lib().crh_table_nce_f32(_lib.ptr(ctx), _lib.ptr(table), int(n_rows), _lib.ptr(idx), _lib.ptr(n_dev),
+                                            int(batch_max), int(d), float(tau), float(scale), int(bool(accumulate)),
+                                            _lib.ptr(grad_ctx), _lib.ptr(grad_table), _lib.ptr(loss), _lib.ptr(workspace),
+                                            workspace.numel(), _lib.current_stream()), "crh_table_nce_f32")
+    return loss, grad_ctx, grad_table
+
+
 # ---- CLCRec's contrastive loss (clcrec.hip) --------------------------------------------------------------------------
 
 def clcrec_max_neg() -> int:

@@ -742,6 +742,171 @@ class CLEngine(LGCNEngine):
                               step_scalars=step_scalars)
 
 
+def lloyd_kmeans(x: torch.Tensor, start: torch.Tensor, iters: int = 20):
+    """The prototype phase's clustering, the project's own (the reference calls faiss, which is not a dependency here):
+    Lloyd's k-means in plain torch on x's device.  ``start``: the k row indices the centroids start from.  ``iters`` rounds
+    of (assign every row to its nearest centroid by squared distance, the first index on a tie; every non-empty cluster's
+    centroid becomes the mean of its rows -- sums by index_put_(accumulate=True), deterministic --, an empty cluster keeps
+    its centroid), then the assignments once more.  Returns (centroids (k, d), assignment (N,) int64)."""
+    c = x[start].clone()
+    k = c.shape[0]
+    xx = (x * x).sum(1, keepdim=True)
+    ones = torch.ones(x.shape[0], dtype=x.dtype, device=x.device)
+
+    def assign(c):
+        return (xx - 2.0 * (x @ c.T) + (c * c).sum(1)[None, :]).argmin(1)
+
+    for _ in range(iters):
+        a = assign(c)
+        sums = torch.zeros_like(c).index_put_((a,), x, accumulate=True)
+        cnt = torch.zeros(k, dtype=x.dtype, device=x.device).index_put_((a,), ones, accumulate=True)
+        c = torch.where((cnt > 0)[:, None], sums / cnt.clamp_min(1.0)[:, None], c)
+    return c, assign(c)
+
+
+class NCLEngine(LGCNEngine):
+    """model/NCL.py:68-128 on the LightGCN engine's kernels.  The encoder is LightGCN's (x_k = A x_{k-1}, OUT = the mean of
+    x_0..x_L); the layer x_{2h} (h = hyper_layers) is kept as the context table CTX (h = 0: CTX is E itself).  One step:
+    BPR + the three-row L2 on OUT (g_f), then the structure contrast of both sides as two crh_table_nce_f32 calls --
+    ctx = CTX[:U], table = E[:U], ids = the batch's users, scale ssl_reg; the same on the item rows with ssl_reg * alpha --
+    which add into g_c (at layer 2h) and into the dense g_0 (at layer 0).  One Horner chain of L SpMMs, c = 1 / (L + 1):
+    D_L = c g_f + [L == 2h] g_c, D_k = c g_f + [k == 2h] g_c + A D_{k+1}, dE0 = c g_f + g_0 + A D_1, the optimiser in the last
+    SpMM's epilogue where built (CRH_LGCN_FUSED=0: gradient table + separate launch, the same bits).
+
+    Prototype phase: once ``e_step()`` has run (the trainer calls it at the start of every epoch >= proto_start) a step adds
+    proto_reg * batch_size * (InfoNCE(E[:U][users], centroids[cluster[users]]) + the same for the positives), through
+    ops.infonce on materialised gathers, the gradient of the first view scattered into g_0.  The clustering is
+    ``lloyd_kmeans`` from ``num_clusters`` rows drawn by a private CPU generator seeded with ``seed`` (users, then items).
+    ``self.loss`` = [bpr, l2, ssl_user, ssl_item, proto_user, proto_item], the contrast terms unscaled.  The step is
+    launched eagerly; data parallelism, row sharding and graph capture are not built for it."""
+
+    def __init__(self, user0, item0, rowptr, col, val, n_layers: int, lr: float, reg: float, device,
+                 optimizer: str = 'adam', tau: float = 0.2, ssl_reg: float = 1e-6, alpha: float = 1.0,
+                 hyper_layers: int = 1, proto_reg: float = 1e-7, num_clusters: int = 20, batch_size: int = 2048,
+                 seed: int = 0):
+        if int(hyper_layers) * 2 > int(n_layers):
+            raise ValueError("NCL expects emb_list[hyper_layers*2] with len(emb_list)==layers+1; "
+                             f"need hyper_layers*2 <= layers, got hyper_layers={hyper_layers}, layers={n_layers}.")
+        super().__init__(user0, item0, rowptr, col, val, n_layers, lr, reg, device, optimizer)
+        if self.d > 256:
+            raise RuntimeError("NCLEngine: embedding widths above 256 are not supported by the contrast kernels")
+        self.tau, self.ssl_reg, self.alpha, self.h = float(tau), float(ssl_reg), float(alpha), int(hyper_layers)
+        self.proto_reg, self.num_clusters, self.batch_size = float(proto_reg), int(num_clusters), int(batch_size)
+        self.loss = torch.zeros(6, dtype=torch.float32, device=self.device)
+        self.CTX = self.E if self.h == 0 else torch.empty_like(self.E)
+        self.G0 = torch.zeros_like(self.E)                               # gradient at layer 0 (dense: the whole tables)
+        self.GC = self.G0 if self.h == 0 else torch.zeros_like(self.E)   # gradient at layer 2h
+        self.proto = None                                                # (user_centroids, user_2cluster, item_..., item_...)
+        self._km_gen = torch.Generator().manual_seed(int(seed))          # private: the global stream is not touched
+        self._tn_ws = {}
+
+    def enable_data_parallel(self, dp: DPContext) -> None:
+        raise RuntimeError("NCL: data-parallel training is not built (single GPU only)")
+
+    def enable_row_sharding(self, dp: DPContext) -> None:
+        raise RuntimeError("NCL: row-sharded propagation is not built (single GPU only)")
+
+    def last_loss(self) -> float:
+        """The batch loss as the reference prints it (host sync)."""
+        l = self.loss.tolist()
+        return (l[0] + l[1] + self.ssl_reg * (l[2] + self.alpha * l[3])
+                + self.proto_reg * self.batch_size * (l[4] + l[5]))
+
+    def _propagate(self, out: torch.Tensor) -> None:
+        c = 1.0 / (self.L + 1)
+        x = self.E
+        for k in range(self.L):
+            last = k == self.L - 1
+            y = self.CTX if k + 1 == 2 * self.h else (None if last else self.X[k & 1])
+            self.k.spmm_csr(self.rowptr, self.col, self.val, x, y=y, acc_in=self.E if k == 0 else out, s_in=1.0,
+                            acc_out=out, s_out=c if last else 1.0, sched=self.sched)
+            x = y
+
+    def e_step(self) -> None:
+        """Cluster both tables (model/NCL.py:32-36 with ``lloyd_kmeans`` in faiss's place)."""
+        U, proto = self.user_num, []
+        for x in (self.E[:U], self.E[U:]):
+            if x.shape[0] < self.num_clusters:
+                raise ValueError(f"NCL: num_clusters={self.num_clusters} exceeds a table of {x.shape[0]} rows")
+            start = torch.randperm(x.shape[0], generator=self._km_gen)[: self.num_clusters].to(self.device)
+            proto.extend(lloyd_kmeans(x, start))
+        self.proto = tuple(proto)
+
+    def _table_nce(self, lo: int, hi: int, idx, scale: float, loss) -> None:
+        key = (int(idx.shape[0]), hi - lo)
+        if key not in self._tn_ws:
+            self._tn_ws[key] = self.k.table_nce_workspace(key[0], key[1], self.d, self.device)
+        self.k.table_nce(self.CTX[lo:hi], self.E[lo:hi], idx, self.tau, scale=scale, accumulate=True,
+                         grad_ctx=self.GC[lo:hi], grad_table=self.G0[lo:hi], loss=loss, workspace=self._tn_ws[key])
+
+    def _proto_nce(self, lo: int, hi: int, idx, centroids, node2cluster, loss) -> None:
+        il = idx.long()
+        v1 = self.E[lo:hi][il]                                           # duplicates kept, as the reference gathers them
+        _, g1, _ = self.k.infonce(v1, centroids[node2cluster[il]], self.tau, True,
+                                  scale=self.proto_reg * self.batch_size, want_grad2=False, loss=loss)
+        self.G0[lo:hi].index_put_((il,), g1, accumulate=True)           # deterministic (index_add_ uses atomics)
+
+    def step(self, user_idx, pos_idx, neg_idx, plan: Optional[torch.Tensor] = None, loss_out=None,
+             step_scalars=None) -> None:
+        """One optimiser step; ``loss_out``: optional 6-float device buffer (see the class docstring)."""
+        U, N = self.user_num, self.E.shape[0]
+        loss = self.loss if loss_out is None else loss_out
+        g = self.dOUT
+        g.zero_()
+        self.G0.zero_()
+        if self.GC is not self.G0:
+            self.GC.zero_()
+        self._propagate(self.OUT)
+        self.k.bpr_fwd_bwd(self.OUT[:U], self.OUT[U:], self.OUT[U:], user_idx, pos_idx, neg_idx, self.reg,
+                           g[:U], g[U:], g[U:], loss, plan=plan, workspace=self._ws(user_idx.shape[0]))
+        self._table_nce(0, U, user_idx, self.ssl_reg, loss[2:3])
+        self._table_nce(U, N, pos_idx, self.ssl_reg * self.alpha, loss[3:4])
+        if self.proto is not None:
+            uc, u2c, ic, i2c = self.proto
+            self._proto_nce(0, U, user_idx, uc, u2c, loss[4:5])
+            self._proto_nce(U, N, pos_idx, ic, i2c, loss[5:6])
+        else:
+            loss[4:6].zero_()
+        self._backward_ncl(step_scalars)
+
+    def _backward_ncl(self, step_scalars) -> None:
+        """dE0 from g_f (= dOUT), g_c and g_0 by L SpMMs, then the optimiser step."""
+        L, c, g, gc, g0, k2 = self.L, 1.0 / (self.L + 1), self.dOUT, self.GC, self.G0, 2 * self.h
+        self.step_count += 1
+        # D_L = c g_f (+ g_c): kept as (g_f, pending scale c) unless g_c has to be added to it
+        if self.h > 0 and k2 == L:
+            gc.add_(g, alpha=c)
+            x, lazy = gc, False
+        else:
+            x, lazy = g, True
+        for k in range(L - 1, 0, -1):                                    # D_k = c g_f + [k == 2h] g_c + A D_{k+1}
+            dst = self.X[k & 1]
+            self.k.spmm_csr(self.rowptr, self.col, self.val, x, y=None, acc_in=g, s_in=1.0 if lazy else c, acc_out=dst,
+                            s_out=c if lazy else 1.0, sched=self.sched)
+            lazy = False
+            if self.h > 0 and k == k2:
+                dst.add_(gc)
+            x = dst
+        # dE0 = (c g_f + g_0) + A D_1; with D_1 still (g_f, c) -- L = 1, c = 1/2 -- as ((c g_f + g_0) * 2 + A g_f) * c, exact
+        g0.add_(g, alpha=c)
+        s_in, s_out = (1.0 / c, c) if lazy else (1.0, 1.0)
+        self._dout_clean = False
+        keep = self.G if self.keep_grad else None
+        if self.fuse_adam and self.optimizer == 'sgd':
+            self.k.spmm_csr_sgd(self.rowptr, self.col, self.val, x, g0, s_in, keep, s_out, self.sched, self.E, self.lr)
+        elif self.fuse_adam:
+            self.k.spmm_csr_adam(self.rowptr, self.col, self.val, x, g0, s_in, keep, s_out, self.sched, self.E, self.M,
+                                 self.V, self.step_count, lr=self.lr, step_scalars=step_scalars)
+        else:
+            self.k.spmm_csr(self.rowptr, self.col, self.val, x, y=None, acc_in=g0, s_in=s_in, acc_out=self.G, s_out=s_out,
+                            sched=self.sched)
+            if self.optimizer == 'sgd':
+                self.k.sgd_dense(self.E, self.G, self.lr, zero_grad=False)
+            else:
+                self.k.adam_dense(self.E, self.G, self.M, self.V, self.step_count, lr=self.lr, zero_grad=False,
+                                  step_scalars=step_scalars)
+
+
 class EpochRunner:
     """One epoch of optimiser steps as a replayable hipGraph.
 

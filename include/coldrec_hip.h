@@ -534,6 +534,35 @@ int crh_infonce_f32(const float* view1, const int32_t* rows1, const float* view2
                     float* grad1, float* grad2, float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * The structure contrast of NCL, forward and backward in one call (reference model/NCL.py:68-94, ssl_layer_loss, called
+ * twice per batch): a batch of rows against EVERY row of a table, the positive being a column of that table:
+ *     X_b = F.normalize(ctx[idx_b]);  T_j = F.normalize(table[j]);  S_bj = <X_b, T_j> / tau
+ *     loss = sum_b (logsumexp_{j < n_rows} S_bj - S_b,idx_b)         (a SUM over the records; the positive is inside the lse)
+ * without the B x n_rows matrix: infonce's two streaming passes made rectangular (v_mfma_f32_32x32x2_f32, online max / sum in
+ * the log2 domain, so the result stays finite where the reference's exp(s / tau).sum() overflows); no atomics, every
+ * reduction in a fixed order (two identical calls give identical bits).
+ *   ctx / table    fp32 row-major n_rows x d (d % 4 == 0, 4 <= d <= 256); may be the same pointer
+ *   idx            int32 row ids of the batch, in [0, n_rows) (a precondition, NOT checked); duplicates allowed
+ *   n_dev          device int32 B (clamped to [0, batch_max]), NULL = batch_max; grids are sized from batch_max
+ *   grad_ctx       d loss/d ctx * scale at the batch's rows only; a row that appears c times gets the sum of its c records
+ *                  (summed in ascending record order).  accumulate != 0 adds into the row, else it is overwritten
+ *   grad_table     d loss/d table * scale at ALL n_rows rows (every row has a softmax term); accumulate as above
+ *                  Either may be NULL (not computed: a NULL grad_table skips the column pass); at least one of grad_ctx,
+ *                  grad_table, loss_out must be given.  The normalize backward clamps the norm at 1e-12 as torch does
+ *   loss_out       device scalar (the unscaled sum), NULL = not written; B = 0 gives 0 and touches no gradient row
+ *   workspace      crh_table_nce_workspace_bytes(batch_max, n_rows, d) bytes, 256-byte aligned: the zero-padded normalised
+ *                  table (ceil32(n_rows) x ceil32(d)), the batch's copy and per-record gradients, and the split partials
+ *                  of the pass that needs more -- crh_table_nce_splits(batch_max, n_rows, 0) x ceil32(batch_max) rows for
+ *                  the row pass, crh_table_nce_splits(batch_max, n_rows, 1) x ceil32(n_rows) rows for the column pass (one
+ *                  split once the table fills the grid): linear in n_rows, nothing of size B x n_rows
+ */
+size_t crh_table_nce_workspace_bytes(int64_t batch_max, int64_t n_rows, int d);
+int crh_table_nce_splits(int64_t batch_max, int64_t n_rows, int col);
+int crh_table_nce_f32(const float* ctx, const float* table, int64_t n_rows, const int32_t* idx, const int32_t* n_dev,
+                      int64_t batch_max, int d, float tau, float scale, int accumulate, float* grad_ctx, float* grad_table,
+                      float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The contrastive loss of CLCRec (reference model/CLCRec.py:117-153), forward and backward in one call.  B records, each
  * the user users[b] and 1 + G items items[b (1+G) + g] (g = 0 the positive); feat holds the content encoder's output once
  * per DISTINCT item of the batch: slot[r] = the feat row of flat row r, slot_item[s] = the item id feat row s encodes.
