@@ -206,6 +206,70 @@ constexpr bool DMA_EVENT_TAIL64 = false;
 #else
 [[maybe_unused]] constexpr bool DMA_EVENT_MASK8_SPLIT = false;
 #endif
+// Round 18, the FULL-LIST form of the 16x16 event.  While the kernel's prologue copies the seeds, each wave works out one wave-uniform
+// flag: every live user slot of the wave holds K' entries.  Lists only grow, so the flag holds for the launch; in the screened route
+// it is set by every seeded call (the prefix stage ranks a masked item at -1e9 under its own id, so a seed list is full whenever the
+// prefix holds K' rows: its tail may be masked, its threshold -inf).  With the flag set the event takes dma_candidate_full below;
+// with it clear (an unseeded call, a seed list that is short all the same, K' read at run time) the event of round 17 runs.
+// Two steps, each with a switch that builds the form before it (variant build, tools/ab_lib.sh):
+//   -DCRH_DMA_EVENT_NO_FULL      no flag and no second form at all (the parent's kernels)
+//   -DCRH_DMA_EVENT_NO_STRAIGHT  no straight-line dispatch: a hit block with one hit lane and one row walks the two loops as well
+// (Measured and not kept, round 18: the full-list form WITHOUT the tail pre-test -- "cannot enter" read off the placing compare as
+// p == K', taken in front of the filter, a second compare only for a masked candidate.  It drops two v_readlane and a scalar
+// crh_better per candidate and ran SLOWER on the same box: +0.96 ms per step at the headline on top of the full-list form alone,
+// +0.22 ms on top of both steps that ship, +0.1 / +0.6 ms without a bitmap (inside the spreads); HISTORY.md,
+// profiles/r18_event_steps_ab.log.  Why is not measured.)
+#ifdef CRH_DMA_EVENT_NO_FULL
+constexpr bool DMA_EVENT_FULL = false;
+#else
+constexpr bool DMA_EVENT_FULL = DMA_EVENT_KC != 0 && DMA_SCREEN_ONE_TRIP;
+#endif
+#ifdef CRH_DMA_EVENT_NO_STRAIGHT
+constexpr bool DMA_EVENT_STRAIGHT = false;
+#else
+constexpr bool DMA_EVENT_STRAIGHT = true;
+#endif
+// dma_candidate<true, true> for a list that is full (K = the compile-time K'): lane l < K holds entry l, an item; there is no fill to
+// read, test or write, and the user's new K-th entry is the old (K-1)-th or the candidate.  The order -- "cannot enter", filter,
+// insert -- and what each outcome writes are dma_candidate's with n = K.
+template <int K>
+__device__ __forceinline__ void dma_candidate_full(float sc, int gi, bool bm_masked, int ul, int64_t slot, float* ls, int* li,
+                                                   const ScoreArgs& a, int lane, const unsigned* rfilter, bool mine, float& tau_reg) {
+    static_assert(K >= 2 && K < 64, "one entry per lane");
+    constexpr unsigned long long LIST = (1ull << K) - 1ull;     // lanes >= K read what lies behind the list (LANE_READ of dma_candidate)
+    float* lsu = ls + ul * K;
+    int* liu = li + ul * K;
+    // one batch of LDS reads: entry `lane`, filter word
+    const unsigned hsh = rated_hash192(gi);
+    const float es = lsu[lane];
+    const int ei = liu[lane];
+    const unsigned fw_raw = a.rated_rowptr ? rfilter[ul * DMA_FW + (hsh >> 5)] : 0u;
+    const float ks = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, es), K - 1));
+    const int ki = __builtin_amdgcn_readlane(ei, K - 1);
+    if (!crh_better(fmaxf(sc, CRH_MASKED_SCORE), gi, ks, ki)) return;   // cannot enter
+    bool masked = bm_masked;
+    if (!masked && ((__builtin_amdgcn_readfirstlane(fw_raw) >> (hsh & 31)) & 1u)) {
+        const int64_t lo = a.rated_rowptr[slot], hi = a.rated_rowptr[slot + 1];
+        masked = wave_is_masked_at(gi, lo, hi, a.rated_col, nullptr, lane);
+        __builtin_amdgcn_s_waitcnt(0x0f70);                     // (the search's loads land inside the rare branch: see dma_candidate)
+    }
+    if (masked) sc = CRH_MASKED_SCORE;
+    const int p = __popcll(__ballot(crh_better(es, ei, sc, gi)) & LIST);
+    if (p < K) {
+        if (lane >= p && lane + 1 < K) {
+            lsu[lane + 1] = es;
+            liu[lane + 1] = ei;
+        }
+        if (lane == 0) {
+            lsu[p] = sc;
+            liu[p] = gi;
+        }
+        const float prev = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, es), K - 2));
+        const float kth = (p == K - 1) ? sc : prev;
+        if (mine) tau_reg = kth >= CRH_MASKED_SCORE ? kth : CRH_NEG_INF;
+    }
+}
+
 // CM (compacted stream): row q of the stream is the q-th unmasked item; idv = the ids of this tile's rows (lane l: row l & 31),
 // read from LDS once per event by the caller.  item0 and split_end stay row numbers; there are no masked rows (tb = 0).
 template <bool ONE_TRIP, bool CM>
@@ -295,10 +359,13 @@ __device__ __forceinline__ float pick8u(const f32x8& v, int r) {
 }
 // KC = the compile-time K' (0: K is the launch's); rows_left = the rows of the selected tile inside the cut, 1 .. 32, and gi0 = the id
 // of its row 0 (stream in id order), both worked out once per event by the caller.
-template <bool CM, int KC>
+// FULL = the wave's lists are all full (round 18): the candidates take dma_candidate_full, and a block with ONE hit lane that holds ONE
+// row -- every event of the sparse part of the stream -- runs its candidate straight, with neither loop's header, back edge and zero test.
+template <bool CM, int KC, bool FULL = false>
 __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& tau_reg, float* ls, int* li, int* cnt, int Krt, int ucol0,
                                                      int64_t slot0, const ScoreArgs& a, int64_t item0, int64_t split_end, int rows_left,
                                                      int gi0, int lane, unsigned tb, const unsigned* rfilter, int idv) {
+    static_assert(!FULL || KC != 0, "the full-list form is compiled for K'");
     const int K = KC ? KC : Krt;
     unsigned cm = gt_mask8(acc, tau_reg);
     unsigned m8 = 0u;                                             // masked rows of this lane, as in the 32x32 form
@@ -309,34 +376,52 @@ __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& ta
     }
     const unsigned bm = cm & m8;
     unsigned long long lanes = __ballot(cm != 0u);
+    // row bit r of hit lane L (its row mask cmL's lowest bit, or its only one); bmL = the lane's masked rows
+    auto candidate = [&](int L, int r, unsigned bmL) __attribute__((always_inline)) {
+        const int jl = L & 15, g = L >> 4;
+        const int64_t slot = slot0 + jl;
+        const int ul = ucol0 + jl;
+        const int row = 16 * (r >> 2) + 4 * g + (r & 3);
+        const int64_t il = item0 + row;
+        // clamped duplicate rows of the tail tile
+        if constexpr (DMA_EVENT_TAIL64) {
+            if (il >= split_end) return;
+        } else {
+            if (row >= rows_left) return;
+        }
+        const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pick8u(acc, r)), L));
+        int gi;
+        if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, row);
+        else if constexpr (DMA_EVENT_TAIL64) gi = (int)(a.item_base + il);
+        else gi = gi0 + row;
+        if constexpr (FULL)
+            dma_candidate_full<KC>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, a, lane, rfilter, (lane & 15) == jl, tau_reg);
+        else
+            dma_candidate<DMA_SCREEN_ONE_TRIP, true>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg);
+    };
+    if constexpr (FULL && DMA_EVENT_STRAIGHT && !DMA_EVENT_SLOT_TEST) {
+        // (one s_bcnt1 and a compare.  Not `lanes & (lanes - 1)`: under a bitmap the masked rows may have left no hit lane at all)
+        if (__popcll(lanes) == 1) {
+            const int L = __builtin_ctzll(lanes);
+            const unsigned cmL = __builtin_amdgcn_readlane(cm, L);
+            if ((cmL & (cmL - 1)) == 0u) {
+                candidate(L, __builtin_ctz(cmL), __builtin_amdgcn_readlane(bm, L));
+                return;
+            }
+        }
+    }
     while (lanes) {
         const int L = __builtin_ctzll(lanes);
         lanes &= lanes - 1;
         unsigned cmL = __builtin_amdgcn_readlane(cm, L);
         const unsigned bmL = __builtin_amdgcn_readlane(bm, L);
-        const int jl = L & 15, g = L >> 4;
-        const int64_t slot = slot0 + jl;
         if constexpr (DMA_EVENT_SLOT_TEST) {
-            if (slot >= a.n_users) continue;
+            if (slot0 + (L & 15) >= a.n_users) continue;
         }
-        const int ul = ucol0 + jl;
         while (cmL) {
             const int r = __builtin_ctz(cmL);
             cmL &= cmL - 1;
-            const int row = 16 * (r >> 2) + 4 * g + (r & 3);
-            const int64_t il = item0 + row;
-            // clamped duplicate rows of the tail tile
-            if constexpr (DMA_EVENT_TAIL64) {
-                if (il >= split_end) continue;
-            } else {
-                if (row >= rows_left) continue;
-            }
-            const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pick8u(acc, r)), L));
-            int gi;
-            if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, row);
-            else if constexpr (DMA_EVENT_TAIL64) gi = (int)(a.item_base + il);
-            else gi = gi0 + row;
-            dma_candidate<DMA_SCREEN_ONE_TRIP, true>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg);
+            candidate(L, r, bmL);
         }
     }
 }
@@ -482,6 +567,11 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     int* li = reinterpret_cast<int*>(ls + UPW * K);      // [UPW][K]
     int* cnt = li + UPW * K;                            // [UPW]
     for (int j = lane; j < UPW; j += 64) cnt[j] = 0;
+    // M16, round 18: every live slot of this wave holds K entries (wave-uniform; lists only grow, so it holds for the launch).  The loop
+    // below ends at the first padding slot: padding slots stay empty and do not count -- their thresholds are +inf, no candidate is
+    // ever theirs.  (A dead wave copies the lists of the call's last group and takes no event at all.)
+    constexpr bool FULL_FORM = M16 && KC != 0 && DMA_EVENT_FULL;
+    [[maybe_unused]] int lists_full = FULL_FORM && a.seed_score != nullptr ? 1 : 0;
     if (a.seed_score) {
         // seeded lists: copy each slot's prefix top-k into LDS; its fill = the entries before the padding
         for (int j = 0; j < UPW; ++j) {
@@ -499,6 +589,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 n += __popcll(__ballot(gi != CRH_PAD_IDX));
             }
             if (lane == 0) cnt[j] = n;
+            if constexpr (FULL_FORM) lists_full &= n == K ? 1 : 0;
         }
     }
     // ---- membership filters of the rated lists (192 bits per user, ids of this split's range only)
@@ -707,6 +798,20 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 #ifdef CRH_PROFILE
     unsigned long long ev_ticks = 0, ev_count = 0;       // CRH_SCORE_TIMING
 #endif
+    // M16: the event of user block u at tile ts, in the form the wave's flag selects -- one scalar branch per event
+    auto event16 = [&](const AccT& v, float& tau_u, int u, int64_t ts, int rows_left, int gi0, unsigned tb, int idv) __attribute__((always_inline)) {
+        if constexpr (M16) {
+            if constexpr (FULL_FORM) {
+                if (lists_full) {
+                    tile_slow_path_dma16<CM, KC, true>(v, tau_u, ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, rows_left, gi0,
+                                                       lane, tb, rfilter, idv);
+                    return;
+                }
+            }
+            tile_slow_path_dma16<CM, KC>(v, tau_u, ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, rows_left, gi0, lane, tb,
+                                         rfilter, idv);
+        }
+    };
     // body j: MFMAs of tile j (ring slot s_cur) into accumulator set P, threshold test of tile j-1 out of set 1-P;
     // s_nxt = slot of tile j+1, s_fill = slot of tile j + PF (barrier form: the slot tile j-1 left)
     auto body = [&](auto Pc, int j, int s_cur, int s_nxt, int s_fill) __attribute__((always_inline)) {
@@ -884,8 +989,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                         // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
                         if ((M16 && !DMA_EVENT_REBALLOT) ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull) {
                             if constexpr (M16)
-                                tile_slow_path_dma16<CM, KC>(acc[Q][u], tau[u], ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end,
-                                                             rows_left, gi0, lane, tb, rfilter, idv);
+                                event16(acc[Q][u], tau[u], u, ts, rows_left, gi0, tb, idv);
                             else
                                 tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32, CM>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a,
                                                                                             ts << 5, split_end, lane, tb, rfilter, idv);
@@ -1050,8 +1154,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                         // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
                         if (!DMA_EVENT_REBALLOT ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull)
                             if constexpr (M16)       // (the other forms never call this body, but they parse it)
-                                tile_slow_path_dma16<CM, KC>(acc[Q][u], tau[u], ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end,
-                                                             rows_left, gi0, lane, tb, rfilter, idv);
+                                event16(acc[Q][u], tau[u], u, ts, rows_left, gi0, tb, idv);
                     // the list stores of the inserts are drained HERE (as in `body`); the fragment reads in flight land with them
                     __builtin_amdgcn_s_waitcnt(0xc07f);
 #ifdef CRH_PROFILE
