@@ -72,4 +72,7 @@ def model_specific_param(model_name, parser, available_models):
                             help='1: weight the two distillation losses by the positive item\'s frequency')
         parser.add_argument('--freq_coef_M', type=float, default=4, help='Cap of the frequency weights: tanh(M)')
         parser.add_argument('--aldi_hidden', type=int, default=200, help='Hidden width of the two student towers')
+    if model_name == 'GAR':       # config/model_param.py:94-96
+        parser.add_argument('--alpha', type=float, default=0.05, help='Weight of the similarity term in the generator loss')
+        parser.add_argument('--beta', type=float, default=0.1, help='Weight of the sampled negative in the recommender loss')
     return parser

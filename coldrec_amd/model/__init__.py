@@ -6,7 +6,7 @@ subclasses ``BaseColdStartTrainer`` can be registered with ``register(name, cls)
 
 ``keys()`` lists the core trainers plus whatever ``register()`` added.  The contrastive trainers (SimGCL, XSimGCL)
 resolve by name through ``[]``, ``.get()`` and ``in`` as well, from a cache of their own: resolving one never changes
-what ``keys()`` reports.  The cold-start trainers CLCRec, CCFCRec and ALDI resolve the same way from a third table and are not part of
+what ``keys()`` reports.  The cold-start trainers CLCRec, CCFCRec, ALDI and GAR resolve the same way from a third table and are not part of
 ``names()`` either (both listings are pinned); NCL, the third graph-contrastive backbone, has a fourth table for the same
 reason.  ``resolvable()`` is everything a ``--model`` flag can name.
 """
@@ -14,7 +14,8 @@ import importlib
 
 _BUILTIN = {'MF': ('.MF', 'MF'), 'LightGCN': ('.LightGCN', 'LightGCN'), 'DropoutNet': ('.DropoutNet', 'DropoutNet')}
 _CONTRASTIVE = {'SimGCL': ('.SimGCL', 'SimGCL'), 'XSimGCL': ('.XSimGCL', 'XSimGCL')}
-_COLD = {'CLCRec': ('.CLCRec', 'CLCRec'), 'CCFCRec': ('.CCFCRec', 'CCFCRec'), 'ALDI': ('.ALDI', 'ALDI')}
+_COLD = {'CLCRec': ('.CLCRec', 'CLCRec'), 'CCFCRec': ('.CCFCRec', 'CCFCRec'), 'ALDI': ('.ALDI', 'ALDI'),
+         'GAR': ('.GAR', 'GAR')}
 _NCL = {'NCL': ('.NCL', 'NCL')}
 _contrastive_cache = {}
 _cold_cache = {}

@@ -1313,6 +1313,98 @@ def aldi(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor
     return loss, grad_user, grad_pos, grad_neg
 
 
+# ---- GAR's loss (gar.hip) --------------------------------------------------------------------------------------------
+
+def gar_chunk_rows() -> int:
+    return int(_lib.lib().crh_gar_chunk_rows())
+
+
+def gar_workspace_bytes(batch: int, d: int, n_items: int, n_users: int) -> int:
+    return int(_lib.lib().crh_gar_workspace_bytes(int(batch), int(d), int(n_items), int(n_users)))
+
+
+def gar_workspace(batch: int, d: int, n_items: int, n_users: int, device) -> torch.Tensor:
+    return torch.empty(max(gar_workspace_bytes(batch, d, n_items, n_users), 1), dtype=torch.uint8, device=device)
+
+
+def gar_plan(users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_users: Optional[int] = None,
+             n_items: Optional[int] = None, id_range=None, chunk: Optional[int] = None) -> dict:
+    """The index side of one crh_gar_f32 step.  users, pos, neg (B,): integer tensors on one device.  Returns int32 tensors:
+    users, pos, neg and the inverse indices -- the records grouped by user (user_ids, user_ptr, user_occ; a stable sort,
+    so ascending inside a user) and cut into chunks of crh_gar_chunk_rows() (user_chunk_ptr, user_chunk_own), and the same
+    over the 2B item occurrences (pos, then neg).  id_range = ((user min, user max), (item min, item max)) when the caller
+    knows them (a trainer that sampled the ids on the host); measured here otherwise, which waits for the device.  With
+    n_users / n_items given, ids outside the tables raise instead of reaching the kernel.  ``chunk`` is the library's
+    unless given (the grouping is plain tensor code and runs on any device)."""
+    B = users.shape[0] if users.dim() == 1 else 0
+    if B < 1 or pos.shape != (B,) or neg.shape != (B,):
+        raise RuntimeError("gar_plan: users, pos, neg must be (B,) with B >= 1")
+    if any(t.dtype.is_floating_point or t.device != users.device for t in (users, pos, neg)):
+        raise RuntimeError("gar_plan: users, pos, neg must be integer tensors on one device")
+    ulong = users.long()
+    both = torch.cat([pos.long(), neg.long()])
+    if id_range is None:
+        id_range = ((int(ulong.min()), int(ulong.max())), (int(both.min()), int(both.max())))
+    user_range, item_range = (tuple(int(x) for x in r) for r in id_range)
+    if n_users is not None and (user_range[0] < 0 or user_range[1] >= n_users):
+        raise RuntimeError("gar_plan: user id outside the user table")
+    if n_items is not None and (item_range[0] < 0 or item_range[1] >= n_items):
+        raise RuntimeError("gar_plan: item id outside the item table")
+    if chunk is None:
+        chunk = gar_chunk_rows()
+    item_ids, item_occ, item_ptr, item_chunk_ptr, item_chunk_own, _ = _owner_chunks(both, chunk)
+    user_ids, user_occ, user_ptr, user_chunk_ptr, user_chunk_own, _ = _owner_chunks(ulong, chunk)
+    c = lambda t: t.to(torch.int32).contiguous()
+    return dict(batch=B, n_items=int(item_ids.shape[0]), n_users=int(user_ids.shape[0]),
+                n_item_chunks=int(item_chunk_own.shape[0]), n_user_chunks=int(user_chunk_own.shape[0]),
+                user_range=user_range, item_range=item_range, users=c(ulong), pos=c(both[:B]), neg=c(both[B:]),
+                item_ids=c(item_ids), item_ptr=c(item_ptr), item_occ=c(item_occ), item_chunk_ptr=c(item_chunk_ptr),
+                item_chunk_own=c(item_chunk_own), user_ids=c(user_ids), user_ptr=c(user_ptr), user_occ=c(user_occ),
+                user_chunk_ptr=c(user_chunk_ptr), user_chunk_own=c(user_chunk_own))
+
+
+def gar(user_table: torch.Tensor, item_table: torch.Tensor, gen: torch.Tensor, plan: dict, alpha: float, beta: float,
+        reg: float, cold_user: bool = False, scale: float = 1.0, want_user: bool = True, want_item: bool = True,
+        want_gen: bool = True, grad_user=None, grad_item=None, grad_gen=None, loss=None, workspace=None):
+    """GAR's loss and its three gradients in one call (crh_gar_f32).  user_table (nu, d), item_table (ni, d): the trained
+    tables; gen (B, d) = the generator's output for the records (the positives' content, or the users' when cold_user);
+    fp32 contiguous, d % 4 == 0 <= 256; plan: ``gar_plan``.  Returns (loss4 = [L_gen, L_rec, R, total], grad_user,
+    grad_item, grad_gen); gradients are d total / d . * scale, the tables' zero at rows the batch does not touch; one
+    that is neither given nor wanted is not computed (None)."""
+    _need_cuda(user_table, item_table, gen, plan["users"], grad_user, grad_item, grad_gen, loss, workspace)
+    dev = user_table.device
+    _check_2d_f32("gar", "tables and the generator's output", user_table, item_table, gen)
+    d = user_table.shape[1]
+    if d % 4 != 0 or d < 4 or d > 256:
+        raise RuntimeError(f"gar: width {d} must be a multiple of 4 in [4, 256]")
+    B = plan["batch"]
+    if item_table.shape[1] != d or gen.shape != (B, d):
+        raise RuntimeError("gar: the generator's output must be (B, d) of the tables' width, one row per record of the plan")
+    for t in (item_table, gen, plan["users"], grad_user, grad_item, grad_gen, loss, workspace):
+        if t is not None and t.device != dev:
+            raise RuntimeError("gar: every tensor must be on the tables' device")
+    (u_lo, u_hi), (i_lo, i_hi) = plan["user_range"], plan["item_range"]
+    if u_lo < 0 or u_hi >= user_table.shape[0] or i_lo < 0 or i_hi >= item_table.shape[0]:
+        raise RuntimeError("gar: ids lie outside the tables")
+
+    grad_user = _grad_buffer("gar", "the tables' and the generator output's shapes", grad_user, user_table, want_user, False)
+    grad_item = _grad_buffer("gar", "the tables' and the generator output's shapes", grad_item, item_table, want_item, False)
+    grad_gen = _grad_buffer("gar", "the tables' and the generator output's shapes", grad_gen, gen, want_gen, True)
+    loss = _loss_buffer("gar", loss, 4, dev)
+    workspace = _workspace_arg("gar", workspace, gar_workspace, B, d, plan["n_items"], plan["n_users"], dev)
+    p = plan
+    _lib.check(_lib.lib().crh_gar_f32(
+        _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]), _lib.ptr(gen),
+        _lib.ptr(p["users"]), _lib.ptr(p["pos"]), _lib.ptr(p["neg"]), int(u_lo), int(u_hi), int(i_lo), int(i_hi),
+        _lib.ptr(p["item_ids"]), _lib.ptr(p["item_ptr"]), _lib.ptr(p["item_occ"]), _lib.ptr(p["item_chunk_ptr"]),
+        _lib.ptr(p["item_chunk_own"]), int(p["n_items"]), int(p["n_item_chunks"]), _lib.ptr(p["user_ids"]),
+        _lib.ptr(p["user_ptr"]), _lib.ptr(p["user_occ"]), _lib.ptr(p["user_chunk_ptr"]), _lib.ptr(p["user_chunk_own"]),
+        int(p["n_users"]), int(p["n_user_chunks"]), int(B), int(d), int(bool(cold_user)), float(alpha), float(beta),
+        float(reg), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item), _lib.ptr(grad_gen), _lib.ptr(loss),
+        _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_gar_f32")
+    return loss, grad_user, grad_item, grad_gen
+
+
 # ---- SimGCL / XSimGCL layer perturbation (perturb.hip) ---------------------------------------------------------------
 
 def _perturb_checks(what: str, y: torch.Tensor, *others) -> None:

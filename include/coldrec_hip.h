@@ -671,6 +671,48 @@ int crh_aldi_f32(const float* user_table, int64_t user_rows, const float* item_t
                  size_t workspace_bytes, void* stream);
 
 /*
+ * The loss of GAR (reference model/GAR.py:24-31, util/utils.py:25-48), forward and backward in one call.  B records, each
+ * the user users[b], the positive pos[b] and the negative neg[b]; Ur = U[users[b]], Pr = V[pos[b]], Nr = V[neg[b]] are rows
+ * of the two trained tables; gen (B, d) = the generator's output, one row per record.  With bpr(x) = -log(1e-5 +
+ * sigmoid(x)), T = Pr when cold_user == 0 and Ur otherwise, and every mean over the B records:
+ *     x1 = <Ur, G> - <Ur, Pr> (cold_user == 0)   x1 = <Pr, G> - <Pr, Ur> (cold_user != 0)
+ *     x2 = <Ur, Pr> - <Ur, G>                    x3 = <Ur, Pr> - <Ur, Nr>
+ *     L_gen = (1 - alpha) mean bpr(x1) + alpha sum |T - G|^2 / (B d)
+ *     L_rec = (1 - beta) mean bpr(x2) + beta mean bpr(x3)
+ *     R     = reg (|Ur|_F + |Pr|_F + |Nr|_F + |G|_F) / B       (Frobenius norms of the gathered (B, d) blocks: a duplicate
+ *                                                              id counts once per occurrence; a block of zero norm
+ *                                                              contributes zero gradient)
+ *     total = L_gen + L_rec + R
+ *   user_rows, item_rows  the tables' row counts; user_min .. item_max = the smallest and largest id of users and of
+ *                  pos + neg, as the caller states them (ops.gar_plan measures them): a range that leaves its table is an
+ *                  argument error
+ *   inverse indices (ops.gar_plan builds them): user_ids[n_users] = the distinct users, user_occ = the records grouped by
+ *                  user (a stable sort: ascending inside a user), user_ptr[n_users + 1] their offsets; every user's records
+ *                  are cut into chunks of crh_gar_chunk_rows(): user_chunk_ptr[n_users + 1] = offsets into the chunk list,
+ *                  user_chunk_own[n_user_chunks] = each chunk's index into user_ids.  The item_* arrays are the same over
+ *                  the 2B occurrences o (o < B: pos[o], else neg[o - B]); offsets and occurrences are read as unsigned
+ *   grad_user, grad_item  d total / d table * scale, written at the touched rows only (the caller zeroes the rest); an
+ *                  item that is a positive and a negative, in one record or in two, receives both contributions;
+ *   grad_gen       (B, d), every row.  Any may be NULL: it is not computed and the others keep their bits
+ *   loss_out       4 device floats: L_gen, L_rec, R, total (not scaled); NULL = not written
+ *   workspace      crh_gar_workspace_bytes(batch, d, n_items, n_users) bytes (0 = a refused shape), 256-byte aligned
+ * d % 4 == 0, 4 <= d <= 256; 1 <= batch < 2^31; tables, gen and gradients 16-byte aligned.  No atomics, every sum in an
+ * order fixed by the shape: two identical calls give identical bits.  One lane group per record, one workgroup for the
+ * loss and the four norms, then one wave per chunk of an owner's occurrences and the chunks' partial sums added in chunk
+ * order.
+ */
+int crh_gar_chunk_rows(void);
+size_t crh_gar_workspace_bytes(int64_t batch, int d, int64_t n_items, int64_t n_users);
+int crh_gar_f32(const float* user_table, int64_t user_rows, const float* item_table, int64_t item_rows, const float* gen,
+                const int32_t* users, const int32_t* pos, const int32_t* neg, int user_min, int user_max, int item_min,
+                int item_max, const int32_t* item_ids, const int32_t* item_ptr, const int32_t* item_occ,
+                const int32_t* item_chunk_ptr, const int32_t* item_chunk_own, int64_t n_items, int64_t n_item_chunks,
+                const int32_t* user_ids, const int32_t* user_ptr, const int32_t* user_occ, const int32_t* user_chunk_ptr,
+                const int32_t* user_chunk_own, int64_t n_users, int64_t n_user_chunks, int64_t batch, int d, int cold_user,
+                float alpha, float beta, float reg, float scale, float* grad_user, float* grad_item, float* grad_gen,
+                float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The layer perturbation of SimGCL / XSimGCL (model/SimGCL.py:106-108), in place on one (n_rows, d) fp32 layer output
  * of the propagation, d % 4 == 0, 4 <= d <= 256, every pointer 16-byte aligned.  Per row, r = the row's d uniforms:
  *     nrm = max(sqrt(sum r^2), 1e-12)                       (F.normalize's clamp)
