@@ -120,6 +120,9 @@ SIGNATURES = {
     "crh_gar_workspace_bytes": (_sz, [_i64, _i32, _i64, _i64]),
     "crh_gar_f32": (_i32, [_vp, _i64, _vp, _i64] + [_vp] * 4 + [_i32] * 4 + [_vp] * 5 + [_i64, _i64] + [_vp] * 5 +
                            [_i64, _i64, _i64, _i32, _i32] + [_f32] * 4 + [_vp] * 5 + [_sz, _vp]),
+    "crh_ngcf_workspace_bytes": (_sz, [_i64, _i32]),
+    "crh_ngcf_layer_fwd_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _f32, _vp, _f32, _vp]),
+    "crh_ngcf_layer_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "crh_noise_uniform_f32": (_i32, [_vp, _i64, _i32, ctypes.c_uint64, _vp, _i64, _vp]),
     "crh_perturb_rows_f32": (_i32, [_vp, _i64, _i32, _f32, _vp, ctypes.c_uint64, _vp, _i64, _vp, _f32, _vp, _f32, _vp]),
     "crh_comm_unique_id": (_i32, [_vp]),

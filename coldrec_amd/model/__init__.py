@@ -8,7 +8,7 @@ subclasses ``BaseColdStartTrainer`` can be registered with ``register(name, cls)
 resolve by name through ``[]``, ``.get()`` and ``in`` as well, from a cache of their own: resolving one never changes
 what ``keys()`` reports.  The cold-start trainers CLCRec, CCFCRec, ALDI and GAR resolve the same way from a third table and are not part of
 ``names()`` either (both listings are pinned); NCL, the third graph-contrastive backbone, has a fourth table for the same
-reason.  ``resolvable()`` is everything a ``--model`` flag can name.
+reason, and NGCF, the third warm backbone, a fifth.  ``resolvable()`` is everything a ``--model`` flag can name.
 """
 import importlib
 
@@ -17,9 +17,11 @@ _CONTRASTIVE = {'SimGCL': ('.SimGCL', 'SimGCL'), 'XSimGCL': ('.XSimGCL', 'XSimGC
 _COLD = {'CLCRec': ('.CLCRec', 'CLCRec'), 'CCFCRec': ('.CCFCRec', 'CCFCRec'), 'ALDI': ('.ALDI', 'ALDI'),
          'GAR': ('.GAR', 'GAR')}
 _NCL = {'NCL': ('.NCL', 'NCL')}
+_NGCF = {'NGCF': ('.NGCF', 'NGCF')}
 _contrastive_cache = {}
 _cold_cache = {}
 _ncl_cache = {}
+_ngcf_cache = {}
 
 
 class _Registry(dict):
@@ -39,6 +41,11 @@ class _Registry(dict):
                 mod, cls = _NCL[name]
                 _ncl_cache[name] = getattr(importlib.import_module(mod, __name__), cls)
             return _ncl_cache[name]
+        if name in _NGCF:
+            if name not in _ngcf_cache:
+                mod, cls = _NGCF[name]
+                _ngcf_cache[name] = getattr(importlib.import_module(mod, __name__), cls)
+            return _ngcf_cache[name]
         if name not in _BUILTIN:
             raise KeyError(name)
         mod, cls = _BUILTIN[name]
@@ -52,7 +59,8 @@ class _Registry(dict):
             return default
 
     def __contains__(self, name):
-        return name in _BUILTIN or name in _CONTRASTIVE or name in _COLD or name in _NCL or dict.__contains__(self, name)
+        return name in _BUILTIN or name in _CONTRASTIVE or name in _COLD or name in _NCL or name in _NGCF or \
+            dict.__contains__(self, name)
 
     def keys(self):
         return sorted(set(_BUILTIN) | set(dict.keys(self)))
@@ -62,8 +70,8 @@ class _Registry(dict):
         return sorted(set(_BUILTIN) | set(_CONTRASTIVE) | set(dict.keys(self)))
 
     def resolvable(self):
-        """Everything a ``--model`` flag can name: ``names()`` + the cold-start trainers + NCL."""
-        return sorted(set(self.names()) | set(_COLD) | set(_NCL))
+        """Everything a ``--model`` flag can name: ``names()`` + the cold-start trainers + NCL + NGCF."""
+        return sorted(set(self.names()) | set(_COLD) | set(_NCL) | set(_NGCF))
 
 
 AVAILABLE_MODELS = _Registry()

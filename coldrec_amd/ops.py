@@ -1405,6 +1405,73 @@ def gar(user_table: torch.Tensor, item_table: torch.Tensor, gen: torch.Tensor, p
     return loss, grad_user, grad_item, grad_gen
 
 
+# ---- NGCF's propagation layer (ngcf.hip) -----------------------------------------------------------------------------
+
+def ngcf_workspace_bytes(n_rows: int, d: int) -> int:
+    return int(_lib.lib().crh_ngcf_workspace_bytes(int(n_rows), int(d)))
+
+
+def ngcf_workspace(n_rows: int, d: int, device) -> torch.Tensor:
+    """Private scratch of one crh_ngcf_layer_bwd_f32 shape: the weight-gradient partials (at most 2048) and their sums."""
+    return torch.empty(max(ngcf_workspace_bytes(n_rows, d), 1), dtype=torch.uint8, device=device)
+
+
+def _ngcf_checks(op: str, x: torch.Tensor, w: torch.Tensor, same_shape, others) -> None:
+    dev = x.device
+    _check_2d_f32(op, "tables and weights", x, w, *[t for t in same_shape if t is not None])
+    for t in same_shape:
+        if t is not None and t.shape != x.shape:
+            raise RuntimeError(f"{op}: every table must have x's shape")
+    if w.shape != (2 * x.shape[1], x.shape[1]):
+        raise RuntimeError(f"{op}: w must be the stacked [Wgc; Wbi] of shape (2 d, d)")
+    for t in (w, *same_shape, *others):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{op}: every tensor must be on x's device")
+
+
+def ngcf_layer_fwd(x: torch.Tensor, s: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, y=None,
+                   acc_in=None, s_in: float = 1.0, acc_out=None, s_out: float = 1.0, want_y: bool = True):
+    """One NGCF layer (crh_ngcf_layer_fwd_f32; reference model/NGCF.py:94-99): x_k = leaky_relu(s Wgc^T + bgc +
+    (x * s) Wbi^T + bbi, 0.01) with s = A x, w = [Wgc; Wbi] stacked (2 d, d) and b = [bgc; bbi] (2, d) or None;
+    y = x_k, acc_out = (acc_in * s_in + x_k) * s_out (the SpMM's layer-sum convention; acc_out may be acc_in).  x, s:
+    fp32 contiguous (n_rows, d), d % 4 == 0 <= 256.  Returns (y, acc_out); ``want_y=False`` without ``y`` skips x_k's
+    store (the last layer of an evaluation forward)."""
+    _need_cuda(x, s, w, b, y, acc_in, acc_out)
+    _ngcf_checks("ngcf_layer_fwd", x, w, (s, y, acc_in, acc_out), (b,))
+    if b is not None and (b.dtype != torch.float32 or not b.is_contiguous() or b.shape != (2, x.shape[1])):
+        raise RuntimeError("ngcf_layer_fwd: b must be the stacked [bgc; bbi], contiguous float32 of shape (2, d)")
+    if y is None and (want_y or acc_out is None):
+        y = torch.empty_like(x)
+    _lib.check(_lib.lib().crh_ngcf_layer_fwd_f32(_lib.ptr(x), _lib.ptr(s), _lib.ptr(w), _lib.ptr(b), x.shape[0], x.shape[1],
+                                                 _lib.ptr(y), _lib.ptr(acc_in), float(s_in), _lib.ptr(acc_out), float(s_out),
+                                                 _lib.current_stream()), "crh_ngcf_layer_fwd_f32")
+    return y, acc_out
+
+
+def ngcf_layer_bwd(x: torch.Tensor, s: torch.Tensor, xk: torch.Tensor, g: Optional[torch.Tensor], dout: torch.Tensor,
+                   c: float, w: torch.Tensor, ds=None, local=None, dw=None, db=None, workspace=None):
+    """The backward of ``ngcf_layer_fwd`` (crh_ngcf_layer_bwd_f32): with dz = g * (xk > 0 ? 1 : 0.01) -- g = None means
+    g = c * dout, the top layer -- and T = dz Wbi, returns (ds, local, dw, db): ds = dz Wgc + x * T, local = c * dout +
+    s * T (so that g_{k-1} = local + A ds: the next SpMM's acc_in), dw = [dz^T s; dz^T (x * s)] in w's layout and db = dz's
+    column sums (the gradient of both biases).  ``local`` may be ``g`` and ``ds`` may be ``s``; every output is written
+    whole, in an order of sums fixed by the shape (two identical calls give identical bits)."""
+    _need_cuda(x, s, xk, g, dout, w, ds, local, dw, db, workspace)
+    _ngcf_checks("ngcf_layer_bwd", x, w, (s, xk, g, dout), (ds, local, dw, db, workspace))
+    ds = _grad_buffer("ngcf_layer_bwd", "x's shape", ds, x, True, True)
+    local = _grad_buffer("ngcf_layer_bwd", "x's shape", local, x, True, True)
+    dw = _grad_buffer("ngcf_layer_bwd", "w's shape", dw, w, True, True)
+    if db is None:
+        db = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
+    elif db.dtype != torch.float32 or not db.is_contiguous() or db.shape != (x.shape[1],):
+        raise RuntimeError("ngcf_layer_bwd: gradient buffers must be contiguous float32 tensors of the bias's shape (d,)")
+    workspace = _workspace_arg("ngcf_layer_bwd", workspace, ngcf_workspace, x.shape[0], x.shape[1], x.device)
+    _lib.check(_lib.lib().crh_ngcf_layer_bwd_f32(_lib.ptr(x), _lib.ptr(s), _lib.ptr(xk), _lib.ptr(g), _lib.ptr(dout), float(c),
+                                                 _lib.ptr(w), x.shape[0], x.shape[1], _lib.ptr(ds), _lib.ptr(local),
+                                                 _lib.ptr(dw), _lib.ptr(db), _lib.ptr(workspace), workspace.numel(),
+                                                 _lib.current_stream()), "crh_ngcf_layer_bwd_f32")
+    return ds, local, dw, db
+
+
 # ---- SimGCL / XSimGCL layer perturbation (perturb.hip) ---------------------------------------------------------------
 
 def _perturb_checks(what: str, y: torch.Tensor, *others) -> None:

@@ -907,6 +907,123 @@ class NCLEngine(LGCNEngine):
                                   step_scalars=step_scalars)
 
 
+class NGCFEngine(LGCNEngine):
+    """model/NGCF.py:15-29,90-104 on the LightGCN engine's table state, CSR schedule, fused BPR and Adam, with the dense
+    part of every layer in one fused kernel per direction (csrc/ngcf.hip).  c = 1 / (L + 1), x_0 = E:
+
+      forward   s_k = A x_{k-1} (the SpMM, y = s_k), then ops.ngcf_layer_fwd: x_k and the running sum of OUT
+      backward  g_L = c dOUT; for k = L..1: ops.ngcf_layer_bwd -> ds, local (= c dOUT + s_k (.) T, over g_k's buffer), the
+                layer's weight gradients; g_{k-1} = local + A ds is the next SpMM with acc_in = acc_out = local, the last one
+                with Adam on the table in its epilogue (CRH_LGCN_FUSED=0: gradient table + separate launch, the same bits).
+
+    Kept per layer for the backward: s_k and x_k (2 L tables; x_0 is E itself), plus ds and g (2 tables).
+    The 4 L dense tensors are ``nn.Parameter`` views ``W_gc[k]``, ``W_bi[k]`` (d, d) and ``b_gc[k]``, ``b_bi[k]`` (d) of one
+    stacked (2 d, d) / (2, d) buffer per layer -- the kernel's operand -- stepped by stock ``torch.optim.Adam(lr)``, their
+    ``.grad`` views of the kernel's buffers: per parameter the reference's arithmetic (its one Adam holds the same state per
+    tensor).  ``weights``: L tuples (W_gc.weight, W_gc.bias, W_bi.weight, W_bi.bias) of nn.Linear layout.
+    The step is launched eagerly; plain SGD, touched-rows Adam, data parallelism, row sharding and graph capture are not
+    built for it."""
+
+    def __init__(self, user0, item0, rowptr, col, val, n_layers: int, lr: float, reg: float, device, weights,
+                 optimizer: str = 'adam'):
+        if optimizer != 'adam':
+            raise ValueError("NGCF: --optimizer sgd is not built (the dense layers are stepped by torch.optim.Adam, as the "
+                             "reference steps them); use --optimizer adam")
+        d = int(user0.shape[1])
+        if d % 4 != 0 or d < 4 or d > 256:
+            raise ValueError(f"NGCF: emb_size {d} must be a multiple of 4 in [4, 256] (the fused HIP layer loads rows in "
+                             f"16-byte pieces and keeps at most 256 columns per wave)")
+        if len(weights) != int(n_layers):
+            raise ValueError(f"NGCF: {len(weights)} weight tuples for {n_layers} layers")
+        super().__init__(user0, item0, rowptr, col, val, n_layers, lr, reg, device, optimizer)
+        dev = self.device
+        self.Wst, self.bst, self.W_gc, self.W_bi, self.b_gc, self.b_bi = [], [], [], [], [], []
+        for wgc, bgc, wbi, bbi in weights:
+            w = torch.cat([torch.as_tensor(wgc).detach().float().reshape(d, d),
+                           torch.as_tensor(wbi).detach().float().reshape(d, d)]).to(dev).contiguous()
+            b = torch.stack([torch.as_tensor(bgc).detach().float().reshape(d),
+                             torch.as_tensor(bbi).detach().float().reshape(d)]).to(dev).contiguous()
+            self.Wst.append(w)
+            self.bst.append(b)
+            self.W_gc.append(torch.nn.Parameter(w[:d]))
+            self.W_bi.append(torch.nn.Parameter(w[d:]))
+            self.b_gc.append(torch.nn.Parameter(b[0]))
+            self.b_bi.append(torch.nn.Parameter(b[1]))
+        self.dWst = [torch.zeros_like(w) for w in self.Wst]
+        self.dbst = [torch.zeros(d, dtype=torch.float32, device=dev) for _ in range(self.L)]
+        for k in range(self.L):
+            self.W_gc[k].grad, self.W_bi[k].grad = self.dWst[k][:d], self.dWst[k][d:]
+            self.b_gc[k].grad = self.b_bi[k].grad = self.dbst[k]
+        self.wopt = torch.optim.Adam(self.dense_parameters(), lr=self.lr)
+        self.X = []                                                     # (the LightGCN ping-pong is not used)
+        self.S = [torch.empty_like(self.E) for _ in range(self.L)]      # s_k = A x_{k-1}
+        self.XK = [torch.empty_like(self.E) for _ in range(self.L)]     # x_k
+        self.DS = torch.empty_like(self.E)
+        self.GB = torch.empty_like(self.E)                              # local part, then g_{k-1}
+        self._ng_ws = self.k.ngcf_workspace(self.E.shape[0], d, dev)
+
+    def dense_parameters(self):
+        """The 4 L dense parameters, per layer W_gc.weight, W_gc.bias, W_bi.weight, W_bi.bias."""
+        return [p for k in range(self.L) for p in (self.W_gc[k], self.b_gc[k], self.W_bi[k], self.b_bi[k])]
+
+    def enable_data_parallel(self, dp: DPContext) -> None:
+        raise RuntimeError("NGCF: data-parallel training is not built (single GPU only)")
+
+    def enable_row_sharding(self, dp: DPContext) -> None:
+        raise RuntimeError("NGCF: row-sharded propagation is not built (single GPU only)")
+
+    def _propagate(self, out: torch.Tensor, keep_last: bool = False) -> None:
+        c = 1.0 / (self.L + 1)
+        x = self.E
+        for k in range(self.L):
+            last = k == self.L - 1
+            self.k.spmm_csr(self.rowptr, self.col, self.val, x, y=self.S[k], sched=self.sched)
+            y = self.XK[k] if (keep_last or not last) else None
+            self.k.ngcf_layer_fwd(x, self.S[k], self.Wst[k], self.bst[k], y=y, acc_in=self.E if k == 0 else out, s_in=1.0,
+                                  acc_out=out, s_out=c if last else 1.0, want_y=False)
+            x = y
+
+    def forward(self):
+        self._propagate(self.OUT)
+        return self._view(self.OUT[: self.user_num]), self._view(self.OUT[self.user_num:])
+
+    def step(self, user_idx, pos_idx, neg_idx, plan: Optional[torch.Tensor] = None, loss_out=None,
+             step_scalars=None) -> None:
+        """One optimiser step over the tables and the dense layers; ``plan`` (ops.build_plans_device) makes the BPR
+        gradient rows deterministic."""
+        U = self.user_num
+        loss = self.loss if loss_out is None else loss_out
+        self._propagate(self.OUT, keep_last=True)
+        self.dOUT.zero_()
+        self.k.bpr_fwd_bwd(self.OUT[:U], self.OUT[U:], self.OUT[U:], user_idx, pos_idx, neg_idx, self.reg,
+                           self.dOUT[:U], self.dOUT[U:], self.dOUT[U:], loss, plan=plan,
+                           workspace=self._ws(user_idx.shape[0]))
+        self._backward(step_scalars)
+
+    def _backward(self, step_scalars) -> None:
+        c = 1.0 / (self.L + 1)
+        self.step_count += 1
+        g = None                                                        # g_L = c dOUT, formed in the kernel
+        for k in range(self.L, 0, -1):
+            x = self.E if k == 1 else self.XK[k - 2]
+            self.k.ngcf_layer_bwd(x, self.S[k - 1], self.XK[k - 1], g, self.dOUT, c, self.Wst[k - 1], ds=self.DS,
+                                  local=self.GB, dw=self.dWst[k - 1], db=self.dbst[k - 1], workspace=self._ng_ws)
+            g = self.GB
+            if k > 1:
+                self.k.spmm_csr(self.rowptr, self.col, self.val, self.DS, y=None, acc_in=g, s_in=1.0, acc_out=g, s_out=1.0,
+                                sched=self.sched)
+            elif self.fuse_adam:
+                self.k.spmm_csr_adam(self.rowptr, self.col, self.val, self.DS, g, 1.0, self.G if self.keep_grad else None,
+                                     1.0, self.sched, self.E, self.M, self.V, self.step_count, lr=self.lr,
+                                     step_scalars=step_scalars)
+            else:
+                self.k.spmm_csr(self.rowptr, self.col, self.val, self.DS, y=None, acc_in=g, s_in=1.0, acc_out=self.G,
+                                s_out=1.0, sched=self.sched)
+                self.k.adam_dense(self.E, self.G, self.M, self.V, self.step_count, lr=self.lr, zero_grad=False,
+                                  step_scalars=step_scalars)
+        self.wopt.step()
+
+
 class EpochRunner:
     """One epoch of optimiser steps as a replayable hipGraph.
 

@@ -713,6 +713,37 @@ int crh_gar_f32(const float* user_table, int64_t user_rows, const float* item_ta
                 float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * One propagation layer of NGCF (reference model/NGCF.py:94-99) over all n_rows rows, forward and backward (csrc/ngcf.hip).
+ * x = x_{k-1}, s = A x (the SpMM's y), both (n_rows, d) fp32; w = [Wgc; Wbi] stacked, (2 d, d) fp32 in nn.Linear's
+ * (out, in) layout; b = [bgc; bbi], (2, d), or NULL = no bias.  4 <= d <= 256, d % 4 == 0, 1 <= n_rows <= 2^30, every
+ * pointer 16-byte aligned.  fp32 MFMA (exact fp32 fma chains), plain launches on `stream`, no atomics; every sum runs
+ * in an order fixed by (n_rows, d), so two identical calls give identical bits.
+ *
+ * crh_ngcf_layer_fwd_f32:
+ *     z = s Wgc^T + bgc + (x (.) s) Wbi^T + bbi ;  x_k = z > 0 ? z : 0.01 z  (z == 0 gives 0)
+ *     y = x_k (if y) ;  acc_out = (acc_in * s_in + x_k) * s_out (if acc_out; acc_in NULL = 0): the SpMM's convention, so
+ *     the mean over the layers costs no pass of its own.  At least one of y, acc_out must be given.
+ *     acc_out may alias acc_in.  No output may alias x or s, and y must not alias acc_out.
+ *
+ * crh_ngcf_layer_bwd_f32: xk = x_k (only its sign is used), g = g_k = d loss / d x_k (NULL: g_k = c * dout, the top
+ * layer), dout = d loss / d OUT, c = 1 / (L + 1):
+ *     dz = g (.) (xk > 0 ? 1 : 0.01)                         (torch's rule: an exact zero takes 0.01)
+ *     T = dz Wbi ;  ds = dz Wgc + x (.) T ;  local = c * dout + s (.) T     (g_{k-1} = local + A ds: the next SpMM's acc_in)
+ *     dw = [dz^T s ; dz^T (x (.) s)]  (2 d, d), w's layout ;  db = column sums of dz  (d: the gradient of bgc AND of bbi)
+ *     All four outputs are written whole.  local may alias g, and ds may alias s: a row's g and s are read for the last
+ *     time before its local and ds are written.  No other output may alias an input or another output.
+ *     workspace: crh_ngcf_workspace_bytes(n_rows, d) bytes, 256-byte aligned -- one (2 ceil32(d) + 1) x ceil32(d) partial
+ *     of dw and db per wave of the launch (at most 2048, a function of n_rows alone) and the sums of 32 consecutive
+ *     partials; a smaller one is refused with CRH_ERR_WS.
+ */
+size_t crh_ngcf_workspace_bytes(int64_t n_rows, int d);
+int crh_ngcf_layer_fwd_f32(const float* x, const float* s, const float* w, const float* b, int64_t n_rows, int d, float* y,
+                           const float* acc_in, float s_in, float* acc_out, float s_out, void* stream);
+int crh_ngcf_layer_bwd_f32(const float* x, const float* s, const float* xk, const float* g, const float* dout, float c,
+                           const float* w, int64_t n_rows, int d, float* ds, float* local, float* dw, float* db,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The layer perturbation of SimGCL / XSimGCL (model/SimGCL.py:106-108), in place on one (n_rows, d) fp32 layer output
  * of the propagation, d % 4 == 0, 4 <= d <= 256, every pointer 16-byte aligned.  Per row, r = the row's d uniforms:
  *     nrm = max(sqrt(sum r^2), 1e-12)                       (F.normalize's clamp)
