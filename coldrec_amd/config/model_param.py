@@ -14,6 +14,20 @@ def _str2bool(v):
     raise argparse.ArgumentTypeError(f'expected a boolean value, got {v!r}')
 
 
+def _lr_wd_pair(v):
+    """An (lr, weight decay) pair written as "0.05,0" or as "[0.05, 0]" (brackets or parentheses, spaces allowed)."""
+    if isinstance(v, (list, tuple)):
+        parts = list(v)
+    else:
+        parts = str(v).strip().strip('[]()').split(',')
+    try:
+        if len(parts) != 2:
+            raise ValueError
+        return [float(x) for x in parts]
+    except (TypeError, ValueError):
+        raise argparse.ArgumentTypeError(f'expected two numbers such as "0.05,0" or "[0.05, 0]", got {v!r}') from None
+
+
 def model_specific_param(model_name, parser, available_models):
     if model_name not in available_models:
         names = available_models.resolvable() if hasattr(available_models, 'resolvable') else \
@@ -75,4 +89,9 @@ def model_specific_param(model_name, parser, available_models):
     if model_name == 'GAR':       # config/model_param.py:94-96
         parser.add_argument('--alpha', type=float, default=0.05, help='Weight of the similarity term in the generator loss')
         parser.add_argument('--beta', type=float, default=0.1, help='Weight of the sampled negative in the recommender loss')
+    if model_name == 'MTPR':      # config/model_param.py:300-303
+        parser.add_argument('--p_emb', type=_lr_wd_pair, default=[0.05, 0.0], help='lr and weight decay of the two id tables')
+        parser.add_argument('--p_ctx', type=_lr_wd_pair, default=[0.05, 0.01],
+                            help='lr and weight decay of the content projection W and of weu')
+        parser.add_argument('--p_proj', type=_lr_wd_pair, default=[0.05, 0.01], help='lr and weight decay of wei')
     return parser

@@ -8,7 +8,7 @@ subclasses ``BaseColdStartTrainer`` can be registered with ``register(name, cls)
 resolve by name through ``[]``, ``.get()`` and ``in`` as well, from a cache of their own: resolving one never changes
 what ``keys()`` reports.  The cold-start trainers CLCRec, CCFCRec, ALDI and GAR resolve the same way from a third table and are not part of
 ``names()`` either (both listings are pinned); NCL, the third graph-contrastive backbone, has a fourth table for the same
-reason, and NGCF, the third warm backbone, a fifth.  ``resolvable()`` is everything a ``--model`` flag can name.
+reason, NGCF, the third warm backbone, a fifth, and MTPR a sixth.  ``resolvable()`` is everything a ``--model`` flag can name.
 """
 import importlib
 
@@ -18,10 +18,12 @@ _COLD = {'CLCRec': ('.CLCRec', 'CLCRec'), 'CCFCRec': ('.CCFCRec', 'CCFCRec'), 'A
          'GAR': ('.GAR', 'GAR')}
 _NCL = {'NCL': ('.NCL', 'NCL')}
 _NGCF = {'NGCF': ('.NGCF', 'NGCF')}
+_MTPR = {'MTPR': ('.MTPR', 'MTPR')}
 _contrastive_cache = {}
 _cold_cache = {}
 _ncl_cache = {}
 _ngcf_cache = {}
+_mtpr_cache = {}
 
 
 class _Registry(dict):
@@ -46,6 +48,11 @@ class _Registry(dict):
                 mod, cls = _NGCF[name]
                 _ngcf_cache[name] = getattr(importlib.import_module(mod, __name__), cls)
             return _ngcf_cache[name]
+        if name in _MTPR:
+            if name not in _mtpr_cache:
+                mod, cls = _MTPR[name]
+                _mtpr_cache[name] = getattr(importlib.import_module(mod, __name__), cls)
+            return _mtpr_cache[name]
         if name not in _BUILTIN:
             raise KeyError(name)
         mod, cls = _BUILTIN[name]
@@ -60,7 +67,7 @@ class _Registry(dict):
 
     def __contains__(self, name):
         return name in _BUILTIN or name in _CONTRASTIVE or name in _COLD or name in _NCL or name in _NGCF or \
-            dict.__contains__(self, name)
+            name in _MTPR or dict.__contains__(self, name)
 
     def keys(self):
         return sorted(set(_BUILTIN) | set(dict.keys(self)))
@@ -70,8 +77,8 @@ class _Registry(dict):
         return sorted(set(_BUILTIN) | set(_CONTRASTIVE) | set(dict.keys(self)))
 
     def resolvable(self):
-        """Everything a ``--model`` flag can name: ``names()`` + the cold-start trainers + NCL + NGCF."""
-        return sorted(set(self.names()) | set(_COLD) | set(_NCL) | set(_NGCF))
+        """Everything a ``--model`` flag can name: ``names()`` + the cold-start trainers + NCL + NGCF + MTPR."""
+        return sorted(set(self.names()) | set(_COLD) | set(_NCL) | set(_NGCF) | set(_MTPR))
 
 
 AVAILABLE_MODELS = _Registry()

@@ -1405,6 +1405,131 @@ def gar(user_table: torch.Tensor, item_table: torch.Tensor, gen: torch.Tensor, p
     return loss, grad_user, grad_item, grad_gen
 
 
+# ---- MTPR's loss (mtpr.hip) and the touched-rows Adagrad (adagrad.hip) -----------------------------------------------
+
+def mtpr_chunk_rows() -> int:
+    return int(_lib.lib().crh_mtpr_chunk_rows())
+
+
+def mtpr_workspace_bytes(batch: int, d: int, cold_user: bool, n_items: int, n_users: int) -> int:
+    return int(_lib.lib().crh_mtpr_workspace_bytes(int(batch), int(d), int(bool(cold_user)), int(n_items), int(n_users)))
+
+
+def mtpr_workspace(batch: int, d: int, cold_user: bool, n_items: int, n_users: int, device) -> torch.Tensor:
+    return torch.empty(max(mtpr_workspace_bytes(batch, d, cold_user, n_items, n_users), 1), dtype=torch.uint8,
+                       device=device)
+
+
+def mtpr_plan(users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_users: Optional[int] = None,
+              n_items: Optional[int] = None, id_range=None, chunk: Optional[int] = None) -> dict:
+    """The index side of one crh_mtpr_f32 step: ``gar_plan``'s arrays (same arguments, same id_range shortcut, same
+    errors) with the owners' occurrences cut into chunks of crh_mtpr_chunk_rows().  user_ids / item_ids are the distinct
+    ids, ascending: what ``adagrad_rows`` steps."""
+    B = users.shape[0] if users.dim() == 1 else 0
+    if B < 1 or pos.shape != (B,) or neg.shape != (B,):
+        raise RuntimeError("mtpr_plan: users, pos, neg must be (B,) with B >= 1")
+    if any(t.dtype.is_floating_point or t.device != users.device for t in (users, pos, neg)):
+        raise RuntimeError("mtpr_plan: users, pos, neg must be integer tensors on one device")
+    ulong = users.long()
+    both = torch.cat([pos.long(), neg.long()])
+    if id_range is None:
+        id_range = ((int(ulong.min()), int(ulong.max())), (int(both.min()), int(both.max())))
+    user_range, item_range = (tuple(int(x) for x in r) for r in id_range)
+    if n_users is not None and (user_range[0] < 0 or user_range[1] >= n_users):
+        raise RuntimeError("mtpr_plan: user id outside the user table")
+    if n_items is not None and (item_range[0] < 0 or item_range[1] >= n_items):
+        raise RuntimeError("mtpr_plan: item id outside the item table")
+    if chunk is None:
+        chunk = mtpr_chunk_rows()
+    item_ids, item_occ, item_ptr, item_chunk_ptr, item_chunk_own, _ = _owner_chunks(both, chunk)
+    user_ids, user_occ, user_ptr, user_chunk_ptr, user_chunk_own, _ = _owner_chunks(ulong, chunk)
+    c = lambda t: t.to(torch.int32).contiguous()
+    return dict(batch=B, n_items=int(item_ids.shape[0]), n_users=int(user_ids.shape[0]),
+                n_item_chunks=int(item_chunk_own.shape[0]), n_user_chunks=int(user_chunk_own.shape[0]),
+                user_range=user_range, item_range=item_range, users=c(ulong), pos=c(both[:B]), neg=c(both[B:]),
+                item_ids=c(item_ids), item_ptr=c(item_ptr), item_occ=c(item_occ), item_chunk_ptr=c(item_chunk_ptr),
+                item_chunk_own=c(item_chunk_own), user_ids=c(user_ids), user_ptr=c(user_ptr), user_occ=c(user_occ),
+                user_chunk_ptr=c(user_chunk_ptr), user_chunk_own=c(user_chunk_own))
+
+
+def mtpr(user_table: torch.Tensor, item_table: torch.Tensor, h: torch.Tensor, weu: torch.Tensor, wei: torch.Tensor,
+         plan: dict, wd1: float, cold_user: bool = False, scale: float = 1.0, want_user: bool = True,
+         want_item: bool = True, want_h: bool = True, want_weu: bool = True, want_wei: bool = True, grad_user=None,
+         grad_item=None, grad_h=None, grad_weu=None, grad_wei=None, loss=None, workspace=None):
+    """MTPR's four ranking terms, the tables' regulariser and their five gradients in one call (crh_mtpr_f32).  d = the
+    embedding width (d % 4 == 0, 4 <= d <= 128); weu, wei (2 d, d).  Item mode: user_table (nu, 2 d), item_table (ni, d),
+    h (2 B, d) = the content projections of the positives, then of the negatives.  User mode (cold_user): user_table
+    (nu, d), item_table (ni, 2 d), h (B, d) = the users' content projections.  fp32 contiguous; plan: ``mtpr_plan``.
+    Returns (loss6 = [L_i, L_f, L_if, L_fi, R_emb, sum], grad_user, grad_item, grad_h, grad_weu, grad_wei); gradients
+    are d sum / d . * scale.  The table gradients are written at the rows the batch touches ONLY: a caller's buffer keeps
+    every other row as it was (a new one is zeroed).  A gradient that is neither given nor wanted is not computed (None)."""
+    _need_cuda(user_table, item_table, h, weu, wei, plan["users"], grad_user, grad_item, grad_h, grad_weu, grad_wei, loss,
+               workspace)
+    dev = user_table.device
+    _check_2d_f32("mtpr", "tables, content rows and projections", user_table, item_table, h, weu, wei)
+    cold_user = bool(cold_user)
+    d = weu.shape[1]
+    if d % 4 != 0 or d < 4 or d > 128:
+        raise RuntimeError(f"mtpr: width {d} must be a multiple of 4 in [4, 128]")
+    B = plan["batch"]
+    wp, wq, hr = (d, 2 * d, B) if cold_user else (2 * d, d, 2 * B)
+    if weu.shape != (2 * d, d) or wei.shape != (2 * d, d):
+        raise RuntimeError("mtpr: weu and wei must be (2 d, d)")
+    if user_table.shape[1] != wp or item_table.shape[1] != wq or h.shape != (hr, d):
+        raise RuntimeError("mtpr: item mode takes tables (nu, 2 d), (ni, d) and h (2 B, d); user mode (nu, d), (ni, 2 d) "
+                           "and h (B, d), B the plan's batch")
+    for t in (item_table, h, weu, wei, plan["users"], grad_user, grad_item, grad_h, grad_weu, grad_wei, loss, workspace):
+        if t is not None and t.device != dev:
+            raise RuntimeError("mtpr: every tensor must be on the tables' device")
+    (u_lo, u_hi), (i_lo, i_hi) = plan["user_range"], plan["item_range"]
+    if u_lo < 0 or u_hi >= user_table.shape[0] or i_lo < 0 or i_hi >= item_table.shape[0]:
+        raise RuntimeError("mtpr: ids lie outside the tables")
+
+    what = "the shapes of the tables, the content rows and the projections"
+    grad_user = _grad_buffer("mtpr", what, grad_user, user_table, want_user, False)
+    grad_item = _grad_buffer("mtpr", what, grad_item, item_table, want_item, False)
+    grad_h = _grad_buffer("mtpr", what, grad_h, h, want_h, True)
+    grad_weu = _grad_buffer("mtpr", what, grad_weu, weu, want_weu, True)
+    grad_wei = _grad_buffer("mtpr", what, grad_wei, wei, want_wei, True)
+    if loss is None:
+        loss = torch.empty(6, dtype=torch.float32, device=dev)
+    elif loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 6:
+        raise RuntimeError("mtpr: loss must be a contiguous float32 buffer of at least six elements")
+    workspace = _workspace_arg("mtpr", workspace, mtpr_workspace, B, d, cold_user, plan["n_items"], plan["n_users"], dev)
+    p = plan
+    _lib.check(_lib.lib().crh_mtpr_f32(
+        _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]), _lib.ptr(h),
+        _lib.ptr(weu), _lib.ptr(wei), _lib.ptr(p["users"]), _lib.ptr(p["pos"]), _lib.ptr(p["neg"]), int(u_lo), int(u_hi),
+        int(i_lo), int(i_hi), _lib.ptr(p["item_ids"]), _lib.ptr(p["item_ptr"]), _lib.ptr(p["item_occ"]),
+        _lib.ptr(p["item_chunk_ptr"]), _lib.ptr(p["item_chunk_own"]), int(p["n_items"]), int(p["n_item_chunks"]),
+        _lib.ptr(p["user_ids"]), _lib.ptr(p["user_ptr"]), _lib.ptr(p["user_occ"]), _lib.ptr(p["user_chunk_ptr"]),
+        _lib.ptr(p["user_chunk_own"]), int(p["n_users"]), int(p["n_user_chunks"]), int(B), int(d), int(cold_user),
+        float(wd1), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item), _lib.ptr(grad_h), _lib.ptr(grad_weu),
+        _lib.ptr(grad_wei), _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_mtpr_f32")
+    return loss, grad_user, grad_item, grad_h, grad_weu, grad_wei
+
+
+def adagrad_rows(p: torch.Tensor, g: torch.Tensor, state_sum: torch.Tensor, ids: torch.Tensor, lr: float,
+                 eps: float = 1e-10, zero_grad: bool = True) -> None:
+    """One step of torch.optim.Adagrad's defaults over the rows ``ids`` (int32, distinct) of p, in place:
+    state_sum += g * g; p -= lr * g / (sqrt(state_sum) + eps); then g's consumed rows are cleared (crh_adagrad_rows_f32).
+    p, g, state_sum: (rows, d) contiguous float32, d % 4 == 0 <= 256.  A row whose gradient is zero keeps its bits."""
+    _need_cuda(p, g, state_sum, ids)
+    _check_2d_f32("adagrad_rows", "p, g and state_sum", p, g, state_sum)
+    if g.shape != p.shape or state_sum.shape != p.shape:
+        raise RuntimeError("adagrad_rows: p, g and state_sum must have one shape")
+    d = p.shape[1]
+    if d % 4 != 0 or d < 4 or d > 256:
+        raise RuntimeError(f"adagrad_rows: width {d} must be a multiple of 4 in [4, 256]")
+    if ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous() or ids.shape[0] > p.shape[0]:
+        raise RuntimeError("adagrad_rows: ids must be a contiguous int32 vector of distinct rows")
+    if any(t.device != p.device for t in (g, state_sum, ids)):
+        raise RuntimeError("adagrad_rows: every tensor must be on p's device")
+    _lib.check(_lib.lib().crh_adagrad_rows_f32(_lib.ptr(p), _lib.ptr(g), _lib.ptr(state_sum), _lib.ptr(ids),
+                                               int(ids.shape[0]), int(p.shape[0]), int(d), float(lr), float(eps),
+                                               int(bool(zero_grad)), _lib.current_stream()), "crh_adagrad_rows_f32")
+
+
 # ---- NGCF's propagation layer (ngcf.hip) -----------------------------------------------------------------------------
 
 def ngcf_workspace_bytes(n_rows: int, d: int) -> int:

@@ -744,6 +744,52 @@ int crh_ngcf_layer_bwd_f32(const float* x, const float* s, const float* xk, cons
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * MTPR's loss (reference model/MTPR.py:140-202), forward and backward in one call (csrc/mtpr.hip).  d = the embedding
+ * width, 4 <= d <= 128, d % 4 == 0; weu, wei (2 d, d); per record b a user u, a positive i, a negative j.
+ *   cold_user == 0  user_table P (user_rows, 2 d), item_table Q (item_rows, d), h (2 batch, d): row o < batch = the content
+ *                   projection of the positive of record o, row batch + o of its negative
+ *                   e = P[u] weu;  f_x = [Q[x] | h_x] wei,  hz_x = h_x wei[d:];  s_x = <e, f_x>,  z_x = <e, hz_x>
+ *   cold_user != 0  P (user_rows, d), Q (item_rows, 2 d), h (batch, d): the content projection of the record's user
+ *                   ef = [P[u] | h_b] weu,  ez = h_b weu[d:];  q_x = Q[x] wei;  s_x = <ef, q_x>,  z_x = <ez, q_x>
+ *   sp(t) = softplus(-t) = max(-t, 0) + log1p(exp(-|t|)); all sums over the batch, no means:
+ *     L_i = sum sp(s_i - s_j)   L_f = sum sp(z_i - z_j)   L_if = sum sp(s_i - z_j)   L_fi = sum sp(z_i - s_j)
+ *     R_emb = wd1 sum_b (|P[u]|^2 + |Q[i]|^2 + |Q[j]|^2)        (a row counts once per occurrence)
+ *   loss_out       6 device floats: L_i, L_f, L_if, L_fi, R_emb, their sum (not scaled); NULL = not written
+ *   grad_user, grad_item  d sum / d table * scale, written at the touched rows ONLY: every other row of the caller's
+ *                  buffer keeps what it held (crh_adagrad_rows_f32 clears the rows it consumes, so a trainer zeroes its
+ *                  buffers once); duplicate ids are summed in the plan's order
+ *   grad_h, grad_weu, grad_wei  d sum / d . * scale, h's shape and (2 d, d), every element written.  Any gradient may be
+ *                  NULL: it is not computed and the others keep their bits
+ *   ids and inverse indices: as crh_gar_f32's, with chunks of crh_mtpr_chunk_rows() (ops.mtpr_plan builds them)
+ *   workspace      crh_mtpr_workspace_bytes(batch, d, cold_user, n_items, n_users) bytes (0 = a refused shape), 256-byte
+ *                  aligned: the per-record gradient rows, one (4 ceil32(d)) x ceil32(d) partial of [dweu ; dwei] per
+ *                  workgroup of the tile launch (at most 512, a function of batch alone), the owner chunks' partials
+ * 1 <= batch < 2^30; every float pointer 16-byte aligned.  fp32 throughout on the fp32 MFMAs; no atomics, every sum in an
+ * order fixed by (batch, d) and the plan: two identical calls give identical bits.
+ */
+int crh_mtpr_chunk_rows(void);
+size_t crh_mtpr_workspace_bytes(int64_t batch, int d, int cold_user, int64_t n_items, int64_t n_users);
+int crh_mtpr_f32(const float* user_table, int64_t user_rows, const float* item_table, int64_t item_rows, const float* h,
+                 const float* weu, const float* wei, const int32_t* users, const int32_t* pos, const int32_t* neg,
+                 int user_min, int user_max, int item_min, int item_max, const int32_t* item_ids, const int32_t* item_ptr,
+                 const int32_t* item_occ, const int32_t* item_chunk_ptr, const int32_t* item_chunk_own, int64_t n_items,
+                 int64_t n_item_chunks, const int32_t* user_ids, const int32_t* user_ptr, const int32_t* user_occ,
+                 const int32_t* user_chunk_ptr, const int32_t* user_chunk_own, int64_t n_users, int64_t n_user_chunks,
+                 int64_t batch, int d, int cold_user, float wd1, float scale, float* grad_user, float* grad_item,
+                 float* grad_h, float* grad_weu, float* grad_wei, float* loss_out, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
+/*
+ * torch.optim.Adagrad's defaults (lr_decay = 0, weight_decay = 0, accumulator 0) over n_ids DISTINCT rows of a (n_rows, d)
+ * table, d % 4 == 0, 4 <= d <= 256 (csrc/adagrad.hip).  Per element, every operation rounded on its own:
+ *     s <- s + g * g ;  p <- p + (-lr) * (g / (sqrt(s) + eps))          (lr and eps rounded to fp32)
+ * then the consumed gradient rows are cleared when zero_grad != 0.  A row whose gradient is zero keeps its bits in p and
+ * s, so the pass over a batch's touched rows equals the dense step.  Ids outside the table update nothing.
+ */
+int crh_adagrad_rows_f32(float* p, float* g, float* state_sum, const int32_t* ids, int64_t n_ids, int64_t n_rows, int d,
+                         double lr, double eps, int zero_grad, void* stream);
+
+/*
  * The layer perturbation of SimGCL / XSimGCL (model/SimGCL.py:106-108), in place on one (n_rows, d) fp32 layer output
  * of the propagation, d % 4 == 0, 4 <= d <= 256, every pointer 16-byte aligned.  Per row, r = the row's d uniforms:
  *     nrm = max(sqrt(sum r^2), 1e-12)                       (F.normalize's clamp)
