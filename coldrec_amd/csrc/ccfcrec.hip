@@ -297,8 +297,6 @@ struct CcfWs {
 
 int64_t ccf_rows(int n_pos, int n_neg, int n_self) { return 1 + (int64_t)n_pos + (int64_t)n_pos * n_neg + n_self; }
 
-int64_t ccf_max_chunks(int64_t occurrences, int64_t n_own) { return n_own + occurrences / CCF_CHUNK; }
-
 bool ccf_shape_ok(int64_t batch, int n_pos, int n_neg, int n_self, int d, int64_t n_items, int64_t n_users) {
     if (batch < 1 || n_pos < 1 || n_neg < 1 || n_self < 1 || !lg_width_ok(d)) return false;
     const int64_t rows = ccf_rows(n_pos, n_neg, n_self);
@@ -316,8 +314,8 @@ CcfWs ccf_layout(void* base, int64_t batch, int64_t rows, int d, int64_t n_items
     w.gi = c.take(batch * d);
     w.gu = c.take(batch * d);
     w.rec = c.take(batch * 4);
-    w.part_i = c.take(ccf_max_chunks(m, n_items) * (2 * d + 4));
-    w.part_u = c.take(ccf_max_chunks(2 * batch, n_users) * d);
+    w.part_i = c.take(lg_max_chunks(m, n_items, CCF_CHUNK) * (2 * d + 4));
+    w.part_u = c.take(lg_max_chunks(2 * batch, n_users, CCF_CHUNK) * d);
     w.bytes = c.bytes;
     return w;
 }
@@ -325,9 +323,8 @@ CcfWs ccf_layout(void* base, int64_t batch, int64_t rows, int d, int64_t n_items
 struct CcfArgs {
     const float *ut, *vt, *q;
     const int32_t *users, *neg_users, *items;
-    const int32_t *item_ids, *item_ptr, *item_rows, *item_chunk_ptr, *item_chunk_own;
-    const int32_t *user_ids, *user_ptr, *user_rows, *user_chunk_ptr, *user_chunk_own;
-    int64_t n_items, n_item_chunks, n_users, n_user_chunks, batch;
+    LgOwners io, uo;                // the inverse index of the items and of the users
+    int64_t batch;
     int n_pos, n_neg, n_self, rows, d;
     float inv_t, w_c, w_s, w_r;
     float *grad_user, *grad_item, *grad_q;
@@ -340,17 +337,18 @@ void ccf_launch(const CcfWs& w, const CcfArgs& a, hipStream_t st) {
                        a.q, a.users, a.neg_users, a.items, a.n_pos, a.n_neg, a.n_self, a.rows, a.d, a.inv_t, a.w_c, a.w_s,
                        a.w_r, w.x1, w.x2, w.qh, w.gi, w.gu, a.grad_q, w.rec);
     if (a.grad_item) {
-        hipLaunchKernelGGL((ccf_item_chunk_kernel<LPR>), dim3((unsigned)a.n_item_chunks), dim3(64), 0, st, a.item_ptr,
-                           a.item_rows, a.item_chunk_ptr, a.item_chunk_own, a.n_items, a.batch, a.rows, a.d, w.x1, w.x2, w.qh,
-                           w.gi, w.part_i);
-        hipLaunchKernelGGL((ccf_item_finish_kernel<LPR>), dim3((unsigned)((a.n_items + RG - 1) / RG)), dim3(64), 0, st, a.vt,
-                           a.item_ids, a.item_chunk_ptr, a.n_items, a.d, w.part_i, a.grad_item);
+        const LgOwners& o = a.io;
+        hipLaunchKernelGGL((ccf_item_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, o.ptr, o.occ, o.chunk_ptr,
+                           o.chunk_own, o.n, a.batch, a.rows, a.d, w.x1, w.x2, w.qh, w.gi, w.part_i);
+        hipLaunchKernelGGL((ccf_item_finish_kernel<LPR>), dim3((unsigned)((o.n + RG - 1) / RG)), dim3(64), 0, st, a.vt, o.ids,
+                           o.chunk_ptr, o.n, a.d, w.part_i, a.grad_item);
     }
     if (a.grad_user) {
-        hipLaunchKernelGGL((ccf_user_chunk_kernel<LPR>), dim3((unsigned)a.n_user_chunks), dim3(64), 0, st, a.user_ptr,
-                           a.user_rows, a.user_chunk_ptr, a.user_chunk_own, a.n_users, a.batch, a.d, w.gu, w.part_u);
-        hipLaunchKernelGGL((ccf_user_finish_kernel<LPR>), dim3((unsigned)((a.n_users + RG - 1) / RG)), dim3(64), 0, st,
-                           a.user_ids, a.user_chunk_ptr, a.n_users, a.d, w.part_u, a.grad_user);
+        const LgOwners& o = a.uo;
+        hipLaunchKernelGGL((ccf_user_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, o.ptr, o.occ, o.chunk_ptr,
+                           o.chunk_own, o.n, a.batch, a.d, w.gu, w.part_u);
+        hipLaunchKernelGGL((ccf_user_finish_kernel<LPR>), dim3((unsigned)((o.n + RG - 1) / RG)), dim3(64), 0, st, o.ids,
+                           o.chunk_ptr, o.n, a.d, w.part_u, a.grad_user);
     }
 }
 
@@ -378,9 +376,9 @@ extern "C" int crh_ccfcrec_f32(const float* user_table, int64_t user_rows, const
                                float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
     CRH_CHECK_ARG(user_table && item_table && q, "crh_ccfcrec_f32: NULL table pointer");
     CRH_CHECK_ARG(users && neg_users && items, "crh_ccfcrec_f32: NULL id pointer");
-    CRH_CHECK_ARG(item_ids && item_ptr && item_occ && item_chunk_ptr && item_chunk_own && user_ids && user_ptr && user_occ &&
-                      user_chunk_ptr && user_chunk_own,
-                  "crh_ccfcrec_f32: NULL inverse-index pointer");
+    const LgOwners io{item_ids, item_ptr, item_occ, item_chunk_ptr, item_chunk_own, n_items, n_item_chunks};
+    const LgOwners uo{user_ids, user_ptr, user_occ, user_chunk_ptr, user_chunk_own, n_users, n_user_chunks};
+    LG_CHECK_OWNER_PTRS("crh_ccfcrec_f32", io, uo);
     CRH_CHECK_ARG(grad_user || grad_item || grad_q || loss_out, "crh_ccfcrec_f32: NULL gradients and loss: nothing to compute");
     LG_CHECK_WIDTH("crh_ccfcrec_f32", d);
     CRH_CHECK_ARG(n_pos >= 1 && n_neg >= 1 && n_self >= 1, "crh_ccfcrec_f32: n_pos = %d, n_neg = %d, n_self = %d must be >= 1",
@@ -390,16 +388,7 @@ extern "C" int crh_ccfcrec_f32(const float* user_table, int64_t user_rows, const
                   CCF_MAX_ROWS);
     CRH_CHECK_ARG(batch >= 1 && batch * rows < ((int64_t)1 << 31),
                   "crh_ccfcrec_f32: batch = %lld: batch * rows must lie in [1, 2^31)", (long long)batch);
-    CRH_CHECK_ARG(n_items >= 1 && n_items <= batch * rows, "crh_ccfcrec_f32: n_items = %lld out of [1, batch * rows]",
-                  (long long)n_items);
-    CRH_CHECK_ARG(n_users >= 1 && n_users <= 2 * batch, "crh_ccfcrec_f32: n_users = %lld out of [1, 2 batch]",
-                  (long long)n_users);
-    CRH_CHECK_ARG(n_item_chunks >= n_items && n_item_chunks <= ccf_max_chunks(batch * rows, n_items),
-                  "crh_ccfcrec_f32: n_item_chunks = %lld out of [n_items, n_items + batch * rows / %d]",
-                  (long long)n_item_chunks, CCF_CHUNK);
-    CRH_CHECK_ARG(n_user_chunks >= n_users && n_user_chunks <= ccf_max_chunks(2 * batch, n_users),
-                  "crh_ccfcrec_f32: n_user_chunks = %lld out of [n_users, n_users + 2 batch / %d]", (long long)n_user_chunks,
-                  CCF_CHUNK);
+    LG_CHECK_OWNER_COUNTS("crh_ccfcrec_f32", io, batch * rows, "batch * rows", uo, 2 * batch, "2 batch", CCF_CHUNK);
     LG_CHECK_IDS("crh_ccfcrec_f32", "user", user_min, user_max, user_rows);
     LG_CHECK_IDS("crh_ccfcrec_f32", "item", item_min, item_max, item_rows);
     CRH_CHECK_ARG(tau > 0.f && isfinite(tau), "crh_ccfcrec_f32: tau must be finite and > 0");
@@ -413,11 +402,7 @@ extern "C" int crh_ccfcrec_f32(const float* user_table, int64_t user_rows, const
     CcfArgs a;
     a.ut = user_table, a.vt = item_table, a.q = q;
     a.users = users, a.neg_users = neg_users, a.items = items;
-    a.item_ids = item_ids, a.item_ptr = item_ptr, a.item_rows = item_occ, a.item_chunk_ptr = item_chunk_ptr;
-    a.item_chunk_own = item_chunk_own;
-    a.user_ids = user_ids, a.user_ptr = user_ptr, a.user_rows = user_occ, a.user_chunk_ptr = user_chunk_ptr;
-    a.user_chunk_own = user_chunk_own;
-    a.n_items = n_items, a.n_item_chunks = n_item_chunks, a.n_users = n_users, a.n_user_chunks = n_user_chunks, a.batch = batch;
+    a.io = io, a.uo = uo, a.batch = batch;
     a.n_pos = n_pos, a.n_neg = n_neg, a.n_self = n_self, a.rows = (int)rows, a.d = d;
     a.inv_t = 1.f / tau;
     a.w_c = scale * lambda1 / (float)n_pos, a.w_s = scale * lambda1, a.w_r = scale * (1.f - lambda1);

@@ -216,8 +216,6 @@ struct GarWs {
     size_t bytes;
 };
 
-int64_t gar_max_chunks(int64_t occurrences, int64_t n_own) { return n_own + occurrences / GAR_CHUNK; }
-
 bool gar_shape_ok(int64_t batch, int d, int64_t n_items, int64_t n_users) {
     return batch >= 1 && batch < ((int64_t)1 << 31) && lg_width_ok(d) && n_items >= 1 && n_items <= 2 * batch &&
            n_users >= 1 && n_users <= batch;
@@ -232,8 +230,8 @@ GarWs gar_layout(void* base, int64_t batch, int d, int64_t n_items, int64_t n_us
     w.rec_a = c.take(batch * 4);
     w.rec_b = c.take(batch * 4);
     w.rinv = c.take(4);
-    w.part_u = c.take(gar_max_chunks(batch, n_users) * (d + 4));
-    w.part_i = c.take(gar_max_chunks(2 * batch, n_items) * (d + 4));
+    w.part_u = c.take(lg_max_chunks(batch, n_users, GAR_CHUNK) * (d + 4));
+    w.part_i = c.take(lg_max_chunks(2 * batch, n_items, GAR_CHUNK) * (d + 4));
     w.bytes = c.bytes;
     return w;
 }
@@ -242,15 +240,12 @@ struct GarArgs {
     const float *ut, *vt, *gen;
     int64_t user_rows, item_rows;
     const int32_t *users, *pos, *neg;
-    const int32_t *item_ids, *item_ptr, *item_occ, *item_chunk_ptr, *item_chunk_own;
-    const int32_t *user_ids, *user_ptr, *user_occ, *user_chunk_ptr, *user_chunk_own;
-    int64_t n_items, n_item_chunks, n_users, n_user_chunks, batch;
+    LgOwners io, uo;                // the inverse index of the items and of the users
+    int64_t batch;
     int d, cold_user;
     float alpha, beta, reg, scale;
     float *grad_user, *grad_item, *grad_gen, *loss;
 };
-
-const uint32_t* gar_u32(const int32_t* p) { return reinterpret_cast<const uint32_t*>(p); }
 
 template <int LPR>
 void gar_launch(const GarWs& w, const GarArgs& a, hipStream_t st) {
@@ -269,20 +264,18 @@ void gar_launch(const GarWs& w, const GarArgs& a, hipStream_t st) {
                            quads, a.grad_gen);
     }
     if (a.grad_user) {
-        hipLaunchKernelGGL((gar_chunk_kernel<LPR>), dim3((unsigned)a.n_user_chunks), dim3(64), 0, st, gar_u32(a.user_ptr),
-                           gar_u32(a.user_occ), a.user_chunk_ptr, a.user_chunk_own, a.n_users, a.batch, a.batch, a.d, w.gu,
-                           w.gu, w.part_u);
-        hipLaunchKernelGGL((gar_finish_kernel<LPR>), dim3((unsigned)((a.n_users + RG - 1) / RG)), dim3(64), 0, st, a.ut,
-                           a.user_rows, a.user_ids, gar_u32(a.user_ptr), a.user_chunk_ptr, a.n_users, a.d, w.part_u, w.rinv, 0,
-                           0, a.grad_user);
+        const LgOwners& o = a.uo;
+        hipLaunchKernelGGL((gar_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, lg_u32(o.ptr), lg_u32(o.occ),
+                           o.chunk_ptr, o.chunk_own, o.n, a.batch, a.batch, a.d, w.gu, w.gu, w.part_u);
+        hipLaunchKernelGGL((gar_finish_kernel<LPR>), dim3((unsigned)((o.n + RG - 1) / RG)), dim3(64), 0, st, a.ut, a.user_rows,
+                           o.ids, lg_u32(o.ptr), o.chunk_ptr, o.n, a.d, w.part_u, w.rinv, 0, 0, a.grad_user);
     }
     if (a.grad_item) {
-        hipLaunchKernelGGL((gar_chunk_kernel<LPR>), dim3((unsigned)a.n_item_chunks), dim3(64), 0, st, gar_u32(a.item_ptr),
-                           gar_u32(a.item_occ), a.item_chunk_ptr, a.item_chunk_own, a.n_items, a.batch, 2 * a.batch, a.d, w.gp,
-                           w.gn, w.part_i);
-        hipLaunchKernelGGL((gar_finish_kernel<LPR>), dim3((unsigned)((a.n_items + RG - 1) / RG)), dim3(64), 0, st, a.vt,
-                           a.item_rows, a.item_ids, gar_u32(a.item_ptr), a.item_chunk_ptr, a.n_items, a.d, w.part_i, w.rinv, 1,
-                           2, a.grad_item);
+        const LgOwners& o = a.io;
+        hipLaunchKernelGGL((gar_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, lg_u32(o.ptr), lg_u32(o.occ),
+                           o.chunk_ptr, o.chunk_own, o.n, a.batch, 2 * a.batch, a.d, w.gp, w.gn, w.part_i);
+        hipLaunchKernelGGL((gar_finish_kernel<LPR>), dim3((unsigned)((o.n + RG - 1) / RG)), dim3(64), 0, st, a.vt, a.item_rows,
+                           o.ids, lg_u32(o.ptr), o.chunk_ptr, o.n, a.d, w.part_i, w.rinv, 1, 2, a.grad_item);
     }
 }
 
@@ -306,21 +299,14 @@ extern "C" int crh_gar_f32(const float* user_table, int64_t user_rows, const flo
                            float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
     CRH_CHECK_ARG(user_table && item_table && gen, "crh_gar_f32: NULL table pointer");
     CRH_CHECK_ARG(users && pos && neg, "crh_gar_f32: NULL id pointer");
-    CRH_CHECK_ARG(item_ids && item_ptr && item_occ && item_chunk_ptr && item_chunk_own && user_ids && user_ptr && user_occ &&
-                      user_chunk_ptr && user_chunk_own,
-                  "crh_gar_f32: NULL inverse-index pointer");
+    const LgOwners io{item_ids, item_ptr, item_occ, item_chunk_ptr, item_chunk_own, n_items, n_item_chunks};
+    const LgOwners uo{user_ids, user_ptr, user_occ, user_chunk_ptr, user_chunk_own, n_users, n_user_chunks};
+    LG_CHECK_OWNER_PTRS("crh_gar_f32", io, uo);
     CRH_CHECK_ARG(grad_user || grad_item || grad_gen || loss_out, "crh_gar_f32: NULL gradients and loss: nothing to compute");
     LG_CHECK_WIDTH("crh_gar_f32", d);
     CRH_CHECK_ARG(batch >= 1 && batch < ((int64_t)1 << 31), "crh_gar_f32: batch = %lld must lie in [1, 2^31)",
                   (long long)batch);
-    CRH_CHECK_ARG(n_items >= 1 && n_items <= 2 * batch, "crh_gar_f32: n_items = %lld out of [1, 2 batch]", (long long)n_items);
-    CRH_CHECK_ARG(n_users >= 1 && n_users <= batch, "crh_gar_f32: n_users = %lld out of [1, batch]", (long long)n_users);
-    CRH_CHECK_ARG(n_item_chunks >= n_items && n_item_chunks <= gar_max_chunks(2 * batch, n_items),
-                  "crh_gar_f32: n_item_chunks = %lld out of [n_items, n_items + 2 batch / %d]", (long long)n_item_chunks,
-                  GAR_CHUNK);
-    CRH_CHECK_ARG(n_user_chunks >= n_users && n_user_chunks <= gar_max_chunks(batch, n_users),
-                  "crh_gar_f32: n_user_chunks = %lld out of [n_users, n_users + batch / %d]", (long long)n_user_chunks,
-                  GAR_CHUNK);
+    LG_CHECK_OWNER_COUNTS("crh_gar_f32", io, 2 * batch, "2 batch", uo, batch, "batch", GAR_CHUNK);
     LG_CHECK_IDS("crh_gar_f32", "user", user_min, user_max, user_rows);
     LG_CHECK_IDS("crh_gar_f32", "item", item_min, item_max, item_rows);
     CRH_CHECK_ARG(isfinite(alpha) && isfinite(beta) && isfinite(reg) && isfinite(scale),
@@ -333,11 +319,7 @@ extern "C" int crh_gar_f32(const float* user_table, int64_t user_rows, const flo
     GarArgs a;
     a.ut = user_table, a.vt = item_table, a.gen = gen, a.user_rows = user_rows, a.item_rows = item_rows;
     a.users = users, a.pos = pos, a.neg = neg;
-    a.item_ids = item_ids, a.item_ptr = item_ptr, a.item_occ = item_occ, a.item_chunk_ptr = item_chunk_ptr;
-    a.item_chunk_own = item_chunk_own;
-    a.user_ids = user_ids, a.user_ptr = user_ptr, a.user_occ = user_occ, a.user_chunk_ptr = user_chunk_ptr;
-    a.user_chunk_own = user_chunk_own;
-    a.n_items = n_items, a.n_item_chunks = n_item_chunks, a.n_users = n_users, a.n_user_chunks = n_user_chunks, a.batch = batch;
+    a.io = io, a.uo = uo, a.batch = batch;
     a.d = d, a.cold_user = cold_user != 0;
     a.alpha = alpha, a.beta = beta, a.reg = reg, a.scale = scale;
     a.grad_user = grad_user, a.grad_item = grad_item, a.grad_gen = grad_gen, a.loss = loss_out;

@@ -1,6 +1,7 @@
-// What the fused loss kernels (infonce.hip, table_nce.hip, clcrec.hip, ccfcrec.hip, aldi.hip) share: the wave and
-// lane-group sums, the lane-group coordinates, the front of the one-workgroup loss kernels, and on the host the workspace carver, the argument
-// checks with their messages and the dispatch on the lane-group width.
+// What the fused loss kernels (infonce.hip, table_nce.hip, clcrec.hip, ccfcrec.hip, aldi.hip, gar.hip, mtpr.hip) share:
+// the wave and lane-group sums, the lane-group coordinates, the front of the one-workgroup loss kernels, and on the host
+// the workspace carver, the argument checks with their messages, the owners' inverse index of a plan and the dispatch on
+// the lane-group width.
 //
 // A lane group is LPR = pow2(d / 4) lanes that hold one row of d floats, four columns per lane (16-byte loads); a wave
 // holds 64 / LPR rows at a time.
@@ -140,6 +141,38 @@ inline bool lg_width_ok(int d) { return d >= 4 && d <= 256 && d % 4 == 0; }
 #define LG_CHECK_IDS(fn, what, lo, hi, rows)                                                                       \
     CRH_CHECK_ARG((lo) >= 0 && (lo) <= (hi) && (hi) < (rows), "%s: %s ids [%d, %d] outside the %s table of %lld rows", \
                   fn, what, lo, hi, what, (long long)(rows))
+
+// One side (the users or the items) of a plan's inverse index, as ccfcrec.hip, gar.hip and mtpr.hip take it: the n
+// distinct owners (ids), their occurrences grouped by owner (ptr, occ) and cut into n_chunks chunks (chunk_ptr, chunk_own).
+struct LgOwners {
+    const int32_t *ids, *ptr, *occ, *chunk_ptr, *chunk_own;
+    int64_t n, n_chunks;
+    bool complete() const { return ids && ptr && occ && chunk_ptr && chunk_own; }
+};
+
+// the most chunks that `occurrences` occurrences of n_own owners are cut into
+inline int64_t lg_max_chunks(int64_t occurrences, int64_t n_own, int chunk) { return n_own + occurrences / chunk; }
+
+// (offsets and occurrences are read as unsigned by the chunk kernels)
+inline const uint32_t* lg_u32(const int32_t* p) { return reinterpret_cast<const uint32_t*>(p); }
+
+#define LG_CHECK_OWNER_PTRS(fn, items, users) \
+    CRH_CHECK_ARG((items).complete() && (users).complete(), "%s: NULL inverse-index pointer", fn)
+
+// the owners' and the chunks' counts of both sides; *_occ = a side's occurrences, *_txt = how the messages spell them
+#define LG_CHECK_OWNER_COUNTS(fn, items, item_occ, item_txt, users, user_occ, user_txt, chunk)                              \
+    do {                                                                                                                    \
+        CRH_CHECK_ARG((items).n >= 1 && (items).n <= (item_occ), "%s: n_items = %lld out of [1, %s]", fn,                   \
+                      (long long)(items).n, item_txt);                                                                      \
+        CRH_CHECK_ARG((users).n >= 1 && (users).n <= (user_occ), "%s: n_users = %lld out of [1, %s]", fn,                   \
+                      (long long)(users).n, user_txt);                                                                      \
+        CRH_CHECK_ARG((items).n_chunks >= (items).n && (items).n_chunks <= lg_max_chunks(item_occ, (items).n, chunk),       \
+                      "%s: n_item_chunks = %lld out of [n_items, n_items + %s / %d]", fn, (long long)(items).n_chunks,      \
+                      item_txt, chunk);                                                                                     \
+        CRH_CHECK_ARG((users).n_chunks >= (users).n && (users).n_chunks <= lg_max_chunks(user_occ, (users).n, chunk),       \
+                      "%s: n_user_chunks = %lld out of [n_users, n_users + %s / %d]", fn, (long long)(users).n_chunks,      \
+                      user_txt, chunk);                                                                                     \
+    } while (0)
 
 template <class... T>
 inline bool lg_aligned16(const T*... p) {

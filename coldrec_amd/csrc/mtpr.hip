@@ -542,8 +542,6 @@ struct MtprWs {
     size_t bytes;
 };
 
-int64_t mtpr_max_chunks(int64_t occurrences, int64_t n_own) { return n_own + occurrences / MTPR_CHUNK; }
-
 bool mtpr_width_ok(int d) { return d >= 4 && d <= 128 && d % 4 == 0; }
 
 bool mtpr_shape_ok(int64_t batch, int d, int64_t n_items, int64_t n_users) {
@@ -565,13 +563,11 @@ MtprWs mtpr_layout(void* base, int64_t batch, int d, int cold_user, int64_t n_it
     w.rec_b = c.take(batch * 4);
     w.part = c.take(parts * pe);
     w.chunk = c.take((parts + MTPR_SUM_CHUNK - 1) / MTPR_SUM_CHUNK * pe);
-    w.part_u = c.take(mtpr_max_chunks(batch, n_users) * wp);
-    w.part_i = c.take(mtpr_max_chunks(2 * batch, n_items) * wq);
+    w.part_u = c.take(lg_max_chunks(batch, n_users, MTPR_CHUNK) * wp);
+    w.part_i = c.take(lg_max_chunks(2 * batch, n_items, MTPR_CHUNK) * wq);
     w.bytes = c.bytes;
     return w;
 }
-
-const uint32_t* mtpr_u32(const int32_t* p) { return reinterpret_cast<const uint32_t*>(p); }
 
 template <bool CU>
 void mtpr_launch_tiles(const MtprK& k, hipStream_t st) {
@@ -584,19 +580,14 @@ void mtpr_launch_tiles(const MtprK& k, hipStream_t st) {
     }
 }
 
-struct MtprOwner {
-    const int32_t *ids, *ptr, *occ, *chunk_ptr, *chunk_own;
-    int64_t n, n_chunks;
-};
-
-void mtpr_owner_pass(const MtprOwner& o, const float* table, int64_t table_rows, int64_t occurrences, int w,
+void mtpr_owner_pass(const LgOwners& o, const float* table, int64_t table_rows, int64_t occurrences, int w,
                      const float* rows, float* part, float reg2, float* grad, hipStream_t st) {
     lg_dispatch_lpr(w, [&](auto lpr) {
         constexpr int LPR = decltype(lpr)::value, RG = 64 / LPR;
-        hipLaunchKernelGGL((mtpr_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, mtpr_u32(o.ptr),
-                           mtpr_u32(o.occ), o.chunk_ptr, o.chunk_own, o.n, occurrences, w, rows, part);
+        hipLaunchKernelGGL((mtpr_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, lg_u32(o.ptr), lg_u32(o.occ),
+                           o.chunk_ptr, o.chunk_own, o.n, occurrences, w, rows, part);
         hipLaunchKernelGGL((mtpr_finish_kernel<LPR>), dim3((unsigned)((o.n + RG - 1) / RG)), dim3(64), 0, st, table,
-                           table_rows, o.ids, mtpr_u32(o.ptr), o.chunk_ptr, o.n, w, part, reg2, grad);
+                           table_rows, o.ids, lg_u32(o.ptr), o.chunk_ptr, o.n, w, part, reg2, grad);
     });
 }
 
@@ -621,22 +612,15 @@ extern "C" int crh_mtpr_f32(const float* user_table, int64_t user_rows, const fl
                             float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
     CRH_CHECK_ARG(user_table && item_table && h && weu && wei, "crh_mtpr_f32: NULL table, content or projection pointer");
     CRH_CHECK_ARG(users && pos && neg, "crh_mtpr_f32: NULL id pointer");
-    CRH_CHECK_ARG(item_ids && item_ptr && item_occ && item_chunk_ptr && item_chunk_own && user_ids && user_ptr && user_occ &&
-                      user_chunk_ptr && user_chunk_own,
-                  "crh_mtpr_f32: NULL inverse-index pointer");
+    const LgOwners io{item_ids, item_ptr, item_occ, item_chunk_ptr, item_chunk_own, n_items, n_item_chunks};
+    const LgOwners uo{user_ids, user_ptr, user_occ, user_chunk_ptr, user_chunk_own, n_users, n_user_chunks};
+    LG_CHECK_OWNER_PTRS("crh_mtpr_f32", io, uo);
     CRH_CHECK_ARG(grad_user || grad_item || grad_h || grad_weu || grad_wei || loss_out,
                   "crh_mtpr_f32: NULL gradients and loss: nothing to compute");
     CRH_CHECK_ARG(mtpr_width_ok(d), "crh_mtpr_f32: d = %d must be a multiple of 4 in [4, 128]", d);
     CRH_CHECK_ARG(batch >= 1 && batch < ((int64_t)1 << 30), "crh_mtpr_f32: batch = %lld must lie in [1, 2^30)",
                   (long long)batch);
-    CRH_CHECK_ARG(n_items >= 1 && n_items <= 2 * batch, "crh_mtpr_f32: n_items = %lld out of [1, 2 batch]", (long long)n_items);
-    CRH_CHECK_ARG(n_users >= 1 && n_users <= batch, "crh_mtpr_f32: n_users = %lld out of [1, batch]", (long long)n_users);
-    CRH_CHECK_ARG(n_item_chunks >= n_items && n_item_chunks <= mtpr_max_chunks(2 * batch, n_items),
-                  "crh_mtpr_f32: n_item_chunks = %lld out of [n_items, n_items + 2 batch / %d]", (long long)n_item_chunks,
-                  MTPR_CHUNK);
-    CRH_CHECK_ARG(n_user_chunks >= n_users && n_user_chunks <= mtpr_max_chunks(batch, n_users),
-                  "crh_mtpr_f32: n_user_chunks = %lld out of [n_users, n_users + batch / %d]", (long long)n_user_chunks,
-                  MTPR_CHUNK);
+    LG_CHECK_OWNER_COUNTS("crh_mtpr_f32", io, 2 * batch, "2 batch", uo, batch, "batch", MTPR_CHUNK);
     LG_CHECK_IDS("crh_mtpr_f32", "user", user_min, user_max, user_rows);
     LG_CHECK_IDS("crh_mtpr_f32", "item", item_min, item_max, item_rows);
     CRH_CHECK_ARG(isfinite(wd1) && isfinite(scale), "crh_mtpr_f32: wd1 and scale must be finite");
@@ -669,14 +653,8 @@ extern "C" int crh_mtpr_f32(const float* user_table, int64_t user_rows, const fl
     }
     if (loss_out) hipLaunchKernelGGL(mtpr_loss_kernel, dim3(1), dim3(256), 0, st, w.rec_a, w.rec_b, batch, wd1, loss_out);
     const float reg2 = 2.f * wd1 * scale;
-    if (grad_user) {
-        const MtprOwner o{user_ids, user_ptr, user_occ, user_chunk_ptr, user_chunk_own, n_users, n_user_chunks};
-        mtpr_owner_pass(o, user_table, user_rows, batch, wp, w.gp, w.part_u, reg2, grad_user, st);
-    }
-    if (grad_item) {
-        const MtprOwner o{item_ids, item_ptr, item_occ, item_chunk_ptr, item_chunk_own, n_items, n_item_chunks};
-        mtpr_owner_pass(o, item_table, item_rows, 2 * batch, wq, w.gq, w.part_i, reg2, grad_item, st);
-    }
+    if (grad_user) mtpr_owner_pass(uo, user_table, user_rows, batch, wp, w.gp, w.part_u, reg2, grad_user, st);
+    if (grad_item) mtpr_owner_pass(io, item_table, item_rows, 2 * batch, wq, w.gq, w.part_i, reg2, grad_item, st);
     CRH_HIP(hipGetLastError());
     return CRH_OK;
 }

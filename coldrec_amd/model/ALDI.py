@@ -16,16 +16,12 @@ Same random streams as the reference: the towers are built on the CPU in its ord
 its default initialisation before ``trunc_normal_`` overwrites the weight), the triples come from the MT19937-exact
 pairwise sampler.
 """
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..train import dp_from_env
-from ..util.utils import epoch_triples
-from .BaseRecommender import BaseColdStartTrainer
+from .FusedLossTrainer import FusedLossTrainer, load_backbone_tables
 from .MF import _check_width, _require_gpu
 
 
@@ -102,18 +98,7 @@ class ALDI_Learner(nn.Module):
         hidden = int(getattr(args, 'aldi_hidden', 200))
         self.user_tower = ALDITower(emb_size, hidden, emb_size)
         self.item_tower = ALDITower(data.item_content_dim, hidden, emb_size)
-        stem = f'./emb/{args.dataset}_cold_{args.cold_object}_{args.backbone}'
-        paths = (stem + '_user_emb.pt', stem + '_item_emb.pt')
-        for p in paths:
-            if not os.path.isfile(p):
-                raise FileNotFoundError(
-                    f'ALDI requires {p}. Train the backbone first '
-                    f'(e.g. main.py --model {args.backbone} --dataset {args.dataset} '
-                    f'--cold_object {args.cold_object} --save_emb true) or set --backbone to match '
-                    f'existing files under ./emb/.')
-        tables = [torch.load(p, map_location='cpu').detach().float().contiguous() for p in paths]
-        if tables[0].shape != (data.user_num, emb_size) or tables[1].shape != (data.item_num, emb_size):
-            raise ValueError(f'ALDI: the tables under {stem}_*_emb.pt do not fit this dataset and --emb_size {emb_size}')
+        tables = load_backbone_tables('ALDI', args, data, emb_size)
         self.register_buffer('user_emb', tables[0], persistent=False)        # the frozen teacher
         self.register_buffer('item_emb', tables[1], persistent=False)
         self.register_buffer('pos_item_weights',
@@ -150,8 +135,10 @@ class ALDI_Learner(nn.Module):
         return self.item_tower(self.item_content[idx])
 
 
-class ALDI(BaseColdStartTrainer):
+class ALDI(FusedLossTrainer):
     fused_eval = False       # batch_predict composes two products; the fused route is _eval_parts'
+    LOSS_TERMS = ('L_bpr', 'L_rate', 'L_rank', 'L_iden', 'total')
+    TABLES = ('warm_user_emb', 'cold_user_emb', 'item_emb')
 
     def __init__(self, config):
         super().__init__(config)
@@ -161,15 +148,18 @@ class ALDI(BaseColdStartTrainer):
         self._warm_idx = self._cold_idx = None
 
     def _item_sets(self):
-        if self._warm_idx is None:
-            dev = self.model.item_emb.device
+        dev = self.model.item_emb.device
+        if self._warm_idx is None or self._warm_idx.device != dev:
             self._warm_idx = torch.as_tensor(np.asarray(self.data.mapped_warm_item_idx), dtype=torch.long, device=dev)
             self._cold_idx = torch.as_tensor(np.asarray(self.data.mapped_cold_item_idx), dtype=torch.long, device=dev)
         return self._warm_idx, self._cold_idx
 
-    def _tables(self):
+    def _optimizers(self, model):
+        return [torch.optim.Adam(model.param_groups(self.reg), lr=self.lr)]
+
+    def _current_tables(self):
         """(teacher users, generated users, teacher items with the cold rows generated) with the towers in eval mode."""
-        m = self.model
+        m = self.model.eval()
         _, cold = self._item_sets()
         item_emb = m.item_emb.clone()
         if cold.numel():
@@ -180,60 +170,6 @@ class ALDI(BaseColdStartTrainer):
         if getattr(self, 'warm_user_emb', None) is None:
             return None
         return [(self.warm_user_emb, self.data.mapped_cold_item_idx), (self.cold_user_emb, self.data.mapped_warm_item_idx)]
-
-    def train(self):
-        _require_gpu(self.device)
-        if dp_from_env() is not None:
-            raise RuntimeError('ALDI: data-parallel training is not built; run it on one GPU')
-        model = self.model.to(self.device)
-        self._warm_idx = self._cold_idx = None
-        optimizer = torch.optim.Adam(model.param_groups(self.reg), lr=self.lr)
-        B = self.batch_size
-        self.batch_losses = np.zeros((0, 5))
-        self.timer(start=True)
-        epoch = -1
-        for epoch in range(self.maxEpoch):
-            model.train()
-            ep = epoch_triples(self.data, B)            # the whole epoch from the reference's stream, one upload
-            id_range = ((int(ep[0].min()), int(ep[0].max())),
-                        (int(min(ep[1].min(), ep[2].min())), int(max(ep[1].max(), ep[2].max()))))
-            eu, ei, ej = (torch.from_numpy(x).to(self.device) for x in ep)
-            n_steps = (eu.shape[0] + B - 1) // B
-            terms = torch.zeros((n_steps, 5), dtype=torch.float32, device=self.device)
-            for n, lo in enumerate(range(0, eu.shape[0], B)):
-                batch_loss = model.loss(eu[lo:lo + B], ei[lo:lo + B], ej[lo:lo + B], id_range)
-                optimizer.zero_grad()
-                batch_loss.backward()
-                optimizer.step()
-                terms[n] = model.last_terms
-            host = terms.cpu().numpy().astype(float)
-            for n in range(0, n_steps, 50):
-                print('training:', epoch + 1, 'batch', n, 'batch_loss:', float(host[n, 4]))
-            self.batch_losses = np.concatenate([self.batch_losses, host])
-            with torch.no_grad():
-                model.eval()
-                self.warm_user_emb, self.cold_user_emb, self.item_emb = self._tables()
-                if epoch % self.eval_every == 0:
-                    self.fast_evaluation(epoch, valid_type='all')
-                    if self.early_stop_flag and self.early_stop_patience <= 0:
-                        break
-        self.epochs_ran = (epoch + 1) if self.maxEpoch > 0 else 0
-        self.timer(start=False)
-        model.eval()
-        self.warm_user_emb, self.cold_user_emb, self.item_emb = \
-            self.best_warm_user_emb, self.best_cold_user_emb, self.best_item_emb
-        if self.args.save_emb:
-            a = self.args
-            os.makedirs('./emb', exist_ok=True)
-            stem = f'./emb/{a.dataset}_cold_{a.cold_object}_{a.model}'
-            torch.save(self.warm_user_emb, stem + '_warm_user_emb.pt')
-            torch.save(self.cold_user_emb, stem + '_cold_user_emb.pt')
-            torch.save(self.item_emb, stem + '_item_emb.pt')
-
-    def save(self):
-        with torch.no_grad():
-            self.model.eval()
-            self.best_warm_user_emb, self.best_cold_user_emb, self.best_item_emb = self._tables()
 
     def predict(self, u):
         with torch.no_grad():

@@ -7,15 +7,12 @@ HIP kernel (csrc/ccfcrec.hip, ``ops.ccfcrec``): the five loss terms and the dens
 encoder's output, deterministic, without atomics.  Same random streams as the reference: module construction order for
 the tables, CPython's ``random`` and NumPy's generator for the samples (the C++ sampler).
 """
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..train import dp_from_env
-from .BaseRecommender import BaseColdStartTrainer
+from .FusedLossTrainer import FusedLossTrainer, load_backbone_tables
 from .MF import _check_width, _require_gpu
 
 
@@ -67,20 +64,8 @@ class CCFCRec_Learner(nn.Module):
         self.attr_W2 = nn.Parameter(torch.empty(A, 1))
         self.pretrained = bool(args.pretrain)
         if self.pretrained:
-            stem = f'./emb/{args.dataset}_cold_{args.cold_object}_{args.backbone}'
-            paths = (stem + '_user_emb.pt', stem + '_item_emb.pt')
-            for p in paths:
-                if not os.path.isfile(p):
-                    raise FileNotFoundError(
-                        f'CCFCRec --pretrain requires {p}. Train the backbone first '
-                        f'(e.g. main.py --model {args.backbone} --dataset {args.dataset} '
-                        f'--cold_object {args.cold_object}) or set --backbone to match '
-                        f'existing files under ./emb/.')
             update = bool(args.pretrain_update)
-            tables = [torch.load(p, map_location='cpu').detach().float().contiguous() for p in paths]
-            if tables[0].shape[0] != data.user_num or tables[1].shape[0] != data.item_num \
-                    or tables[0].shape[1] != tables[1].shape[1]:
-                raise ValueError(f'CCFCRec --pretrain: the tables under {stem}_*_emb.pt do not fit this dataset')
+            tables = load_backbone_tables('CCFCRec --pretrain', args, data, save_flag='')
             self.user_embedding = nn.Parameter(tables[0], requires_grad=update)
             self.item_embedding = nn.Parameter(tables[1], requires_grad=update)
         else:
@@ -131,8 +116,9 @@ class CCFCRec_Learner(nn.Module):
         return total
 
 
-class CCFCRec(BaseColdStartTrainer):
-    fused_eval = True        # batch_predict below is the stock user_emb[users] @ item_emb.T
+class CCFCRec(FusedLossTrainer):
+    fused_eval = True        # the base class's batch_predict is the stock user_emb[users] @ item_emb.T
+    LOSS_TERMS = ('L_c', 'L_s', 'L_r1', 'L_r2', 'total')
     UPLOAD_BATCHES = 16      # batches of ids uploaded at once (16 x 4096 records x 248 ids of the defaults are 65 MB)
 
     def __init__(self, config):
@@ -153,69 +139,14 @@ class CCFCRec(BaseColdStartTrainer):
         item_emb[cold] = self.model(cold, cold).detach()
         return item_emb
 
-    def train(self):
-        _require_gpu(self.device)
-        if dp_from_env() is not None:
-            raise RuntimeError('CCFCRec: data-parallel training is not built; run it on one GPU')
-        model = self.model.to(self.device)
-        optimizer = torch.optim.Adam(model.parameters(), lr=self.lr)
-        B, (P, N, S), s = self.batch_size, self.shape, self.data.sampler
-        self.batch_losses = np.zeros((0, 5))
-        self.timer(start=True)
-        epoch = -1
-        for epoch in range(self.maxEpoch):
-            model.train()
-            s.pull_python_state()
-            s.pull_numpy_state()                        # (the positives come from NumPy's global stream)
-            ep = s.epoch_ccfcrec(P, N, S)               # the whole epoch from the reference's streams, in one host call
-            s.push_numpy_state()
-            s.push_python_state()
-            n_rec = ep[0].shape[0]
-            n_steps = (n_rec + B - 1) // B
-            terms = torch.zeros((n_steps, 5), dtype=torch.float32, device=self.device)
-            block = B * self.UPLOAD_BATCHES
-            for n, lo in enumerate(range(0, n_rec, B)):
-                if lo % block == 0:
-                    dev = [torch.from_numpy(a[lo:lo + block]).to(self.device) for a in ep]
-                o = lo % block
-                batch_loss = model.loss(*(t[o:o + B] for t in dev))
-                optimizer.zero_grad()
-                batch_loss.backward()
-                optimizer.step()
-                terms[n] = model.last_terms
-            host = terms.cpu().numpy().astype(float)
-            for n in range(0, n_steps, 50):
-                print('training:', epoch + 1, 'batch', n, 'batch_loss:', float(host[n, 4]))
-            self.batch_losses = np.concatenate([self.batch_losses, host])
-            with torch.no_grad():
-                model.eval()
-                self.user_emb = self.model.user_embedding.detach().clone()
-                self.item_emb = self._item_embeddings_for_eval()
-                if epoch % self.eval_every == 0:
-                    self.fast_evaluation(epoch, valid_type='all')
-                    if self.early_stop_flag and self.early_stop_patience <= 0:
-                        break
-        self.epochs_ran = (epoch + 1) if self.maxEpoch > 0 else 0
-        self.timer(start=False)
-        model.eval()
-        self.user_emb, self.item_emb = self.best_user_emb, self.best_item_emb
-        if self.args.save_emb:
-            a = self.args
-            os.makedirs('./emb', exist_ok=True)
-            stem = f'./emb/{a.dataset}_cold_{a.cold_object}_{a.model}'
-            torch.save(self.user_emb, stem + '_user_emb.pt')
-            torch.save(self.item_emb, stem + '_item_emb.pt')
+    def _current_tables(self):
+        return self.model.user_embedding.detach().clone(), self._item_embeddings_for_eval()
 
-    def save(self):
-        with torch.no_grad():
-            self.best_user_emb = self.model.user_embedding.detach().clone()
-            self.best_item_emb = self._item_embeddings_for_eval()
-
-    def predict(self, u):
-        with torch.no_grad():
-            return (self.item_emb @ self.user_emb[self.data.get_user_id(u)]).cpu().numpy()
-
-    def batch_predict(self, users):
-        with torch.no_grad():
-            users = torch.as_tensor(self.data.get_user_id_list(users), device=self.device)
-            return self.user_emb[users] @ self.item_emb.T
+    def _epoch_batches(self):
+        s = self.data.sampler
+        s.pull_python_state()
+        s.pull_numpy_state()                        # (the positives come from NumPy's global stream)
+        ep = s.epoch_ccfcrec(*self.shape)           # the whole epoch from the reference's streams, in one host call
+        s.push_numpy_state()
+        s.push_python_state()
+        return self._block_batches(ep)

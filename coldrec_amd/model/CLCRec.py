@@ -13,8 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from ..train import dp_from_env
-from .BaseRecommender import BaseColdStartTrainer
+from .FusedLossTrainer import FusedLossTrainer
 from .MF import _check_width, _require_gpu
 
 
@@ -94,8 +93,9 @@ class CLCRec_Learner(nn.Module):
         return self.embedding_dict['user_emb'], self.embedding_dict['item_emb'], feature[self.data.mapped_cold_item_idx]
 
 
-class CLCRec(BaseColdStartTrainer):
-    fused_eval = True        # batch_predict below is the stock user_emb[users] @ item_emb.T
+class CLCRec(FusedLossTrainer):
+    fused_eval = True        # the base class's batch_predict is the stock user_emb[users] @ item_emb.T
+    LOSS_TERMS = ('L1', 'L2', 'R', 'total')
     UPLOAD_BATCHES = 64      # batches of ids uploaded at once (an epoch of 800 k records x 129 ids is 413 MB)
 
     def __init__(self, config):
@@ -105,72 +105,15 @@ class CLCRec(BaseColdStartTrainer):
         _check_width('CLCRec', '--emb_size', self.emb_size)
         self.model = CLCRec_Learner(self.args, self.data, self.emb_size, self.device)
 
-    def _snapshot(self):
+    def _current_tables(self):
         u, i, cold = self.model.get_all_embs()
         u, i = u.detach().clone(), i.detach().clone()
         i[torch.as_tensor(self.data.mapped_cold_item_idx, dtype=torch.long, device=i.device)] = cold
         return u, i
 
-    def train(self):
-        _require_gpu(self.device)
-        if dp_from_env() is not None:
-            raise RuntimeError('CLCRec: data-parallel training is not built; run it on one GPU')
-        model = self.model.to(self.device)
-        optimizer = torch.optim.Adam(model.parameters(), lr=self.lr)
-        B, G, s = self.batch_size, int(self.args.num_neg), self.data.sampler
-        self.batch_losses = np.zeros((0, 4))
-        self.timer(start=True)
-        epoch = -1
-        for epoch in range(self.maxEpoch):
-            model.train()
-            s.pull_python_state()
-            eu, ei = s.epoch_clcrec(G)                  # the whole epoch from the reference's stream, in one host call
-            s.push_python_state()
-            n_steps = (eu.shape[0] + B - 1) // B
-            terms = torch.zeros((n_steps, 4), dtype=torch.float32, device=self.device)
-            block = B * self.UPLOAD_BATCHES
-            for n, lo in enumerate(range(0, eu.shape[0], B)):
-                if lo % block == 0:
-                    du = torch.from_numpy(eu[lo:lo + block]).to(self.device)
-                    di = torch.from_numpy(ei[lo:lo + block]).to(self.device)
-                o = lo % block
-                batch_loss = model.loss(du[o:o + B], di[o:o + B])
-                optimizer.zero_grad()
-                batch_loss.backward()
-                optimizer.step()
-                terms[n] = model.last_terms
-            host = terms.cpu().numpy().astype(float)
-            for n in range(0, n_steps, 50):
-                print('training:', epoch + 1, 'batch', n, 'batch_loss:', float(host[n, 3]))
-            self.batch_losses = np.concatenate([self.batch_losses, host])
-            with torch.no_grad():
-                model.eval()
-                self.user_emb, self.item_emb = self._snapshot()
-                if epoch % self.eval_every == 0:
-                    self.fast_evaluation(epoch, valid_type='all')
-                    if self.early_stop_flag and self.early_stop_patience <= 0:
-                        break
-        self.epochs_ran = (epoch + 1) if self.maxEpoch > 0 else 0
-        self.timer(start=False)
-        model.eval()
-        self.user_emb, self.item_emb = self.best_user_emb, self.best_item_emb
-        if self.args.save_emb:
-            import os
-            a = self.args
-            os.makedirs('./emb', exist_ok=True)
-            stem = f'./emb/{a.dataset}_cold_{a.cold_object}_{a.model}'
-            torch.save(self.user_emb, stem + '_user_emb.pt')
-            torch.save(self.item_emb, stem + '_item_emb.pt')
-
-    def save(self):
-        with torch.no_grad():
-            self.best_user_emb, self.best_item_emb = self._snapshot()
-
-    def predict(self, u):
-        with torch.no_grad():
-            return (self.item_emb @ self.user_emb[self.data.get_user_id(u)]).cpu().numpy()
-
-    def batch_predict(self, users):
-        with torch.no_grad():
-            users = torch.as_tensor(self.data.get_user_id_list(users), device=self.device)
-            return self.user_emb[users] @ self.item_emb.T
+    def _epoch_batches(self):
+        s = self.data.sampler
+        s.pull_python_state()
+        eu, ei = s.epoch_clcrec(int(self.args.num_neg))    # the whole epoch from the reference's stream, in one host call
+        s.push_python_state()
+        return self._block_batches((eu, ei))

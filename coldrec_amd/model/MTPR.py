@@ -21,16 +21,12 @@ Embedding Q, then randn + xavier_uniform_ for W, weu, wei on the CPU generator; 
 pairwise sampler.  (The reference draws on its device: run on a GPU it would take the device generator's stream.  This
 trainer always draws on the CPU, as the G25 fixture's runs do.)
 """
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..train import dp_from_env
-from ..util.utils import epoch_triples
-from .BaseRecommender import BaseColdStartTrainer
+from .FusedLossTrainer import FusedLossTrainer
 from .MF import _require_gpu
 
 
@@ -130,8 +126,9 @@ class MTPR_Learner(nn.Module):
         return self.P.weight @ self.weu, torch.cat([self.Q.weight, cw], 1) @ self.wei
 
 
-class MTPR(BaseColdStartTrainer):
-    fused_eval = True        # batch_predict below is the stock user_emb[users] @ item_emb.T
+class MTPR(FusedLossTrainer):
+    fused_eval = True        # the base class's batch_predict is the stock user_emb[users] @ item_emb.T
+    LOSS_TERMS = ('L_i', 'L_f', 'L_if', 'L_fi', 'regs', 'batch_loss')
 
     def __init__(self, config):
         super().__init__(config)
@@ -146,70 +143,24 @@ class MTPR(BaseColdStartTrainer):
             raise ValueError('MTPR: --shard_graph is not built (there is no graph to shard); run it on one GPU')
         self.model = MTPR_Learner(a, self.data, self.emb_size, self.device)      # built on the CPU
 
-    def train(self):
-        _require_gpu(self.device)
-        if dp_from_env() is not None:
-            raise RuntimeError('MTPR: data-parallel training is not built; run it on one GPU')
-        model = self.model.to(self.device)
+    def _optimizers(self, model):
         a = self.args
-        opt_ctx = torch.optim.Adam([model.W, model.weu], lr=float(a.p_ctx[0]))
-        opt_proj = torch.optim.Adam([model.wei], lr=float(a.p_proj[0]))
-        B = self.batch_size
-        self.batch_losses = np.zeros((0, 6))
-        self.timer(start=True)
-        epoch = -1
-        for epoch in range(self.maxEpoch):
-            model.train()
-            ep = epoch_triples(self.data, B)            # the whole epoch from the reference's stream, one upload
-            id_range = ((int(ep[0].min()), int(ep[0].max())),
-                        (int(min(ep[1].min(), ep[2].min())), int(max(ep[1].max(), ep[2].max()))))
-            eu, ei, ej = (torch.from_numpy(x).to(self.device) for x in ep)
-            n_steps = (eu.shape[0] + B - 1) // B
-            terms = torch.zeros((n_steps, 6), dtype=torch.float32, device=self.device)
-            for n, lo in enumerate(range(0, eu.shape[0], B)):
-                total = model.loss(eu[lo:lo + B], ei[lo:lo + B], ej[lo:lo + B], id_range)
-                rw = model.weight_regs()
-                batch_loss = total + rw
-                opt_ctx.zero_grad()
-                opt_proj.zero_grad()
-                batch_loss.backward()
-                model.step_tables()
-                opt_ctx.step()
-                opt_proj.step()
-                with torch.no_grad():                   # [L_i, L_f, L_if, L_fi, regs, batch_loss]
-                    terms[n, :4] = model.last_terms[:4]
-                    terms[n, 4] = model.last_terms[4] + rw
-                    terms[n, 5] = batch_loss
-            host = terms.cpu().numpy().astype(float)
-            for n in range(0, n_steps, 50):
-                print('training:', epoch + 1, 'batch', n, 'batch_loss:', float(host[n, 5]))
-            self.batch_losses = np.concatenate([self.batch_losses, host])
-            with torch.no_grad():
-                model.eval()
-                self.user_emb, self.item_emb = model()
-                if epoch % self.eval_every == 0:
-                    self.fast_evaluation(epoch, valid_type='all')
-                    if self.early_stop_flag and self.early_stop_patience <= 0:
-                        break
-        self.epochs_ran = (epoch + 1) if self.maxEpoch > 0 else 0
-        self.timer(start=False)
-        model.eval()
-        self.user_emb, self.item_emb = self.best_user_emb, self.best_item_emb
-        if a.save_emb:
-            os.makedirs('./emb', exist_ok=True)
-            stem = f'./emb/{a.dataset}_cold_{a.cold_object}_{a.model}'
-            torch.save(self.user_emb, stem + '_user_emb.pt')
-            torch.save(self.item_emb, stem + '_item_emb.pt')
+        return [torch.optim.Adam([model.W, model.weu], lr=float(a.p_ctx[0])),
+                torch.optim.Adam([model.wei], lr=float(a.p_proj[0]))]
 
-    def save(self):
+    def _step(self, model, opts, batch):
+        total = model.loss(*batch)
+        rw = model.weight_regs()
+        batch_loss = total + rw
+        for opt in opts:
+            opt.zero_grad()
+        batch_loss.backward()
+        model.step_tables()
+        for opt in opts:
+            opt.step()
         with torch.no_grad():
-            self.best_user_emb, self.best_item_emb = self.model()
+            t = model.last_terms
+            return torch.cat([t[:4], (t[4] + rw).reshape(1), batch_loss.reshape(1)])
 
-    def predict(self, u):
-        with torch.no_grad():
-            return (self.item_emb @ self.user_emb[self.data.get_user_id(u)]).cpu().numpy()
-
-    def batch_predict(self, users):
-        with torch.no_grad():
-            users = torch.as_tensor(self.data.get_user_id_list(users), device=self.device)
-            return self.user_emb[users] @ self.item_emb.T
+    def _current_tables(self):
+        return self.model()

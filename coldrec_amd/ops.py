@@ -908,7 +908,25 @@ def _grad_buffer(op: str, what: str, g, like: torch.Tensor, want: bool, overwrit
     return g
 
 
-_AT_LEAST = {1: "one element", 4: "four elements", 5: "five elements"}
+def _check_width(op: str, d: int, widest: int = 256) -> None:
+    if d % 4 != 0 or d < 4 or d > widest:
+        raise RuntimeError(f"{op}: width {d} must be a multiple of 4 in [4, {widest}]")
+
+
+def _check_one_device(op: str, whose: str, dev, *tensors) -> None:
+    for t in tensors:
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{op}: every tensor must be on {whose} device")
+
+
+def _check_ids_in_tables(op: str, what: str, user_range, item_range, user_table, item_table) -> None:
+    """what: "ids", or "the plan's ids" where the ranges were measured when the plan was made."""
+    if user_range[0] < 0 or user_range[1] >= user_table.shape[0] or item_range[0] < 0 \
+            or item_range[1] >= item_table.shape[0]:
+        raise RuntimeError(f"{op}: {what} lie outside the tables")
+
+
+_AT_LEAST = {1: "one element", 4: "four elements", 5: "five elements", 6: "six elements"}
 
 
 def _loss_buffer(op: str, loss, n: int, device) -> torch.Tensor:
@@ -952,9 +970,7 @@ def infonce(view1: torch.Tensor, view2: torch.Tensor, tau: float, b_cos: bool = 
     _check_2d_f32("infonce", "views", view1, view2)
     if view1.shape[1] != view2.shape[1]:
         raise RuntimeError("infonce: views differ in width")
-    for t in (view2, rows1, rows2, n_dev, grad1, grad2, loss, workspace):
-        if t is not None and t.device != dev:
-            raise RuntimeError("infonce: every tensor must be on the views' device")
+    _check_one_device("infonce", "the views'", dev, view2, rows1, rows2, n_dev, grad1, grad2, loss, workspace)
     for r in (rows1, rows2):
         if r is not None and (r.dtype != torch.int32 or not r.is_contiguous() or r.dim() != 1):
             raise RuntimeError("infonce: row ids must be contiguous 1-D int32")
@@ -1007,9 +1023,7 @@ def table_nce(ctx: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, tau: fl
     _check_2d_f32("table_nce", "ctx and table", ctx, table)
     if ctx.shape != table.shape:
         raise RuntimeError("table_nce: ctx and table differ in shape")
-    for t in (table, idx, n_dev, grad_ctx, grad_table, loss, workspace):
-        if t is not None and t.device != dev:
-            raise RuntimeError("table_nce: every tensor must be on ctx's device")
+    _check_one_device("table_nce", "ctx's", dev, table, idx, n_dev, grad_ctx, grad_table, loss, workspace)
     if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.dim() != 1:
         raise RuntimeError("table_nce: row ids must be contiguous 1-D int32")
     if n_dev is not None and (n_dev.dtype != torch.int32 or n_dev.numel() < 1):
@@ -1067,6 +1081,24 @@ def _owner_chunks(ids: torch.Tensor, chunk: int):
     return uniq, order, ptr, chunk_ptr, chunk_own, inv
 
 
+def _owner_index(items: torch.Tensor, users: torch.Tensor, chunk: int) -> dict:
+    """The inverse-index half of a plan: ``_owner_chunks`` of the item and of the user occurrences as int32 tensors, with
+    the counts the kernels take."""
+    out = {}
+    for side, ids in (("item", items), ("user", users)):
+        own_ids, occ, ptr, chunk_ptr, chunk_own = (t.to(torch.int32).contiguous() for t in _owner_chunks(ids, chunk)[:5])
+        out.update({f"n_{side}s": int(own_ids.shape[0]), f"n_{side}_chunks": int(chunk_own.shape[0]), f"{side}_ids": own_ids,
+                    f"{side}_ptr": ptr, f"{side}_occ": occ, f"{side}_chunk_ptr": chunk_ptr, f"{side}_chunk_own": chunk_own})
+    return out
+
+
+def _check_ids_in_plan(op: str, user_range, item_range, n_users: Optional[int], n_items: Optional[int]) -> None:
+    if n_users is not None and (user_range[0] < 0 or user_range[1] >= n_users):
+        raise RuntimeError(f"{op}: user id outside the user table")
+    if n_items is not None and (item_range[0] < 0 or item_range[1] >= n_items):
+        raise RuntimeError(f"{op}: item id outside the item table")
+
+
 def clcrec_plan(users: torch.Tensor, items: torch.Tensor, n_users: Optional[int] = None,
                 n_items: Optional[int] = None) -> dict:
     """The index side of one crh_clcrec_f32 step.  users (B,), items (B, 1 + G): integer device tensors (column 0 = the
@@ -1113,19 +1145,15 @@ def clcrec(user_table: torch.Tensor, item_table: torch.Tensor, feat: torch.Tenso
     d = user_table.shape[1]
     if item_table.shape[1] != d or feat.shape[1] != d:
         raise RuntimeError("clcrec: tables and feat differ in width")
-    if d % 4 != 0 or d < 4 or d > 256:
-        raise RuntimeError(f"clcrec: width {d} must be a multiple of 4 in [4, 256]")
+    _check_width("clcrec", d)
     B, G, S = plan["batch"], plan["n_neg"], plan["n_slots"]
     if feat.shape[0] != S:
         raise RuntimeError("clcrec: feat must have one row per slot of the plan")
-    if plan["user_range"][0] < 0 or plan["user_range"][1] >= user_table.shape[0] or plan["item_range"][0] < 0 \
-            or plan["item_range"][1] >= item_table.shape[0]:
-        raise RuntimeError("clcrec: the plan's ids lie outside the tables")
+    _check_ids_in_tables("clcrec", "the plan's ids", plan["user_range"], plan["item_range"], user_table, item_table)
     if mix_count.dtype != torch.int32 or not mix_count.is_contiguous() or mix_count.numel() != B * (1 + G):
         raise RuntimeError("clcrec: mix_count must be a contiguous int32 tensor of B * (1 + G) elements")
-    for t in (item_table, feat, mix_count, plan["users"], grad_user, grad_item, grad_feat, loss, workspace):
-        if t is not None and t.device != dev:
-            raise RuntimeError("clcrec: every tensor must be on the tables' device")
+    _check_one_device("clcrec", "the tables'", dev, item_table, feat, mix_count, plan["users"], grad_user, grad_item,
+                      grad_feat, loss, workspace)
 
     grad_user = _grad_buffer("clcrec", "the tables' shapes", grad_user, user_table, want_user, False)
     grad_item = _grad_buffer("clcrec", "the tables' shapes", grad_item, item_table, want_item, False)
@@ -1183,25 +1211,15 @@ def ccfcrec_plan(users: torch.Tensor, items: torch.Tensor, neg_users: torch.Tens
     ts = (users, items, neg_users, pos, neg, self_neg)
     if any(t.dtype.is_floating_point or t.device != users.device for t in ts):
         raise RuntimeError("ccfcrec_plan: the six index tensors must be integer tensors on one device")
-    i32 = torch.int32
     P, N, S = int(pos.shape[1]), int(neg.shape[2]), int(self_neg.shape[1])
     flat = torch.cat([items.long().view(B, 1), pos.long(), neg.long().reshape(B, P * N), self_neg.long()], 1).reshape(-1)
     both = torch.cat([users.long(), neg_users.long()])
     user_range, item_range = (int(both.min()), int(both.max())), (int(flat.min()), int(flat.max()))
-    if n_users is not None and (user_range[0] < 0 or user_range[1] >= n_users):
-        raise RuntimeError("ccfcrec_plan: user id outside the user table")
-    if n_items is not None and (item_range[0] < 0 or item_range[1] >= n_items):
-        raise RuntimeError("ccfcrec_plan: item id outside the item table")
-    chunk = int(_lib.lib().crh_ccfcrec_chunk_rows())
-    item_ids, item_occ, item_ptr, item_chunk_ptr, item_chunk_own, _ = _owner_chunks(flat, chunk)
-    user_ids, user_occ, user_ptr, user_chunk_ptr, user_chunk_own, _ = _owner_chunks(both, chunk)
-    c = lambda t: t.to(i32).contiguous()
-    return dict(batch=B, n_pos=P, n_neg=N, n_self=S, n_items=int(item_ids.shape[0]), n_users=int(user_ids.shape[0]),
-                n_item_chunks=int(item_chunk_own.shape[0]), n_user_chunks=int(user_chunk_own.shape[0]),
-                user_range=user_range, item_range=item_range, users=c(both[:B]), neg_users=c(both[B:]), items=c(flat),
-                item_ids=c(item_ids), item_ptr=c(item_ptr), item_occ=c(item_occ), item_chunk_ptr=c(item_chunk_ptr),
-                item_chunk_own=c(item_chunk_own), user_ids=c(user_ids), user_ptr=c(user_ptr), user_occ=c(user_occ),
-                user_chunk_ptr=c(user_chunk_ptr), user_chunk_own=c(user_chunk_own))
+    _check_ids_in_plan("ccfcrec_plan", user_range, item_range, n_users, n_items)
+    c = lambda t: t.to(torch.int32).contiguous()
+    return dict(batch=B, n_pos=P, n_neg=N, n_self=S, user_range=user_range, item_range=item_range, users=c(both[:B]),
+                neg_users=c(both[B:]), items=c(flat),
+                **_owner_index(flat, both, int(_lib.lib().crh_ccfcrec_chunk_rows())))
 
 
 def ccfcrec(user_table: torch.Tensor, item_table: torch.Tensor, q: torch.Tensor, plan: dict, tau: float, lambda1: float,
@@ -1218,20 +1236,16 @@ def ccfcrec(user_table: torch.Tensor, item_table: torch.Tensor, q: torch.Tensor,
     d = user_table.shape[1]
     if item_table.shape[1] != d or q.shape[1] != d:
         raise RuntimeError("ccfcrec: tables and q differ in width")
-    if d % 4 != 0 or d < 4 or d > 256:
-        raise RuntimeError(f"ccfcrec: width {d} must be a multiple of 4 in [4, 256]")
+    _check_width("ccfcrec", d)
     B, P, N, S = plan["batch"], plan["n_pos"], plan["n_neg"], plan["n_self"]
     if ccfcrec_rows(P, N, S) > ccfcrec_max_rows():
         raise RuntimeError(f"ccfcrec: 1 + P + P N + S = {ccfcrec_rows(P, N, S)} rows per record exceed the cap "
                            f"{ccfcrec_max_rows()}")
     if q.shape[0] != B:
         raise RuntimeError("ccfcrec: q must have one row per record of the plan")
-    if plan["user_range"][0] < 0 or plan["user_range"][1] >= user_table.shape[0] or plan["item_range"][0] < 0 \
-            or plan["item_range"][1] >= item_table.shape[0]:
-        raise RuntimeError("ccfcrec: the plan's ids lie outside the tables")
-    for t in (item_table, q, plan["users"], grad_user, grad_item, grad_q, loss, workspace):
-        if t is not None and t.device != dev:
-            raise RuntimeError("ccfcrec: every tensor must be on the tables' device")
+    _check_ids_in_tables("ccfcrec", "the plan's ids", plan["user_range"], plan["item_range"], user_table, item_table)
+    _check_one_device("ccfcrec", "the tables'", dev, item_table, q, plan["users"], grad_user, grad_item, grad_q, loss,
+                      workspace)
 
     grad_user = _grad_buffer("ccfcrec", "the tables' shapes", grad_user, user_table, want_user, False)
     grad_item = _grad_buffer("ccfcrec", "the tables' shapes", grad_item, item_table, want_item, False)
@@ -1277,8 +1291,7 @@ def aldi(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor
     dev = user_table.device
     _check_2d_f32("aldi", "tables and tower outputs", user_table, item_table, gen_user, gen_pos, gen_neg)
     d = user_table.shape[1]
-    if d % 4 != 0 or d < 4 or d > 256:
-        raise RuntimeError(f"aldi: width {d} must be a multiple of 4 in [4, 256]")
+    _check_width("aldi", d)
     B = users.shape[0] if users.dim() == 1 else 0
     if B < 1 or pos.shape != (B,) or neg.shape != (B,):
         raise RuntimeError("aldi: users, pos, neg must be (B,) with B >= 1")
@@ -1289,15 +1302,13 @@ def aldi(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor
     ids = (users, pos, neg)
     if any(t.dtype.is_floating_point for t in ids):
         raise RuntimeError("aldi: users, pos, neg must be integer tensors")
-    for t in (item_table, *ids, gen_user, gen_pos, gen_neg, item_weight, grad_user, grad_pos, grad_neg, loss, workspace):
-        if t is not None and t.device != dev:
-            raise RuntimeError("aldi: every tensor must be on the tables' device")
+    _check_one_device("aldi", "the tables'", dev, item_table, *ids, gen_user, gen_pos, gen_neg, item_weight, grad_user,
+                      grad_pos, grad_neg, loss, workspace)
     if id_range is None:
         items = torch.cat([pos.reshape(-1), neg.reshape(-1)])
         id_range = ((int(users.min()), int(users.max())), (int(items.min()), int(items.max())))
     (u_lo, u_hi), (i_lo, i_hi) = id_range
-    if u_lo < 0 or u_hi >= user_table.shape[0] or i_lo < 0 or i_hi >= item_table.shape[0]:
-        raise RuntimeError("aldi: ids lie outside the tables")
+    _check_ids_in_tables("aldi", "ids", (u_lo, u_hi), (i_lo, i_hi), user_table, item_table)
     users, pos, neg = (t.to(torch.int32).contiguous() for t in ids)
 
     grad_user, grad_pos, grad_neg = (_grad_buffer("aldi", "the tower outputs' shape", g, gen_user, want, True)
@@ -1327,6 +1338,24 @@ def gar_workspace(batch: int, d: int, n_items: int, n_users: int, device) -> tor
     return torch.empty(max(gar_workspace_bytes(batch, d, n_items, n_users), 1), dtype=torch.uint8, device=device)
 
 
+def _triple_plan(op: str, chunk_rows, users, pos, neg, n_users, n_items, id_range, chunk) -> dict:
+    """``gar_plan`` / ``mtpr_plan``: op fronts the messages, chunk_rows() is the library's chunk size."""
+    B = users.shape[0] if users.dim() == 1 else 0
+    if B < 1 or pos.shape != (B,) or neg.shape != (B,):
+        raise RuntimeError(f"{op}: users, pos, neg must be (B,) with B >= 1")
+    if any(t.dtype.is_floating_point or t.device != users.device for t in (users, pos, neg)):
+        raise RuntimeError(f"{op}: users, pos, neg must be integer tensors on one device")
+    ulong = users.long()
+    both = torch.cat([pos.long(), neg.long()])
+    if id_range is None:
+        id_range = ((int(ulong.min()), int(ulong.max())), (int(both.min()), int(both.max())))
+    user_range, item_range = (tuple(int(x) for x in r) for r in id_range)
+    _check_ids_in_plan(op, user_range, item_range, n_users, n_items)
+    c = lambda t: t.to(torch.int32).contiguous()
+    return dict(batch=B, user_range=user_range, item_range=item_range, users=c(ulong), pos=c(both[:B]), neg=c(both[B:]),
+                **_owner_index(both, ulong, chunk_rows() if chunk is None else chunk))
+
+
 def gar_plan(users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_users: Optional[int] = None,
              n_items: Optional[int] = None, id_range=None, chunk: Optional[int] = None) -> dict:
     """The index side of one crh_gar_f32 step.  users, pos, neg (B,): integer tensors on one device.  Returns int32 tensors:
@@ -1336,31 +1365,7 @@ def gar_plan(users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_users:
     knows them (a trainer that sampled the ids on the host); measured here otherwise, which waits for the device.  With
     n_users / n_items given, ids outside the tables raise instead of reaching the kernel.  ``chunk`` is the library's
     unless given (the grouping is plain tensor code and runs on any device)."""
-    B = users.shape[0] if users.dim() == 1 else 0
-    if B < 1 or pos.shape != (B,) or neg.shape != (B,):
-        raise RuntimeError("gar_plan: users, pos, neg must be (B,) with B >= 1")
-    if any(t.dtype.is_floating_point or t.device != users.device for t in (users, pos, neg)):
-        raise RuntimeError("gar_plan: users, pos, neg must be integer tensors on one device")
-    ulong = users.long()
-    both = torch.cat([pos.long(), neg.long()])
-    if id_range is None:
-        id_range = ((int(ulong.min()), int(ulong.max())), (int(both.min()), int(both.max())))
-    user_range, item_range = (tuple(int(x) for x in r) for r in id_range)
-    if n_users is not None and (user_range[0] < 0 or user_range[1] >= n_users):
-        raise RuntimeError("gar_plan: user id outside the user table")
-    if n_items is not None and (item_range[0] < 0 or item_range[1] >= n_items):
-        raise RuntimeError("gar_plan: item id outside the item table")
-    if chunk is None:
-        chunk = gar_chunk_rows()
-    item_ids, item_occ, item_ptr, item_chunk_ptr, item_chunk_own, _ = _owner_chunks(both, chunk)
-    user_ids, user_occ, user_ptr, user_chunk_ptr, user_chunk_own, _ = _owner_chunks(ulong, chunk)
-    c = lambda t: t.to(torch.int32).contiguous()
-    return dict(batch=B, n_items=int(item_ids.shape[0]), n_users=int(user_ids.shape[0]),
-                n_item_chunks=int(item_chunk_own.shape[0]), n_user_chunks=int(user_chunk_own.shape[0]),
-                user_range=user_range, item_range=item_range, users=c(ulong), pos=c(both[:B]), neg=c(both[B:]),
-                item_ids=c(item_ids), item_ptr=c(item_ptr), item_occ=c(item_occ), item_chunk_ptr=c(item_chunk_ptr),
-                item_chunk_own=c(item_chunk_own), user_ids=c(user_ids), user_ptr=c(user_ptr), user_occ=c(user_occ),
-                user_chunk_ptr=c(user_chunk_ptr), user_chunk_own=c(user_chunk_own))
+    return _triple_plan("gar_plan", gar_chunk_rows, users, pos, neg, n_users, n_items, id_range, chunk)
 
 
 def gar(user_table: torch.Tensor, item_table: torch.Tensor, gen: torch.Tensor, plan: dict, alpha: float, beta: float,
@@ -1375,17 +1380,14 @@ def gar(user_table: torch.Tensor, item_table: torch.Tensor, gen: torch.Tensor, p
     dev = user_table.device
     _check_2d_f32("gar", "tables and the generator's output", user_table, item_table, gen)
     d = user_table.shape[1]
-    if d % 4 != 0 or d < 4 or d > 256:
-        raise RuntimeError(f"gar: width {d} must be a multiple of 4 in [4, 256]")
+    _check_width("gar", d)
     B = plan["batch"]
     if item_table.shape[1] != d or gen.shape != (B, d):
         raise RuntimeError("gar: the generator's output must be (B, d) of the tables' width, one row per record of the plan")
-    for t in (item_table, gen, plan["users"], grad_user, grad_item, grad_gen, loss, workspace):
-        if t is not None and t.device != dev:
-            raise RuntimeError("gar: every tensor must be on the tables' device")
+    _check_one_device("gar", "the tables'", dev, item_table, gen, plan["users"], grad_user, grad_item, grad_gen, loss,
+                      workspace)
     (u_lo, u_hi), (i_lo, i_hi) = plan["user_range"], plan["item_range"]
-    if u_lo < 0 or u_hi >= user_table.shape[0] or i_lo < 0 or i_hi >= item_table.shape[0]:
-        raise RuntimeError("gar: ids lie outside the tables")
+    _check_ids_in_tables("gar", "ids", (u_lo, u_hi), (i_lo, i_hi), user_table, item_table)
 
     grad_user = _grad_buffer("gar", "the tables' and the generator output's shapes", grad_user, user_table, want_user, False)
     grad_item = _grad_buffer("gar", "the tables' and the generator output's shapes", grad_item, item_table, want_item, False)
@@ -1425,31 +1427,7 @@ def mtpr_plan(users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_users
     """The index side of one crh_mtpr_f32 step: ``gar_plan``'s arrays (same arguments, same id_range shortcut, same
     errors) with the owners' occurrences cut into chunks of crh_mtpr_chunk_rows().  user_ids / item_ids are the distinct
     ids, ascending: what ``adagrad_rows`` steps."""
-    B = users.shape[0] if users.dim() == 1 else 0
-    if B < 1 or pos.shape != (B,) or neg.shape != (B,):
-        raise RuntimeError("mtpr_plan: users, pos, neg must be (B,) with B >= 1")
-    if any(t.dtype.is_floating_point or t.device != users.device for t in (users, pos, neg)):
-        raise RuntimeError("mtpr_plan: users, pos, neg must be integer tensors on one device")
-    ulong = users.long()
-    both = torch.cat([pos.long(), neg.long()])
-    if id_range is None:
-        id_range = ((int(ulong.min()), int(ulong.max())), (int(both.min()), int(both.max())))
-    user_range, item_range = (tuple(int(x) for x in r) for r in id_range)
-    if n_users is not None and (user_range[0] < 0 or user_range[1] >= n_users):
-        raise RuntimeError("mtpr_plan: user id outside the user table")
-    if n_items is not None and (item_range[0] < 0 or item_range[1] >= n_items):
-        raise RuntimeError("mtpr_plan: item id outside the item table")
-    if chunk is None:
-        chunk = mtpr_chunk_rows()
-    item_ids, item_occ, item_ptr, item_chunk_ptr, item_chunk_own, _ = _owner_chunks(both, chunk)
-    user_ids, user_occ, user_ptr, user_chunk_ptr, user_chunk_own, _ = _owner_chunks(ulong, chunk)
-    c = lambda t: t.to(torch.int32).contiguous()
-    return dict(batch=B, n_items=int(item_ids.shape[0]), n_users=int(user_ids.shape[0]),
-                n_item_chunks=int(item_chunk_own.shape[0]), n_user_chunks=int(user_chunk_own.shape[0]),
-                user_range=user_range, item_range=item_range, users=c(ulong), pos=c(both[:B]), neg=c(both[B:]),
-                item_ids=c(item_ids), item_ptr=c(item_ptr), item_occ=c(item_occ), item_chunk_ptr=c(item_chunk_ptr),
-                item_chunk_own=c(item_chunk_own), user_ids=c(user_ids), user_ptr=c(user_ptr), user_occ=c(user_occ),
-                user_chunk_ptr=c(user_chunk_ptr), user_chunk_own=c(user_chunk_own))
+    return _triple_plan("mtpr_plan", mtpr_chunk_rows, users, pos, neg, n_users, n_items, id_range, chunk)
 
 
 def mtpr(user_table: torch.Tensor, item_table: torch.Tensor, h: torch.Tensor, weu: torch.Tensor, wei: torch.Tensor,
@@ -1469,8 +1447,7 @@ def mtpr(user_table: torch.Tensor, item_table: torch.Tensor, h: torch.Tensor, we
     _check_2d_f32("mtpr", "tables, content rows and projections", user_table, item_table, h, weu, wei)
     cold_user = bool(cold_user)
     d = weu.shape[1]
-    if d % 4 != 0 or d < 4 or d > 128:
-        raise RuntimeError(f"mtpr: width {d} must be a multiple of 4 in [4, 128]")
+    _check_width("mtpr", d, 128)
     B = plan["batch"]
     wp, wq, hr = (d, 2 * d, B) if cold_user else (2 * d, d, 2 * B)
     if weu.shape != (2 * d, d) or wei.shape != (2 * d, d):
@@ -1478,12 +1455,10 @@ def mtpr(user_table: torch.Tensor, item_table: torch.Tensor, h: torch.Tensor, we
     if user_table.shape[1] != wp or item_table.shape[1] != wq or h.shape != (hr, d):
         raise RuntimeError("mtpr: item mode takes tables (nu, 2 d), (ni, d) and h (2 B, d); user mode (nu, d), (ni, 2 d) "
                            "and h (B, d), B the plan's batch")
-    for t in (item_table, h, weu, wei, plan["users"], grad_user, grad_item, grad_h, grad_weu, grad_wei, loss, workspace):
-        if t is not None and t.device != dev:
-            raise RuntimeError("mtpr: every tensor must be on the tables' device")
+    _check_one_device("mtpr", "the tables'", dev, item_table, h, weu, wei, plan["users"], grad_user, grad_item, grad_h,
+                      grad_weu, grad_wei, loss, workspace)
     (u_lo, u_hi), (i_lo, i_hi) = plan["user_range"], plan["item_range"]
-    if u_lo < 0 or u_hi >= user_table.shape[0] or i_lo < 0 or i_hi >= item_table.shape[0]:
-        raise RuntimeError("mtpr: ids lie outside the tables")
+    _check_ids_in_tables("mtpr", "ids", (u_lo, u_hi), (i_lo, i_hi), user_table, item_table)
 
     what = "the shapes of the tables, the content rows and the projections"
     grad_user = _grad_buffer("mtpr", what, grad_user, user_table, want_user, False)
@@ -1491,10 +1466,7 @@ def mtpr(user_table: torch.Tensor, item_table: torch.Tensor, h: torch.Tensor, we
     grad_h = _grad_buffer("mtpr", what, grad_h, h, want_h, True)
     grad_weu = _grad_buffer("mtpr", what, grad_weu, weu, want_weu, True)
     grad_wei = _grad_buffer("mtpr", what, grad_wei, wei, want_wei, True)
-    if loss is None:
-        loss = torch.empty(6, dtype=torch.float32, device=dev)
-    elif loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < 6:
-        raise RuntimeError("mtpr: loss must be a contiguous float32 buffer of at least six elements")
+    loss = _loss_buffer("mtpr", loss, 6, dev)
     workspace = _workspace_arg("mtpr", workspace, mtpr_workspace, B, d, cold_user, plan["n_items"], plan["n_users"], dev)
     p = plan
     _lib.check(_lib.lib().crh_mtpr_f32(
@@ -1519,12 +1491,10 @@ def adagrad_rows(p: torch.Tensor, g: torch.Tensor, state_sum: torch.Tensor, ids:
     if g.shape != p.shape or state_sum.shape != p.shape:
         raise RuntimeError("adagrad_rows: p, g and state_sum must have one shape")
     d = p.shape[1]
-    if d % 4 != 0 or d < 4 or d > 256:
-        raise RuntimeError(f"adagrad_rows: width {d} must be a multiple of 4 in [4, 256]")
+    _check_width("adagrad_rows", d)
     if ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous() or ids.shape[0] > p.shape[0]:
         raise RuntimeError("adagrad_rows: ids must be a contiguous int32 vector of distinct rows")
-    if any(t.device != p.device for t in (g, state_sum, ids)):
-        raise RuntimeError("adagrad_rows: every tensor must be on p's device")
+    _check_one_device("adagrad_rows", "p's", p.device, g, state_sum, ids)
     _lib.check(_lib.lib().crh_adagrad_rows_f32(_lib.ptr(p), _lib.ptr(g), _lib.ptr(state_sum), _lib.ptr(ids),
                                                int(ids.shape[0]), int(p.shape[0]), int(d), float(lr), float(eps),
                                                int(bool(zero_grad)), _lib.current_stream()), "crh_adagrad_rows_f32")

@@ -86,7 +86,7 @@ def test_refusals(tmp_path, monkeypatch):
     assert [len(g["params"]) for g in groups] == [4, 8] and [g["weight_decay"] for g in groups] == [0.0, 1e-4]
     with pytest.raises(RuntimeError, match="MI355X only"):
         tr.train()
-    import coldrec_amd.model.ALDI as mod
+    import coldrec_amd.model.FusedLossTrainer as mod
     monkeypatch.setattr(mod, "dp_from_env", lambda: object())  # a data-parallel launch is refused before anything runs
     tr.device = torch.device("cuda:0")
     with pytest.raises(RuntimeError, match="data-parallel"):

@@ -70,7 +70,7 @@ def test_refusals(tmp_path, monkeypatch):
     tr = new(_cfg(data))
     with pytest.raises(RuntimeError, match="MI355X only"):
         tr.train()
-    import coldrec_amd.model.CCFCRec as mod
+    import coldrec_amd.model.FusedLossTrainer as mod
     monkeypatch.setattr(mod, "dp_from_env", lambda: object())  # a data-parallel launch is refused before anything runs
     tr.device = torch.device("cuda:0")
     with pytest.raises(RuntimeError, match="data-parallel"):

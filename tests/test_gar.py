@@ -84,7 +84,7 @@ def test_refusals(cold, tmp_path, monkeypatch):
     assert m.content.shape == ((data.user_num if cold == "user" else data.item_num), 16)
     with pytest.raises(RuntimeError, match="MI355X only"):
         tr.train()
-    import coldrec_amd.model.GAR as mod
+    import coldrec_amd.model.FusedLossTrainer as mod
     monkeypatch.setattr(mod, "dp_from_env", lambda: object())  # a data-parallel launch is refused before anything runs
     tr.device = torch.device("cuda:0")
     with pytest.raises(RuntimeError, match="data-parallel"):
@@ -119,12 +119,19 @@ def test_queries_without_gpu():
     assert all(a <= b for a, b in zip(sizes, sizes[1:])) and sizes[0] < sizes[-1]                                  # monotone in B
 
 
+@pytest.mark.parametrize("which", ["gar", "mtpr"])
 @pytest.mark.parametrize("case", [(37, 20, 11, 30), ("chunks", 132, 3, 5), (2048, 64, 300, 500)], ids=IDS)
-def test_plan_arrays_against_a_numpy_grouping(case):
+def test_plan_arrays_against_a_numpy_grouping(case, which):
+    """One body builds both plans: each against the NumPy grouping at its own library chunk size, and the two against
+    each other, same keys and equal tensors, at that chunk size and at a small one."""
     from coldrec_amd import ops
     _, _, users, pos, neg, _ = _inputs(case)
-    chunk = ops.gar_chunk_rows()
-    plan = ops.gar_plan(users, pos, neg, n_users=case[2], n_items=case[3])
+    make_plan = getattr(ops, which + "_plan")
+    chunk = getattr(ops, which + "_chunk_rows")()
+    plan = make_plan(users, pos, neg, n_users=case[2], n_items=case[3])
+    for c in (chunk, 7):
+        a, b = ops.gar_plan(users, pos, neg, chunk=c), ops.mtpr_plan(users, pos, neg, chunk=c)
+        assert list(a) == list(b) and all(torch.equal(a[k], b[k]) if torch.is_tensor(a[k]) else a[k] == b[k] for k in a)
     B = users.shape[0]
     assert plan["batch"] == B and all(v.dtype == torch.int32 for v in plan.values() if torch.is_tensor(v))
     for side, ids in (("user", users.numpy()), ("item", np.concatenate([pos.numpy(), neg.numpy()]))):
@@ -141,12 +148,12 @@ def test_plan_arrays_against_a_numpy_grouping(case):
         assert plan[f"{side}_range"] == (ids.min(), ids.max())
     assert np.array_equal(plan["users"].numpy(), users.numpy()) and np.array_equal(plan["pos"].numpy(), pos.numpy())
     assert np.array_equal(plan["neg"].numpy(), neg.numpy())
-    stated = ops.gar_plan(users, pos, neg, id_range=((0, case[2] - 1), (0, case[3] - 1)))
+    stated = make_plan(users, pos, neg, id_range=((0, case[2] - 1), (0, case[3] - 1)))
     assert stated["user_range"] == (0, case[2] - 1) and torch.equal(stated["item_occ"], plan["item_occ"])
-    with pytest.raises(RuntimeError, match="outside the user table"):
-        ops.gar_plan(users, pos, neg, n_users=int(users.max()))
-    with pytest.raises(RuntimeError, match=r"must be \(B,\)"):
-        ops.gar_plan(users, pos[:-1], neg)
+    with pytest.raises(RuntimeError, match=which + "_plan: user id outside the user table"):
+        make_plan(users, pos, neg, n_users=int(users.max()))
+    with pytest.raises(RuntimeError, match=which + r"_plan: users, pos, neg must be \(B,\)"):
+        make_plan(users, pos[:-1], neg)
 
 
 @pytest.fixture(scope="module")

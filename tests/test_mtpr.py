@@ -89,7 +89,7 @@ def test_refusals(cold, monkeypatch):
     assert m.content.shape == ((data.user_num if cold == "user" else data.item_num), 16)
     with pytest.raises(RuntimeError, match="MI355X only"):
         tr.train()
-    import coldrec_amd.model.MTPR as mod
+    import coldrec_amd.model.FusedLossTrainer as mod
     monkeypatch.setattr(mod, "dp_from_env", lambda: object())  # a data-parallel launch is refused before anything runs
     tr.device = torch.device("cuda:0")
     with pytest.raises(RuntimeError, match="data-parallel"):
