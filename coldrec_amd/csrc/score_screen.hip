@@ -120,6 +120,15 @@ __device__ __forceinline__ void row_sums(const f32x4& x0, const f32x4& x1, _Floa
     }
 }
 
+// B_u (see the head of the file) from the user's three norms and the item maxima, all upper bounds in float: fp64, the absolute
+// term of the exact chain's subnormal roundings, and 2^-20 over the roundings of this very sum.  The ONE definition: stage 2's
+// predicate and stage 1's margin (screen_users_kernel, screen_margin_kernel) must speak of the same number.
+__device__ __forceinline__ double screen_bound(float un, float uhn, float udn, float R, float N, float Nh) {
+    const double gd = SD * 0x1p-24 / (1.0 - SD * 0x1p-24), gp = 0x1p-12;
+    const double B = (double)un * R + (double)udn * Nh + gd * (double)un * N + gp * (double)uhn * Nh + 0x1p-126;
+    return B * (1.0 + 0x1p-20);
+}
+
 // an upper bound of sqrt(s) for an fp64 sum of squares (its own rounding error is far below the 2^-30 margin)
 __device__ __forceinline__ float up_norm(double s) { return up_float(sqrt(s) * (1.0 + 0x1p-30)); }
 
@@ -272,10 +281,15 @@ __global__ __launch_bounds__(256) void screen_items_kernel(const float* __restri
 }
 
 // User block (in `users` order) -> fp16 row-major [n_users][128]; per user |u|, |u^|, |u - u^| (upper bounds) into ustat[3 j ..].
+// The item maxima are in the stats block by now (built in front of this kernel, or copied from the prepared state): the largest B_u of
+// the call goes to stats[SCREEN_STAT_MAXB] (float bits, atomicMax as R, N, N^; a non-finite B_u -- a non-finite row makes a norm
+// +inf -- goes in as +inf), for the margin of stage 1 (screen_margin_kernel).
 __global__ __launch_bounds__(256) void screen_users_kernel(const float* __restrict__ uemb, const int32_t* __restrict__ users,
                                                            int64_t n_users, _Float16* __restrict__ uh, float* __restrict__ ustat,
-                                                           const unsigned* __restrict__ stats) {
+                                                           unsigned* __restrict__ stats) {
     const int e = scale_exp(stats, 1);
+    const float R = __uint_as_float(stats[2]), N = __uint_as_float(stats[3]), Nh = __uint_as_float(stats[4]);
+    float mb = 0.0f;
     const int64_t n_units = n_users * 16;
     for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < ((n_units + 255) & ~(int64_t)255); w += (int64_t)gridDim.x * 256) {
         const int64_t j = (w < n_units ? w : n_units - 1) >> 4;      // (the shuffles need every lane of the row group)
@@ -290,12 +304,38 @@ __global__ __launch_bounds__(256) void screen_users_kernel(const float* __restri
             reinterpret_cast<u32x4*>(uh)[j * 16 + c] = __builtin_bit_cast(u32x4, f16x8{hv[0], hv[1], hv[2], hv[3], hv[4], hv[5], hv[6], hv[7]});
             if (c == 0) {
                 const bool bad = sxx != sxx || sdd != sdd;
-                ustat[3 * j + 0] = bad ? __builtin_inff() : up_norm(sxx);
-                ustat[3 * j + 1] = bad ? __builtin_inff() : up_norm(shh);
-                ustat[3 * j + 2] = bad ? __builtin_inff() : up_norm(sdd);
+                const float un = bad ? __builtin_inff() : up_norm(sxx), uhn = bad ? __builtin_inff() : up_norm(shh);
+                const float udn = bad ? __builtin_inff() : up_norm(sdd);
+                ustat[3 * j + 0] = un;
+                ustat[3 * j + 1] = uhn;
+                ustat[3 * j + 2] = udn;
+                // (from the floats stage 2 reads; up_float turns NaN and overflow into +inf)
+                mb = fmaxf(mb, up_float(screen_bound(un, uhn, udn, R, N, Nh)));
             }
         }
     }
+    __shared__ float red[4];
+    mb = wave_max(mb);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mb;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float b = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        if (b > 0.0f) atomicMax(stats + SCREEN_STAT_MAXB, __float_as_uint(b));
+    }
+}
+
+// The margin of stage 1's thresholds, one thread: M = 2 (1 + 2^-10) max B_u in the fp16 kernel's score units (the
+// two table scales are powers of two: exact), rounded UP to a float and never below the smallest normal one -- so M > 2 B_u for every
+// user of the call after every rounding, and the 2^-10 covers the kernel's float subtraction L[k-1] - M (B_u >= 2^-12 |a| for every
+// approximate score a of the user).  A non-finite bound, or margin_on == 0, gives +inf: the rule is off for the call.
+__global__ void screen_margin_kernel(unsigned* __restrict__ stats, int margin_on) {
+    const float maxb = __uint_as_float(stats[SCREEN_STAT_MAXB]);
+    float M = __builtin_inff();
+    if (margin_on && maxb <= 3.4028235e38f) {             // (NaN fails)
+        const double m = 2.0 * (1.0 + 0x1p-10) * (double)maxb * ldexp(1.0, scale_exp(stats, 0) + scale_exp(stats, 1));
+        M = fmaxf(up_float(m), 0x1p-126f);
+    }
+    stats[SCREEN_STAT_MARGIN] = __float_as_uint(M);
 }
 
 // the canonical score: fmaf chain over k ascending from +0 (oracle/topk_oracle.c)
@@ -356,17 +396,25 @@ __global__ __launch_bounds__(256) void screen_certify_kernel(ScreenArgs s) {
     const unsigned long long kth = __ballot(mine && rank == K - 1);
     const float ek = __shfl(sc, kth ? __builtin_ctzll(kth) : 0);
     const float a_last = __shfl(a, KP - 1);
+    const float a_k = __shfl(a, K - 1);
     bool cert = s.mode != 3 && __ballot(!ok) == 0ull && kth != 0ull;
     if (cert) {
         const float* us = s.ustat + 3 * slot;
         const float R = __uint_as_float(s.stats[2]), N = __uint_as_float(s.stats[3]), Nh = __uint_as_float(s.stats[4]);
-        const double gd = SD * 0x1p-24 / (1.0 - SD * 0x1p-24), gp = 0x1p-12;
-        double B = (double)us[0] * R + (double)us[2] * Nh + gd * (double)us[0] * N + gp * (double)us[1] * Nh + 0x1p-126;
-        B *= 1.0 + 0x1p-20;
-        const double A = (double)a_last * ldexp(1.0, -(scale_exp(s.stats, 0) + scale_exp(s.stats, 1)));   // exact
+        const double B = screen_bound(us[0], us[1], us[2], R, N, Nh);
+        const double unscale = ldexp(1.0, -(scale_exp(s.stats, 0) + scale_exp(s.stats, 1)));
+        const double A = (double)a_last * unscale;         // exact
         double thr = A + B;
         thr += fabs(thr) * 0x1p-50;                        // the rounding of that sum, upward
         cert = (double)ek > thr && ek > CRH_MASKED_SCORE;  // NaN anywhere fails both
+        // stage 1's margin rule kept out of the list only rows below a_k - M: what it dropped lies below (a_k - M) + B_u.  With
+        // M > 2 B_u this holds whenever the bound does (e_k >= a_k - B_u), so it moves no count; M = +inf (the rule off) passes
+        const float Mk = __uint_as_float(s.stats[SCREEN_STAT_MARGIN]);
+        if (Mk <= 3.4028235e38f) {
+            double thr_m = ((double)a_k - (double)Mk) * unscale + B;
+            thr_m += fabs(thr_m) * 0x1p-50;
+            cert = cert && (double)ek > thr_m;
+        }
     }
     if (cert) {
         if (mine && rank < K) {
@@ -579,12 +627,14 @@ int launch_screen_prep_items(const ScreenArgs& s, unsigned* stats, _Float16* pac
     return CRH_OK;
 }
 
-int launch_screen_prep_users(const ScreenArgs& s, _Float16* uh, hipStream_t st) {
+int launch_screen_prep_users(const ScreenArgs& s, _Float16* uh, int margin_on, hipStream_t st) {
     hipLaunchKernelGGL(screen_maxabs_kernel<false>, dim3(256), dim3(256), 0, st, s.user_emb, s.users, s.n_users, s.stats, 1, nullptr);
     CRH_HIP(hipGetLastError());
     const int64_t ub = (s.n_users * 16 + 255) / 256;
     hipLaunchKernelGGL(screen_users_kernel, dim3((unsigned)(ub < 2048 ? ub : 2048)), dim3(256), 0, st, s.user_emb, s.users, s.n_users,
                        uh, s.ustat, s.stats);
+    CRH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(screen_margin_kernel, dim3(1), dim3(1), 0, st, s.stats, margin_on);
     CRH_HIP(hipGetLastError());
     return CRH_OK;
 }

@@ -1289,6 +1289,8 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
     a.user_base = 0;
     a.seed_score = seed_score;
     a.seed_idx = seed_idx;
+    a.margin = nullptr;         // (the screen's rule: score_topk_screened)
+    a.screen_k = 0;
     const int64_t T = (n_items + 31) / 32;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
@@ -1541,7 +1543,10 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
         rc = screen_items_build(s, s.stats, pk, P, idmap, reinterpret_cast<unsigned*>(ws + L.scan), ordered ? &ord : nullptr, tbits, st);
         if (rc != CRH_OK) return rc;
     }
-    rc = launch_screen_prep_users(s, uh, st);
+    // CRH_SCORE_SCREEN_MARGIN (read per call): 1 (default) stage 1 drops a row whose approximate score lies more than the margin
+    // below its user's current k-th one; 0 the margin is +inf and the thresholds are the lists' tails
+    const char* margin_env = getenv("CRH_SCORE_SCREEN_MARGIN");
+    rc = launch_screen_prep_users(s, uh, !(margin_env && atoi(margin_env) == 0), st);
     if (rc != CRH_OK) return rc;
     if (ev_kernel_start) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_start), st));
 
@@ -1569,6 +1574,8 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     a.tile_bits = reinterpret_cast<const uint32_t*>(pk);
     a.idmap = nullptr;          // (the prefix is not compacted)
     a.n_live = nullptr;
+    a.margin = nullptr;         // (the prefix is ranked whole: the rule is stage 1's DMA launch's)
+    a.screen_k = 0;
     if (P > 0) {
         const int64_t stride = P;                       // P is a multiple of 32
         const int upw_pw = users_per_wave(2, D);
@@ -1607,6 +1614,8 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     a.n_ugroups = (n_users + 127) / 128;
     const int64_t n_wg = (a.n_ugroups + 3) / 4;
     a.n_splits = screen_splits(n_users, n_main, P > 0);
+    a.margin = reinterpret_cast<const float*>(s.stats + SCREEN_STAT_MARGIN);
+    a.screen_k = k;
     if (a.n_splits == 1) {
         a.out_score = cand_s;
         a.out_idx = cand_i;

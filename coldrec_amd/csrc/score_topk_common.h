@@ -48,6 +48,12 @@ struct ScoreArgs {
     // n_items is its upper bound, which the host sized the launch by).  NULL: rows are items.
     const int32_t* idmap;
     const unsigned* n_live;
+    // The screen's MARGIN rule (fp16 d=128 launches only): once a list's tail is an item, its user's threshold is
+    // max(tail, L[screen_k - 1] - *margin) -- *margin in the kernel's scaled score units, above twice every user's error bound
+    // (screen_margin_kernel), +inf = the rule is off -- so a row that can never reach the call's exact top screen_k enters no list.
+    // NULL: the thresholds are the lists' tails (every other launch).
+    const float* margin;
+    int screen_k;
 };
 
 // in : lane (i,0) holds k = 8q+0..3 of row i, lane (i,1) holds k = 8q+4..7
@@ -411,6 +417,7 @@ struct ScreenArgs {
     const float* cand_score;      // [n_users][kp] the fp16 kernel's lists (scaled scores, canonical order)
     const int32_t* cand_idx;
     unsigned* stats;              // [0] max|v| [1] max|u| (float bits) [2] R [3] N [4] N^ [5] uncertified users [6] live rows (compacted)
+                                  // [7] max B_u of the call (float bits) [8] the margin M of stage 1, scaled (float; SCREEN_STAT_*)
     float* ustat;                 // [n_users][3] |u|, |u^|, |u - u^|
     int32_t* fail_list;           // [n_users] slots of the uncertified users (stats[5] of them)
     float* part_score;            // [n_users][n_slices][k] the fallback's slice lists
@@ -423,6 +430,10 @@ __attribute__((visibility("hidden"))) int screen_fallback_slices(int64_t n_items
 // idmap != NULL: the rows behind the first `prefix` items are compacted to the unmasked ones (idmap[q] = global id of the q-th,
 // their number in s.stats[SCREEN_STAT_LIVE]; scan = screen_scan_bytes of scratch words)
 constexpr int SCREEN_STAT_LIVE = 6;
+// the call's largest error bound (float bits, atomicMax as R, N, N^) and the margin derived from it: words of the per-call block that
+// the prepared copy never carries (they depend on the users)
+constexpr int SCREEN_STAT_MAXB = 7;
+constexpr int SCREEN_STAT_MARGIN = 8;
 __attribute__((visibility("hidden"))) size_t screen_scan_bytes(int64_t n_main);
 // The ORDERED map (CRH_SCORE_SCREEN_ORDER; one cut only): the live rows streamed by descending norm key, ascending id inside a key,
 // so that every user's threshold rises early and fewer later rows beat it.  Insertion is order-independent under the canonical
@@ -444,7 +455,8 @@ __attribute__((visibility("hidden"))) size_t screen_sort_bytes(int64_t n_slots);
 // ord != NULL (needs idmap): stage 1 and the packed copy follow ord->idmap
 __attribute__((visibility("hidden"))) int launch_screen_prep_items(const ScreenArgs& s, unsigned* stats, _Float16* packed, int64_t prefix,
                                                                    int32_t* idmap, unsigned* scan, const ScreenOrder* ord, hipStream_t st);
-__attribute__((visibility("hidden"))) int launch_screen_prep_users(const ScreenArgs& s, _Float16* uh, hipStream_t st);
+// margin_on = 0 (CRH_SCORE_SCREEN_MARGIN=0): the margin word is +inf, stage 1 keeps the lists' tails as thresholds
+__attribute__((visibility("hidden"))) int launch_screen_prep_users(const ScreenArgs& s, _Float16* uh, int margin_on, hipStream_t st);
 __attribute__((visibility("hidden"))) int screen_map_only(const uint32_t* bitmap, const float* item_emb, int64_t n_items,
                                                           int64_t item_base, int64_t prefix, int ordered, int32_t* map_out,
                                                           int32_t* keys_out, int64_t* count, hipStream_t st);

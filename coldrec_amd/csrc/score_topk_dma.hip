@@ -68,6 +68,31 @@ constexpr bool DMA_ONE_TRIP_F32 = false;
 #else
 constexpr bool DMA_ONE_TRIP_F32 = true;
 #endif
+// The screen's MARGIN rule (round 19; ScoreArgs::margin).  A user's threshold is the tail of its list; once that tail
+// is an item (above CRH_MASKED_SCORE) it is max(tail, L[k-1] - M): k = the call's k (ScoreArgs::screen_k <= K'), M one value per call,
+// above twice every user's error bound, so a row below L[k-1] - M has an exact score below the k-th best exact one and need not enter
+// any list.  M = +inf switches the rule off: L[k-1] - inf = -inf and the maximum is the tail, the same code.  Every wave holds M in
+// one register for the launch (a word of LDS read with each candidate's list was measured: 300 cycles per event, more than the rule
+// saved).  The new L[k-1] comes out of the registers the insert already holds, as the new tail does: the list is sorted, so with the
+// old entries e1 = L[k-1] <= e2 = L[k-2] it is the MEDIAN of e1, e2 and the candidate wherever the candidate lands (below e1: e1;
+// between them: the candidate; above e2: e2) -- two v_readlane, one v_med3_f32, no compare with the insert position.  kc = max(k, 2):
+// a call with k = 1 takes its SECOND entry, which is no larger than the first -- a lower threshold, covered by the same proof -- so that
+// e2 needs no special case.
+// Compiled into the fp16 d=128 kernels only (the screen's launches); every other kernel keeps the tail (MG = false).
+// es = the old list (lane l: entry l, every entry below the old fill valid), tail = the new tail, an item's or not.
+template <bool MG>
+__device__ __forceinline__ float dma_new_tau(float tail, float es, float sc, int kc, float m) {
+    float t = tail >= CRH_MASKED_SCORE ? tail : CRH_NEG_INF;      // never above what a masked (-1e9) candidate could beat
+    if constexpr (MG) {
+        const float e1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, es), kc - 1));
+        const float e2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, es), kc - 2));
+        const float lk = __builtin_amdgcn_fmed3f(sc, e1, e2);
+        // (the maximum as a median with +inf: fmaxf quiets its operands first, one more instruction)
+        t = __builtin_amdgcn_fmed3f(t, tail > CRH_MASKED_SCORE ? lk - m : CRH_NEG_INF, __builtin_inff());
+    }
+    return t;
+}
+
 // One candidate of an event, shared by the 32x32 and the 16x16 forms of the slow path: the LDS batch read, the "cannot enter"
 // test, the rated filter with its bounded search, the insert and the user's new threshold out of registers.  sc / gi = the
 // candidate's score and id, bm_masked = its candidate-bitmap bit, ul / slot = its user's column in the wave and slot in the call,
@@ -75,9 +100,11 @@ constexpr bool DMA_ONE_TRIP_F32 = true;
 // LANE_READ (ONE_TRIP, the 16x16 event): lane l reads entry l whatever K -- lanes >= K read the LDS words behind the user's list (the
 // wave's own lists, ids and fills: K + 64 words stay inside them) and nobody uses them; the clamp and the select that blanks the
 // lanes >= n cost the event two registers that the 16x16 form does not have.
-template <bool ONE_TRIP, bool LANE_READ = false>
+// MG: the margin rule above (margin = the call's M).
+template <bool ONE_TRIP, bool LANE_READ = false, bool MG = false>
 __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, int ul, int64_t slot, float* ls, int* li, int* cnt, int K,
-                                              const ScoreArgs& a, int lane, const unsigned* rfilter, bool mine, float& tau_reg) {
+                                              const ScoreArgs& a, int lane, const unsigned* rfilter, bool mine, float& tau_reg,
+                                              float margin = 0.0f) {
     float* lsu = ls + ul * K;
     int* liu = li + ul * K;
     // one batch of LDS reads: fill, tail entry, filter word
@@ -138,7 +165,8 @@ __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, 
         if (n2 >= K) {
             const float prev = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, es), K >= 2 ? K - 2 : 0));
             const float kth = (p == K - 1) ? sc : prev;
-            if (mine) tau_reg = kth >= CRH_MASKED_SCORE ? kth : CRH_NEG_INF;
+            const float t = dma_new_tau<MG>(kth, es, sc, a.screen_k < 2 ? 2 : a.screen_k, margin);
+            if (mine) tau_reg = t;
         }
     }
 }
@@ -234,7 +262,8 @@ constexpr bool DMA_EVENT_STRAIGHT = true;
 // insert -- and what each outcome writes are dma_candidate's with n = K.
 template <int K>
 __device__ __forceinline__ void dma_candidate_full(float sc, int gi, bool bm_masked, int ul, int64_t slot, float* ls, int* li,
-                                                   const ScoreArgs& a, int lane, const unsigned* rfilter, bool mine, float& tau_reg) {
+                                                   const ScoreArgs& a, int lane, const unsigned* rfilter, bool mine, float& tau_reg,
+                                                   float margin) {
     static_assert(K >= 2 && K < 64, "one entry per lane");
     constexpr unsigned long long LIST = (1ull << K) - 1ull;     // lanes >= K read what lies behind the list (LANE_READ of dma_candidate)
     float* lsu = ls + ul * K;
@@ -266,16 +295,18 @@ __device__ __forceinline__ void dma_candidate_full(float sc, int gi, bool bm_mas
         }
         const float prev = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, es), K - 2));
         const float kth = (p == K - 1) ? sc : prev;
-        if (mine) tau_reg = kth >= CRH_MASKED_SCORE ? kth : CRH_NEG_INF;
+        const float t = dma_new_tau<true>(kth, es, sc, a.screen_k < 2 ? 2 : a.screen_k, margin);
+        if (mine) tau_reg = t;
     }
 }
 
 // CM (compacted stream): row q of the stream is the q-th unmasked item; idv = the ids of this tile's rows (lane l: row l & 31),
 // read from LDS once per event by the caller.  item0 and split_end stay row numbers; there are no masked rows (tb = 0).
-template <bool ONE_TRIP, bool CM>
+template <bool ONE_TRIP, bool CM, bool MG = false>
 __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau_reg, float* ls, int* li, int* cnt, int K,
                                                    int ucol0, int64_t slot0, const ScoreArgs& a, int64_t item0,
-                                                   int64_t split_end, int lane, unsigned tb, const unsigned* rfilter, int idv) {
+                                                   int64_t split_end, int lane, unsigned tb, const unsigned* rfilter, int idv,
+                                                   float margin = 0.0f) {
     unsigned cm = gt_mask16(acc, tau_reg);
     // bits of this lane's 16 rows: rows (r&3) + 8*(r>>2) + 4*hh <-> bit r.  Masked rows are packed as zeros: with no negative
     // threshold in the group none of them is a candidate, and the bit shuffling (a dozen VALU instructions) is skipped
@@ -306,7 +337,7 @@ __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau
             int gi;
             if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, (r & 3) + 8 * (r >> 2) + 4 * hh);
             else gi = (int)(a.item_base + il);
-            dma_candidate<ONE_TRIP>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 31) == jl, tau_reg);
+            dma_candidate<ONE_TRIP, false, MG>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 31) == jl, tau_reg, margin);
         }
     }
     // (no read-back of the thresholds: every insert above updated its user's lanes; padding columns keep their +inf)
@@ -364,7 +395,7 @@ __device__ __forceinline__ float pick8u(const f32x8& v, int r) {
 template <bool CM, int KC, bool FULL = false>
 __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& tau_reg, float* ls, int* li, int* cnt, int Krt, int ucol0,
                                                      int64_t slot0, const ScoreArgs& a, int64_t item0, int64_t split_end, int rows_left,
-                                                     int gi0, int lane, unsigned tb, const unsigned* rfilter, int idv) {
+                                                     int gi0, int lane, unsigned tb, const unsigned* rfilter, int idv, float margin) {
     static_assert(!FULL || KC != 0, "the full-list form is compiled for K'");
     const int K = KC ? KC : Krt;
     unsigned cm = gt_mask8(acc, tau_reg);
@@ -395,9 +426,9 @@ __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& ta
         else if constexpr (DMA_EVENT_TAIL64) gi = (int)(a.item_base + il);
         else gi = gi0 + row;
         if constexpr (FULL)
-            dma_candidate_full<KC>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, a, lane, rfilter, (lane & 15) == jl, tau_reg);
+            dma_candidate_full<KC>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin);
         else
-            dma_candidate<DMA_SCREEN_ONE_TRIP, true>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg);
+            dma_candidate<DMA_SCREEN_ONE_TRIP, true, true>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin);
     };
     if constexpr (FULL && DMA_EVENT_STRAIGHT && !DMA_EVENT_SLOT_TEST) {
         // (one s_bcnt1 and a compare.  Not `lanes & (lanes - 1)`: under a bitmap the masked rows may have left no hit lane at all)
@@ -528,6 +559,9 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     constexpr int KC = M16 ? DMA_EVENT_KC : 0;          // the 16x16 form is compiled for the screen's K' (launch_score_dma checks a.k)
     const int K = KC ? KC : a.k;
     const int i = lane & (M16 ? 15 : 31), h = lane >> (M16 ? 4 : 5);   // user column in its block, k-group (M16: c and g of the 16x16x32 layout)
+    // the screen's launches (fp16 d=128, both MFMA shapes; the public fp16 d=128 calls take another kernel): the margin rule of
+    // dma_new_tau
+    constexpr bool MG = std::is_same<T, _Float16>::value && D == 128;
 
     char* ring = smem;                                  // [R][TILE_B]
     unsigned* tbits = reinterpret_cast<unsigned*>(smem + R * TILE_B);   // [2][64]; CM: [IDS_SLOTS + 1][32] ids
@@ -567,6 +601,10 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     int* li = reinterpret_cast<int*>(ls + UPW * K);      // [UPW][K]
     int* cnt = li + UPW * K;                            // [UPW]
     for (int j = lane; j < UPW; j += 64) cnt[j] = 0;
+    [[maybe_unused]] float margin = __builtin_inff();   // MG: the call's M, in one register for the launch
+    if constexpr (MG) {
+        if (a.margin != nullptr) margin = *a.margin;
+    }
     // M16, round 18: every live slot of this wave holds K entries (wave-uniform; lists only grow, so it holds for the launch).  The loop
     // below ends at the first padding slot: padding slots stay empty and do not count -- their thresholds are +inf, no candidate is
     // ever theirs.  (A dead wave copies the lists of the call's last group and takes no event at all.)
@@ -624,7 +662,13 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         // padding columns never take a candidate.  The 16x16 event RELIES on this +inf (and on the dead wave's below): it no longer tests
         // `slot < n_users` per hit lane, so nothing but these thresholds keeps a padding column out of a hit mask
         tau[u] = slot < a.n_users ? CRH_NEG_INF : __builtin_inff();
-        if (a.seed_score && slot < a.n_users) tau[u] = wave_list_tau(ls + (UB * u + i) * K, cnt[UB * u + i], K);
+        if (a.seed_score && slot < a.n_users) {
+            tau[u] = wave_list_tau(ls + (UB * u + i) * K, cnt[UB * u + i], K);
+            if constexpr (MG) {       // a full seed list whose tail is an item: the rule holds from the first tile
+                if (cnt[UB * u + i] >= K && ls[(UB * u + i) * K + K - 1] > CRH_MASKED_SCORE)
+                    tau[u] = fmaxf(tau[u], ls[(UB * u + i) * K + (a.screen_k < 2 ? 2 : a.screen_k) - 1] - margin);
+            }
+        }
         if (slot >= a.n_users) slot = a.n_users - 1;
         const int64_t row = a.users ? (int64_t)a.users[slot] : a.user_base + slot;
         const char* up = reinterpret_cast<const char*>(a.user_emb) + row * ROWB + 16 * h;
@@ -804,12 +848,12 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
             if constexpr (FULL_FORM) {
                 if (lists_full) {
                     tile_slow_path_dma16<CM, KC, true>(v, tau_u, ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, rows_left, gi0,
-                                                       lane, tb, rfilter, idv);
+                                                       lane, tb, rfilter, idv, margin);
                     return;
                 }
             }
             tile_slow_path_dma16<CM, KC>(v, tau_u, ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, rows_left, gi0, lane, tb,
-                                         rfilter, idv);
+                                         rfilter, idv, margin);
         }
     };
     // body j: MFMAs of tile j (ring slot s_cur) into accumulator set P, threshold test of tile j-1 out of set 1-P;
@@ -991,8 +1035,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                             if constexpr (M16)
                                 event16(acc[Q][u], tau[u], u, ts, rows_left, gi0, tb, idv);
                             else
-                                tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32, CM>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a,
-                                                                                            ts << 5, split_end, lane, tb, rfilter, idv);
+                                tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32, CM, MG>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a,
+                                                                                                ts << 5, split_end, lane, tb, rfilter, idv, margin);
                         }
                     // the list stores of the inserts are drained HERE: left pending, the compiler parks an lgkmcnt(0) at a
                     // later point of the common path, right behind the fragment reads of the barrier group
@@ -1315,6 +1359,8 @@ int score_dma_ring_slots(int esz, int d, int k, int mode) {
 int launch_score_dma(int esz, int d, int mode, const ScoreArgs& a, hipStream_t stream) {
     // both fp16 d=128 launches are the screen's: their 16x16 form is compiled for its K' and takes no other list length
     if (esz == 2 && d == 128 && DMA_SCREEN_M16 && DMA_EVENT_KC != 0 && a.k != DMA_EVENT_KC) return CRH_ERR_ARG;
+    // ... and they carry the margin rule (dma_new_tau): its word and the call's k come with the launch
+    if (esz == 2 && d == 128 && (a.margin == nullptr || a.screen_k < 1 || a.screen_k > a.k)) return CRH_ERR_ARG;
     if (esz == 2 && d == 128 && a.idmap != nullptr) {     // the compacted stream of the screened route
         if (score_dma_lds_bytes(d * esz, a.k, 4, false, true) > 160 * 1024) return CRH_ERR_ARG;
         return launch_score_dma_t<_Float16, 128, 4, false, true, DMA_SCREEN_M16>(a, stream);

@@ -8,13 +8,34 @@ ascending order and for the order by descending norm key (the high 16 bits of th
 events per wave, tiles in which any wave has an event, and the sum over tiles of the busiest wave's candidates.  Tables are drawn
 like the bench's (uniform, xavier bound); --norm-sigma scales the item rows by a lognormal factor.
 
+Every count is printed with the MARGIN rule off and on: with it, once a list is full, a row is a candidate only above
+max(K'-th score, k-th score - M), M = 2 (1 + 2^-10) max B_u from the error bound of oracle/screen_model.py (k = 20).
+
     python tools/screen_order_sim.py [--items 8000000] [--users 512] [--norm-sigma 0.0]
 """
 import argparse
+import os
+import sys
 
 import numpy as np
 
-KP, SEED, TILE, WAVE = 28, 8192, 32, 128
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import screen_model as sm  # noqa: E402
+
+KP, SEED, TILE, WAVE, K = 28, 8192, 32, 128, 20
+
+
+def margin(U, V, chunk=65536):
+    """M of the call in the scores' own units: the item maxima chunk by chunk, B_u of every user, 2 (1 + 2^-10) times the largest."""
+    e_i, e_u = sm.scale_exp(V), sm.scale_exp(U)
+    R = N = Nh = 0.0
+    for c0 in range(0, len(V), chunk):
+        v = V[c0:c0 + chunk]
+        vn, vhn, vdn = sm.row_norms(v, sm.f16_copy(v, e_i))
+        R, N, Nh = max(R, float(vdn.max())), max(N, float(vn.max())), max(Nh, float(vhn.max()))
+    un, uhn, udn = sm.row_norms(U, sm.f16_copy(U, e_u))
+    B, _ = sm.bound(un, uhn, udn, R, N, Nh)
+    return np.float32(2.0 * (1.0 + 2.0 ** -10) * B.max()), float(B.max())
 
 
 def norm_keys(V):
@@ -22,8 +43,9 @@ def norm_keys(V):
     return (ss.view(np.uint32) >> 16).astype(np.int64)
 
 
-def stream(U, V, order, chunk=8192):
-    """Events of streaming V[order] behind the seed prefix; returns (events per wave, busy tiles, sum of busiest-wave candidates)."""
+def stream(U, V, order, chunk=8192, M=None):
+    """Events of streaming V[order] behind the seed prefix; returns (events per wave, busy tiles, sum of busiest-wave candidates).
+    M: the margin rule's M (None: the thresholds are the K'-th scores)."""
     nu = U.shape[0]
     n_waves = nu // WAVE
     lists = -np.sort(-(U @ V[:SEED].T), axis=1)[:, :KP].copy()      # descending; column KP-1 is the threshold
@@ -31,11 +53,12 @@ def stream(U, V, order, chunk=8192):
     cand = np.zeros((n_tiles, n_waves), np.int32)
     for c0 in range(0, len(order), chunk):
         S = U @ V[order[c0:c0 + chunk]].T
-        us, ps = np.nonzero(S > lists[:, KP - 1:KP])                 # a superset: thresholds only rise inside the chunk
+        thr = lists[:, KP - 1:KP] if M is None else np.maximum(lists[:, KP - 1:KP], lists[:, K - 1:K] - M)
+        us, ps = np.nonzero(S > thr)                                 # a superset: thresholds only rise inside the chunk
         for j in np.argsort(ps, kind="stable"):
             u, p = us[j], ps[j]
             s = S[u, p]
-            if s > lists[u, KP - 1]:
+            if s > (lists[u, KP - 1] if M is None else max(lists[u, KP - 1], lists[u, K - 1] - M)):
                 row = lists[u]
                 q = np.searchsorted(-row, -s)
                 row[q + 1:] = row[q:-1]
@@ -61,14 +84,23 @@ def main():
     keys = norm_keys(V[SEED:])
     by_norm = main_ids[np.argsort(-keys, kind="stable")]
     print("distinct keys in the main range: %d" % len(np.unique(keys)))
+    M, Bmax = margin(U, V)
+    sd = float((U[:64] @ V[:65536].T).std())
+    print("largest B_u %.3g = %.4f sigma of the scores; M = %.3g" % (Bmax, Bmax / sd, M))
     r_id = stream(U, V, main_ids)
     r_nm = stream(U, V, by_norm)
+    m_id = stream(U, V, main_ids, M=M)
+    m_nm = stream(U, V, by_norm, M=M)
     names = ("events per wave", "tiles where any of the %d waves has an event" % (a.users // WAVE),
              "sum over tiles of the busiest wave's candidates")
     print("| | id order | main range by descending norm key | change |")
     print("|---|---|---|---|")
     for n, x, y in zip(names, r_id, r_nm):
         print("| %s | %.0f | %.0f | %+.1f %% |" % (n, x, y, 100.0 * (y - x) / x))
+    print("| with the margin rule | id order | main range by descending norm key | change against the rule off (id order / norm order) |")
+    print("|---|---|---|---|")
+    for n, x, y, x0, y0 in zip(names, m_id, m_nm, r_id, r_nm):
+        print("| %s | %.0f | %.0f | %+.1f %% / %+.1f %% |" % (n, x, y, 100.0 * (x - x0) / x0, 100.0 * (y - y0) / y0))
 
 
 if __name__ == "__main__":
