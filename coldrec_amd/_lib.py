@@ -38,6 +38,9 @@ SIGNATURES = {
     "crh_score_topk_screen_plan": (_i32, [_i64, _i64, _sz, _i32, _vp, _vp]),
     "crh_score_topk_screen_ordered": (_i32, [_i64, _i64, _sz, _i32]),
     "crh_score_topk_screen_map": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "crh_score_topk_screen_rated_tiles": (_i32, [_i64, _i64, _sz, _i32, _i32]),
+    "crh_score_topk_screen_flags_bytes": (_sz, [_i64, _i64]),
+    "crh_score_topk_screen_flags": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
     "crh_score_topk_f32": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp,
                                   _vp, _sz, _vp]),
     "crh_score_topk_f32_ex": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp,

@@ -220,6 +220,35 @@ __global__ __launch_bounds__(256) void screen_mapkeys_kernel(const uint16_t* __r
     if (q < n) out[q] = (int32_t)(uint16_t)~skeys[q];
 }
 
+// inv[map[q] - g0] = q for the live rows of the map stage 1 streams by (launch_screen_invmap)
+__global__ __launch_bounds__(256) void screen_invmap_kernel(const int32_t* __restrict__ map, const unsigned* __restrict__ n_live, int64_t g0,
+                                                            int32_t* __restrict__ inv) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < (int64_t)*n_live) inv[(int64_t)map[q] - g0] = (int32_t)q;
+}
+
+// The rated-tile flags (ScoreArgs::rated_tiles), one thread per rated entry of the call (grid-stride: the host does not know their
+// number).  The entry's owner is the last slot whose list starts at or before it; an id outside the main range [g0, g1), or cold
+// under the bitmap, is not in the stream and sets nothing.  nb = 256-byte pieces per workgroup.
+__global__ __launch_bounds__(256) void screen_rated_tiles_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                                 int64_t n_users, const uint32_t* __restrict__ bitmap, int64_t g0, int64_t g1,
+                                                                 const int32_t* __restrict__ inv, uint32_t* __restrict__ flags, int64_t nb) {
+    const int64_t e0 = rowptr[0], e1 = rowptr[n_users];
+    for (int64_t e = e0 + (int64_t)blockIdx.x * 256 + threadIdx.x; e < e1; e += (int64_t)gridDim.x * 256) {
+        const int64_t v = col[e];
+        if (v < g0 || v >= g1) continue;
+        if ((bitmap[v >> 5] >> (v & 31)) & 1u) continue;
+        int64_t lo = 0, hi = n_users;                 // the owner: the last slot with rowptr[slot] <= e
+        while (hi - lo > 1) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (rowptr[mid] <= e) lo = mid;
+            else hi = mid;
+        }
+        const int64_t wave = lo >> 7, t = (int64_t)inv[v - g0] >> 5;
+        atomicOr(flags + ((wave >> 2) * nb * 64 + (t >> 3)), 1u << (4 * (int)(t & 7) + (int)(wave & 3)));
+    }
+}
+
 // Item shard -> fp16 in the fragment-ordered packed layout of pack_items_f16_kernel<128> (tile t, unit c = 8 elements of row r at
 // ((t * 8 + c / 2) * 64 + (c & 1) * 32 + r)), bitmap-masked rows zero; the maxima of |v - v^|, |v|, |v^| over the unmasked rows
 // go to stats[2..4].  Grid-stride over tiles; 16 lanes per row.
@@ -608,6 +637,26 @@ int launch_screen_map(const uint32_t* bitmap, int64_t item_base, int64_t n_items
     return CRH_OK;
 }
 
+int launch_screen_invmap(const int32_t* map, const unsigned* n_live, int64_t g0, int64_t n_main, int32_t* inv, hipStream_t st) {
+    hipLaunchKernelGGL(screen_invmap_kernel, dim3((unsigned)((n_main + 255) / 256)), dim3(256), 0, st, map, n_live, g0, inv);
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
+size_t screen_rated_tiles_bytes(int64_t n_users, int64_t n_main) {
+    const int64_t groups = ((n_users + 127) / 128 + 3) / 4;
+    return (size_t)(groups * screen_rated_blocks(n_main)) * 256;
+}
+
+int launch_screen_rated_tiles(const int64_t* rated_rowptr, const int32_t* rated_col, int64_t n_users, const uint32_t* bitmap, int64_t g0,
+                              int64_t g1, const int32_t* inv, uint32_t* flags, hipStream_t st) {
+    CRH_HIP(hipMemsetAsync(flags, 0, screen_rated_tiles_bytes(n_users, g1 - g0), st));
+    hipLaunchKernelGGL(screen_rated_tiles_kernel, dim3(4096), dim3(256), 0, st, rated_rowptr, rated_col, n_users, bitmap, g0, g1, inv, flags,
+                       screen_rated_blocks(g1 - g0));
+    CRH_HIP(hipGetLastError());
+    return CRH_OK;
+}
+
 int launch_screen_prep_items(const ScreenArgs& s, unsigned* stats, _Float16* packed, int64_t prefix, int32_t* idmap, unsigned* scan,
                              const ScreenOrder* ord, hipStream_t st) {
     const int64_t T = (s.n_items + 31) / 32;     // (compacted: the upper bound; the kernel walks the live tiles)
@@ -642,12 +691,14 @@ int launch_screen_prep_users(const ScreenArgs& s, _Float16* uh, int margin_on, h
 // Only the map construction of stage 0, into buffers of its own (crh_score_topk_screen_map; synchronises): map_out and keys_out take
 // n_items - prefix entries each, the first *count of them meaningful.
 int screen_map_only(const uint32_t* bitmap, const float* item_emb, int64_t n_items, int64_t item_base, int64_t prefix, int ordered,
-                    int32_t* map_out, int32_t* keys_out, int64_t* count, hipStream_t st) {
+                    int32_t* map_out, int32_t* keys_out, int64_t* count, hipStream_t st, const int64_t* rated_rowptr,
+                    const int32_t* rated_col, int64_t n_users, uint32_t* flags_out) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const int64_t n_main = n_items - prefix, n_slots = screen_map_slots(n_main);
     const size_t o_scan = 256, o_map = o_scan + al(screen_scan_bytes(n_main)), o_rk = o_map + al((size_t)n_slots * 4),
                  o_k0 = o_rk + al((size_t)n_items * 2), o_k1 = o_k0 + al((size_t)n_slots * 2), o_m1 = o_k1 + al((size_t)n_slots * 2),
-                 o_tmp = o_m1 + al((size_t)n_slots * 4), total = o_tmp + screen_sort_bytes(n_slots);
+                 o_tmp = o_m1 + al((size_t)n_slots * 4), o_inv = o_tmp + al(screen_sort_bytes(n_slots)),
+                 total = o_inv + (flags_out ? al((size_t)n_main * 4) : 0);
     char* buf = nullptr;
     CRH_HIP(hipMalloc(reinterpret_cast<void**>(&buf), total));
     ScreenOrder ord;
@@ -675,6 +726,12 @@ int screen_map_only(const uint32_t* bitmap, const float* item_emb, int64_t n_ite
     }
     if (e == hipSuccess && rc == CRH_OK)
         e = hipMemcpyAsync(map_out, ordered ? ord.idmap : idmap, (size_t)n_main * 4, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && rc == CRH_OK && flags_out != nullptr) {
+        int32_t* inv = reinterpret_cast<int32_t*>(buf + o_inv);
+        rc = launch_screen_invmap(ordered ? ord.idmap : idmap, stats + SCREEN_STAT_LIVE, item_base + prefix, n_main, inv, st);
+        if (rc == CRH_OK)
+            rc = launch_screen_rated_tiles(rated_rowptr, rated_col, n_users, bitmap, item_base + prefix, item_base + n_items, inv, flags_out, st);
+    }
     if (e == hipSuccess && rc == CRH_OK) e = hipMemcpyAsync(&live, stats + SCREEN_STAT_LIVE, 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(buf);

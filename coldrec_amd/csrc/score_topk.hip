@@ -992,12 +992,14 @@ int screen_splits(int64_t n_users, int64_t n_main, bool seeded) {
     return s;
 }
 struct ScreenLayout {
-    size_t stats, ustat, fail, uh, seed, cand, packed, tbits, sync, idmap, scan, rowkeys, skeys, idmap2, sorttmp, scratch, need;
+    size_t stats, ustat, fail, uh, seed, cand, packed, tbits, sync, idmap, scan, rowkeys, skeys, idmap2, sorttmp, inv, rtiles, scratch, need;
 };
 // compact: with the live-row map of the main range (one id per item, rounded up to whole tiles plus the one the id DMA of the
 // last tile may touch: screen_map_slots) and the block sums of its scan; ordered (needs compact): behind them the norm keys of
-// the shard's rows, the sort keys along both maps, the sorted map and the sort's temporary storage
-ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool compact = false, bool ordered = false) {
+// the shard's rows, the sort keys along both maps, the sorted map and the sort's temporary storage; rated_tiles (needs compact): the
+// inverse of the streamed map (sized like it) and the call's rated-tile flags (screen_rated_tiles_bytes)
+ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool compact = false, bool ordered = false,
+                           bool rated_tiles = false) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     ScreenLayout L;
     L.stats = 0;
@@ -1017,7 +1019,10 @@ ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool com
     L.skeys = L.rowkeys + (ordered ? al((size_t)n_items * sizeof(uint16_t)) : 0);
     L.idmap2 = L.skeys + (ordered ? 2 * al(slots * sizeof(uint16_t)) : 0);
     L.sorttmp = L.idmap2 + (ordered ? al(slots * sizeof(int32_t)) : 0);
-    L.scratch = L.sorttmp + (ordered ? al(screen_sort_bytes((int64_t)slots)) : 0);
+    rated_tiles = rated_tiles && compact;
+    L.inv = L.sorttmp + (ordered ? al(screen_sort_bytes((int64_t)slots)) : 0);
+    L.rtiles = L.inv + (rated_tiles ? al(slots * sizeof(int32_t)) : 0);
+    L.scratch = L.rtiles + (rated_tiles ? al(screen_rated_tiles_bytes(n_users, n_items - P)) : 0);
     // scratch: the stage-1 split lists, the prefix's score block (one 64-user group at the least) and the fallback's slice lists
     const int S = screen_splits(n_users, n_items - P, P > 0);
     const size_t lists = S > 1 ? (size_t)S * n_users * SCREEN_KP * 8 : 0;
@@ -1052,6 +1057,16 @@ bool screen_ordered(int64_t n_users, int64_t n_items, size_t workspace_bytes, bo
     const int64_t P = screen_prefix(n_items);
     if (screen_splits(n_users, n_items - P, P > 0) != 1) return false;
     return workspace_bytes >= screen_layout(n_users, n_items, P, true, true).need;
+}
+// CRH_SCORE_SCREEN_RATED_TILES (read per call): 1 (default) a compacted call with rated lists flags, per workgroup of 512 users and
+// tile of the stream, the waves that rated a row of the tile, and stage 1 consults a user's filter (and on a hit its list) only in
+// flagged tiles -- when the workspace holds the flags and the inverse map as well; 0, or a workspace without the room, passes no
+// flags and the call runs as before.  Never changes the route, the compaction or the order.
+bool screen_rated_tiles(int64_t n_users, int64_t n_items, size_t workspace_bytes, bool has_bitmap, bool has_rated) {
+    const char* e = getenv("CRH_SCORE_SCREEN_RATED_TILES");
+    if (!has_rated || (e && atoi(e) == 0) || !screen_compact(n_users, n_items, workspace_bytes, has_bitmap)) return false;
+    const bool ordered = screen_ordered(n_users, n_items, workspace_bytes, has_bitmap);
+    return workspace_bytes >= screen_layout(n_users, n_items, screen_prefix(n_items), true, ordered, true).need;
 }
 bool screen_route(int esz, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes, bool has_bitmap, int n_splits) {
     const int mode = screen_mode();
@@ -1213,15 +1228,16 @@ int print_wave_timing(unsigned long long* dev, int64_t n_waves, int timing, hipS
     return CRH_OK;
 }
 // CRH_SCORE_TIMING of a DMA-kernel launch (score_topk_impl and the screened route's stage 1): per-tile duration histograms of the
-// first 16 workgroups' waves (64 buckets) + [wave][cycles in events, events], printed to stderr after the launch
+// first 16 workgroups' waves (64 buckets) + [wave][cycles in events, events] + [wave][cycles in the events' memory trips, trips],
+// printed to stderr after the launch
 int dma_timing_begin(ScoreArgs& a, hipStream_t st) {
-    CRH_HIP(hipMalloc(&a.wave_clock, (size_t)16 * 4 * 66 * 8));
-    CRH_HIP(hipMemsetAsync(a.wave_clock, 0, (size_t)16 * 4 * 66 * 8, st));
+    CRH_HIP(hipMalloc(&a.wave_clock, (size_t)16 * 4 * 68 * 8));
+    CRH_HIP(hipMemsetAsync(a.wave_clock, 0, (size_t)16 * 4 * 68 * 8, st));
     return CRH_OK;
 }
 int dma_timing_report(ScoreArgs& a, int esz, int d, hipStream_t st) {
     CRH_HIP(hipStreamSynchronize(st));
-    std::vector<unsigned long long> h((size_t)16 * 4 * 66);
+    std::vector<unsigned long long> h((size_t)16 * 4 * 68);
     CRH_HIP(hipMemcpy(h.data(), a.wave_clock, h.size() * 8, hipMemcpyDeviceToHost));
     CRH_HIP(hipFree(a.wave_clock));
     {
@@ -1230,6 +1246,7 @@ int dma_timing_report(ScoreArgs& a, int esz, int d, hipStream_t st) {
         fprintf(stderr, "[crh dma timing] events: %.0f per wave, %.0f cycles each (tiles with at least one candidate; 64 waves)\n",
                 (double)ne / 64.0, ne ? (double)tk / (double)ne : 0.0);
     }
+    unsigned long long trip_tk = 0, trip_n = 0, loop_cycles = 0;     // the events' memory trips; cycles of the timed tile pairs
     for (int wv = 0; wv < 4; ++wv) {
         unsigned long long tot = 0, wsum = 0;
         std::vector<unsigned long long> b(64, 0);
@@ -1241,7 +1258,13 @@ int dma_timing_report(ScoreArgs& a, int esz, int d, hipStream_t st) {
                 tot ? (double)wsum / (double)tot : 0.0, bw);
         for (int q = 0; q < 64; ++q) fprintf(stderr, " %llu", b[q]);
         fprintf(stderr, "\n");
+        loop_cycles += 2 * wsum;      // (a count is a pair of tiles)
     }
+    for (int q = 0; q < 64; ++q) { trip_tk += h[(size_t)16 * 4 * 66 + 2 * q]; trip_n += h[(size_t)16 * 4 * 66 + 2 * q + 1]; }
+    fprintf(stderr, "[crh dma timing] memory trips inside events (filter hit -> list bounds + search): %.0f per wave, %.0f cycles each, "
+                    "%.0f cycles per wave = %.4f of the timed tile loop (64 waves)\n",
+            (double)trip_n / 64.0, trip_n ? (double)trip_tk / (double)trip_n : 0.0, (double)trip_tk / 64.0,
+            loop_cycles ? (double)trip_tk / (double)loop_cycles : 0.0);
     a.wave_clock = nullptr;
     return CRH_OK;
 }
@@ -1291,6 +1314,7 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
     a.seed_idx = seed_idx;
     a.margin = nullptr;         // (the screen's rule: score_topk_screened)
     a.screen_k = 0;
+    a.rated_tiles = nullptr;
     const int64_t T = (n_items + 31) / 32;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
@@ -1480,7 +1504,8 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     const int64_t P = screen_prefix(n_items);
     const bool compact = screen_compact(n_users, n_items, workspace_bytes, cand_bitmap != nullptr);
     const bool ordered = screen_ordered(n_users, n_items, workspace_bytes, cand_bitmap != nullptr);
-    const ScreenLayout L = screen_layout(n_users, n_items, P, compact, ordered);
+    const bool rated_tiles = screen_rated_tiles(n_users, n_items, workspace_bytes, cand_bitmap != nullptr, rated_rowptr != nullptr);
+    const ScreenLayout L = screen_layout(n_users, n_items, P, compact, ordered, rated_tiles);
     CRH_CHECK_ARG(workspace_bytes >= L.need, "%s: workspace %zu < %zu bytes (screened route)", who, workspace_bytes, L.need);
     int32_t* idmap = compact ? reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + L.idmap) : nullptr;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1576,6 +1601,7 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     a.n_live = nullptr;
     a.margin = nullptr;         // (the prefix is ranked whole: the rule is stage 1's DMA launch's)
     a.screen_k = 0;
+    a.rated_tiles = nullptr;
     if (P > 0) {
         const int64_t stride = P;                       // P is a multiple of 32
         const int upw_pw = users_per_wave(2, D);
@@ -1638,6 +1664,17 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     if (compact) {               // the stream holds the unmasked rows only: no tile bits, the rows' ids instead
         a.idmap = stream_map;       // (ordered: one cut, the only launch that may stream another order)
         a.n_live = s.stats + SCREEN_STAT_LIVE;
+        if (rated_tiles) {          // the call's rated-tile flags: they depend on the users, so they are built per call
+            // (and with them the inverse of the streamed map, prepared or not: a prepared state has no room for a second map --
+            // its size is pinned to the copy and one id per row -- and the inverse costs a call 0.1 ms at 10 M rows)
+            int32_t* inv = reinterpret_cast<int32_t*>(ws + L.inv);
+            uint32_t* rt = reinterpret_cast<uint32_t*>(ws + L.rtiles);
+            rc = launch_screen_invmap(stream_map, a.n_live, item_base + P, n_main, inv, st);
+            if (rc != CRH_OK) return rc;
+            rc = launch_screen_rated_tiles(rated_rowptr, rated_col, n_users, cand_bitmap, item_base + P, item_base + n_items, inv, rt, st);
+            if (rc != CRH_OK) return rc;
+            a.rated_tiles = rt;
+        }
     } else if (cand_bitmap) {
         a.tile_bits = tbits;        // (of the main range: screen_items_build)
     }
@@ -1753,6 +1790,41 @@ extern "C" int crh_score_topk_screen_plan(int64_t n_users, int64_t n_items, size
 extern "C" int crh_score_topk_screen_ordered(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap) {
     if (n_users <= 0 || n_items <= 0) return 0;
     return screen_ordered(n_users, n_items, workspace_bytes, has_bitmap != 0) ? 1 : 0;
+}
+
+// Would a screened call of this shape gate stage 1's rated lookups by per-tile flags (CRH_SCORE_SCREEN_RATED_TILES, read per call:
+// 1 default)?  Needs the compaction, rated lists and a workspace that holds the flags and the inverse map.
+extern "C" int crh_score_topk_screen_rated_tiles(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap, int has_rated) {
+    if (n_users <= 0 || n_items <= 0) return 0;
+    return screen_rated_tiles(n_users, n_items, workspace_bytes, has_bitmap != 0, has_rated != 0) ? 1 : 0;
+}
+
+// Bytes of the rated-tile flags of a call of n_users slots over a main range of n_main items: per workgroup of 512 slots one 256-byte
+// piece per 512 tiles, word t >> 3 and nibble 4 (t & 7) of the workgroup's run for tile t, bit w for its wave w.
+extern "C" size_t crh_score_topk_screen_flags_bytes(int64_t n_users, int64_t n_main) {
+    if (n_users <= 0 || n_main <= 0) return 0;
+    return screen_rated_tiles_bytes(n_users, n_main);
+}
+
+// Only the flag construction of the screened route, for tests: the map of crh_score_topk_screen_map, its inverse, and the rated-tile
+// flags of a call of n_users slots with these rated lists into flags_out (device, crh_score_topk_screen_flags_bytes).  Allocates its own
+// buffers and synchronises `stream`.
+extern "C" int crh_score_topk_screen_flags(const uint32_t* bitmap, const float* item_emb, int64_t n_items, int64_t item_base,
+                                           int64_t prefix, int ordered, const int64_t* rated_rowptr, const int32_t* rated_col,
+                                           int64_t n_users, uint32_t* flags_out, void* stream) {
+    CRH_CHECK_ARG(bitmap && item_emb && rated_rowptr && rated_col && flags_out, "crh_score_topk_screen_flags: NULL argument");
+    CRH_CHECK_ARG(n_users > 0 && prefix >= 0 && (prefix & 31) == 0 && n_items > prefix, "crh_score_topk_screen_flags: prefix %lld of %lld items",
+                  (long long)prefix, (long long)n_items);
+    CRH_CHECK_ARG(((uintptr_t)item_emb & 15) == 0, "crh_score_topk_screen_flags: table must be 16-byte aligned");
+    CRH_CHECK_ARG(item_base >= 0 && item_base + n_items < (int64_t)CRH_PAD_IDX, "crh_score_topk_screen_flags: item ids exceed int32");
+    const int64_t n_main = n_items - prefix;
+    int32_t* tmp = nullptr;
+    CRH_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), (size_t)n_main * 8));
+    int64_t count = 0;
+    const int rc = screen_map_only(bitmap, item_emb, n_items, item_base, prefix, ordered, tmp, tmp + n_main, &count,
+                                   reinterpret_cast<hipStream_t>(stream), rated_rowptr, rated_col, n_users, flags_out);
+    (void)hipFree(tmp);
+    return rc;
 }
 
 // Only the map construction of the screened route's stage 0, for tests: the live-row map of [item_base + prefix, item_base +

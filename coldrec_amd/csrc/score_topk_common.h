@@ -54,7 +54,14 @@ struct ScoreArgs {
     // NULL: the thresholds are the lists' tails (every other launch).
     const float* margin;
     int screen_k;
+    // The screen's RATED-TILE flags (compacted stream only): four bits per (workgroup = four waves of 128 users, tile of
+    // the stream), bit w set iff a user of wave w rated an item whose live row lies in the tile (screen_rated_tiles_kernel).  Workgroup
+    // g owns screen_rated_blocks(n_items) pieces of 64 words, word t >> 3 and nibble 4 (t & 7) for tile t.  A candidate in a tile whose
+    // bit is clear is unrated by construction and skips the filter and the search.  NULL: every bit counts as set.
+    const uint32_t* rated_tiles;
 };
+// 256-byte pieces (512 tiles each) of one workgroup's rated-tile flags over a stream of at most n_rows rows
+__host__ __device__ constexpr int64_t screen_rated_blocks(int64_t n_rows) { return (((n_rows + 31) >> 5) + 511) >> 9; }
 
 // in : lane (i,0) holds k = 8q+0..3 of row i, lane (i,1) holds k = 8q+4..7
 // out: .x = {8q | 8q+1}, .z = {8q+2 | 8q+3}, .y = {8q+4 | 8q+5}, .w = {8q+6 | 8q+7}  (low | high half)
@@ -457,9 +464,22 @@ __attribute__((visibility("hidden"))) int launch_screen_prep_items(const ScreenA
                                                                    int32_t* idmap, unsigned* scan, const ScreenOrder* ord, hipStream_t st);
 // margin_on = 0 (CRH_SCORE_SCREEN_MARGIN=0): the margin word is +inf, stage 1 keeps the lists' tails as thresholds
 __attribute__((visibility("hidden"))) int launch_screen_prep_users(const ScreenArgs& s, _Float16* uh, int margin_on, hipStream_t st);
+// flags_out != NULL: also the rated-tile flags of a call of n_users slots with these lists over that map (screen_rated_tiles_bytes)
 __attribute__((visibility("hidden"))) int screen_map_only(const uint32_t* bitmap, const float* item_emb, int64_t n_items,
                                                           int64_t item_base, int64_t prefix, int ordered, int32_t* map_out,
-                                                          int32_t* keys_out, int64_t* count, hipStream_t st);
+                                                          int32_t* keys_out, int64_t* count, hipStream_t st,
+                                                          const int64_t* rated_rowptr = nullptr, const int32_t* rated_col = nullptr,
+                                                          int64_t n_users = 0, uint32_t* flags_out = nullptr);
+// The inverse of the map stage 1 streams by: inv[id - (item_base + prefix)] = stream row of a live id (a cold id's entry is never
+// written, and never read); n_main entries.  Built per call beside the flags.
+__attribute__((visibility("hidden"))) int launch_screen_invmap(const int32_t* map, const unsigned* n_live, int64_t g0, int64_t n_main,
+                                                               int32_t* inv, hipStream_t st);
+// The rated-tile flags of a call (ScoreArgs::rated_tiles): cleared, then one atomicOr per rated entry whose id is a live row of the
+// main range [g0, g1).  Per call: they depend on the users.
+__attribute__((visibility("hidden"))) size_t screen_rated_tiles_bytes(int64_t n_users, int64_t n_main);
+__attribute__((visibility("hidden"))) int launch_screen_rated_tiles(const int64_t* rated_rowptr, const int32_t* rated_col, int64_t n_users,
+                                                                    const uint32_t* bitmap, int64_t g0, int64_t g1, const int32_t* inv,
+                                                                    uint32_t* flags, hipStream_t st);
 __attribute__((visibility("hidden"))) int launch_screen_certify(const ScreenArgs& s, hipStream_t st);
 
 }  // namespace crh_score

@@ -19,9 +19,14 @@ constexpr int FLAGS_B = 64;         // flag form: ready[<= 8] and done[<= 8] cou
 // When body j issues it every wave has selected tile j-2, and tile j+4 shares a slot with tile j-4: eight slots are enough.
 constexpr int IDS_SLOTS = 8;
 constexpr int IDS_B = (IDS_SLOTS + 1) * 32 * 4;
+// ... and behind the id slots the RATED-TILE flags of this workgroup (ScoreArgs::rated_tiles): two 256-byte pieces of 512 tiles each,
+// block ts >> 9 in buffer (ts >> 9) & 1.  Wave 0 fetches block b + 1 from the head of a loop trip once every wave is past the last
+// tile of block b - 1 (the trip's own rare path: trip_head), some 448 tiles before the first event that reads it.
+constexpr int RT_B = 2 * 256;
 
 // per-wave LDS of the DMA kernel: the lists (scores, ids, fill) and a 192-bit membership filter of each user's rated list.
-// The rated-list bounds are read from memory when a candidate's filter says "maybe rated" (rare).  k = 20: 188 bytes per user,
+// The rated-list bounds are read from memory when a candidate's filter says "maybe rated" -- NOT rare where lists are long: an unrated
+// candidate hits with probability 1 - e^(-len/192), one in five at the headline's lists.  k = 20: 188 bytes per user,
 // 94 KiB per workgroup beside the 64 KiB ring.
 constexpr int DMA_FW = 6;           // filter words per user
 __host__ __device__ constexpr size_t dma_wave_lds_bytes(int K) {
@@ -93,6 +98,25 @@ __device__ __forceinline__ float dma_new_tau(float tail, float es, float sc, int
     return t;
 }
 
+// CRH_SCORE_TIMING (profile build): the memory trips taken inside events -- a hit in the user's filter, then the list bounds and the
+// search -- and the cycles spent in them, per wave.  The sums travel down to the candidate as one more argument of the profile build.
+#ifdef CRH_PROFILE
+struct DmaTripProf { unsigned long long ticks, count; };
+#define CRH_TRIP_PARAM , DmaTripProf& tp
+#define CRH_TRIP_ARG , tp
+#define CRH_TRIP_BEGIN const unsigned long long trip_t0 = a.wave_clock != nullptr ? __builtin_amdgcn_s_memtime() : 0ull
+#define CRH_TRIP_END                                                   \
+    if (a.wave_clock != nullptr) {                                     \
+        tp.ticks += __builtin_amdgcn_s_memtime() - trip_t0;            \
+        tp.count += 1;                                                 \
+    }
+#else
+#define CRH_TRIP_PARAM
+#define CRH_TRIP_ARG
+#define CRH_TRIP_BEGIN
+#define CRH_TRIP_END
+#endif
+
 // One candidate of an event, shared by the 32x32 and the 16x16 forms of the slow path: the LDS batch read, the "cannot enter"
 // test, the rated filter with its bounded search, the insert and the user's new threshold out of registers.  sc / gi = the
 // candidate's score and id, bm_masked = its candidate-bitmap bit, ul / slot = its user's column in the wave and slot in the call,
@@ -101,10 +125,13 @@ __device__ __forceinline__ float dma_new_tau(float tail, float es, float sc, int
 // wave's own lists, ids and fills: K + 64 words stay inside them) and nobody uses them; the clamp and the select that blanks the
 // lanes >= n cost the event two registers that the 16x16 form does not have.
 // MG: the margin rule above (margin = the call's M).
-template <bool ONE_TRIP, bool LANE_READ = false, bool MG = false>
+// RT (the compacted stream): rt = "a user of this wave rated a row of the candidate's tile", the wave's bit of the tile's rated-tile flags,
+// worked out once per event by the caller.  Clear, the candidate is unrated by construction: no filter word, no search.  Without RT
+// the filter is consulted whenever the call has rated lists.
+template <bool ONE_TRIP, bool LANE_READ = false, bool MG = false, bool RT = false>
 __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, int ul, int64_t slot, float* ls, int* li, int* cnt, int K,
                                               const ScoreArgs& a, int lane, const unsigned* rfilter, bool mine, float& tau_reg,
-                                              float margin = 0.0f) {
+                                              float margin, bool rt CRH_TRIP_PARAM) {
     float* lsu = ls + ul * K;
     int* liu = li + ul * K;
     // one batch of LDS reads: fill, tail entry, filter word
@@ -113,7 +140,7 @@ __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, 
     const int le = ONE_TRIP ? (LANE_READ ? lane : (lane < K ? lane : K - 1)) : K - 1;   // (ONE_TRIP: lane l reads entry l; the others the tail entry)
     const float ks_raw = lsu[le];
     const int ki_raw = liu[le];
-    const unsigned fw_raw = a.rated_rowptr ? rfilter[ul * DMA_FW + (hsh >> 5)] : 0u;
+    const unsigned fw_raw = (RT ? rt : a.rated_rowptr != nullptr) ? rfilter[ul * DMA_FW + (hsh >> 5)] : 0u;
     const int n = __builtin_amdgcn_readfirstlane(n_raw);
     if (n >= K) {
         const float ks = ONE_TRIP ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ks_raw), K - 1))
@@ -123,13 +150,15 @@ __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, 
     }
     bool masked = bm_masked;
     if (!masked && ((__builtin_amdgcn_readfirstlane(fw_raw) >> (hsh & 31)) & 1u)) {
+        CRH_TRIP_BEGIN;
         const int64_t lo = a.rated_rowptr[slot], hi = a.rated_rowptr[slot + 1];
         masked = wave_is_masked_at(gi, lo, hi, a.rated_col, nullptr, lane);
-        // every load of the search has landed HERE, inside the rare branch: left pending on this exit, hipcc guards the
+        // every load of the search has landed HERE, inside the branch: left pending on this exit, hipcc guards the
         // join with s_waitcnt vmcnt(0) -- paid by EVERY event, and vmcnt counts the tile DMAs in flight too: the
         // flag form issued them one group (0.8 us) earlier, the barrier form at 256-byte rows in this very group, so an
         // event waited for a DMA round trip (round 6, found in the ISA; tile_slow_path has had the same fix since round 4)
         __builtin_amdgcn_s_waitcnt(0x0f70);
+        CRH_TRIP_END
     }
     if (masked) sc = CRH_MASKED_SCORE;
     // wave_list_insert (k <= 64 here) that also hands back the user's NEW threshold out of the registers it already
@@ -260,10 +289,10 @@ constexpr bool DMA_EVENT_STRAIGHT = true;
 // dma_candidate<true, true> for a list that is full (K = the compile-time K'): lane l < K holds entry l, an item; there is no fill to
 // read, test or write, and the user's new K-th entry is the old (K-1)-th or the candidate.  The order -- "cannot enter", filter,
 // insert -- and what each outcome writes are dma_candidate's with n = K.
-template <int K>
+template <int K, bool RT>
 __device__ __forceinline__ void dma_candidate_full(float sc, int gi, bool bm_masked, int ul, int64_t slot, float* ls, int* li,
                                                    const ScoreArgs& a, int lane, const unsigned* rfilter, bool mine, float& tau_reg,
-                                                   float margin) {
+                                                   float margin, bool rt CRH_TRIP_PARAM) {
     static_assert(K >= 2 && K < 64, "one entry per lane");
     constexpr unsigned long long LIST = (1ull << K) - 1ull;     // lanes >= K read what lies behind the list (LANE_READ of dma_candidate)
     float* lsu = ls + ul * K;
@@ -272,15 +301,17 @@ __device__ __forceinline__ void dma_candidate_full(float sc, int gi, bool bm_mas
     const unsigned hsh = rated_hash192(gi);
     const float es = lsu[lane];
     const int ei = liu[lane];
-    const unsigned fw_raw = a.rated_rowptr ? rfilter[ul * DMA_FW + (hsh >> 5)] : 0u;
+    const unsigned fw_raw = (RT ? rt : a.rated_rowptr != nullptr) ? rfilter[ul * DMA_FW + (hsh >> 5)] : 0u;
     const float ks = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, es), K - 1));
     const int ki = __builtin_amdgcn_readlane(ei, K - 1);
     if (!crh_better(fmaxf(sc, CRH_MASKED_SCORE), gi, ks, ki)) return;   // cannot enter
     bool masked = bm_masked;
     if (!masked && ((__builtin_amdgcn_readfirstlane(fw_raw) >> (hsh & 31)) & 1u)) {
+        CRH_TRIP_BEGIN;
         const int64_t lo = a.rated_rowptr[slot], hi = a.rated_rowptr[slot + 1];
         masked = wave_is_masked_at(gi, lo, hi, a.rated_col, nullptr, lane);
-        __builtin_amdgcn_s_waitcnt(0x0f70);                     // (the search's loads land inside the rare branch: see dma_candidate)
+        __builtin_amdgcn_s_waitcnt(0x0f70);                     // (the search's loads land inside the branch: see dma_candidate)
+        CRH_TRIP_END
     }
     if (masked) sc = CRH_MASKED_SCORE;
     const int p = __popcll(__ballot(crh_better(es, ei, sc, gi)) & LIST);
@@ -306,7 +337,7 @@ template <bool ONE_TRIP, bool CM, bool MG = false>
 __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau_reg, float* ls, int* li, int* cnt, int K,
                                                    int ucol0, int64_t slot0, const ScoreArgs& a, int64_t item0,
                                                    int64_t split_end, int lane, unsigned tb, const unsigned* rfilter, int idv,
-                                                   float margin = 0.0f) {
+                                                   float margin, bool rt CRH_TRIP_PARAM) {
     unsigned cm = gt_mask16(acc, tau_reg);
     // bits of this lane's 16 rows: rows (r&3) + 8*(r>>2) + 4*hh <-> bit r.  Masked rows are packed as zeros: with no negative
     // threshold in the group none of them is a candidate, and the bit shuffling (a dozen VALU instructions) is skipped
@@ -337,7 +368,7 @@ __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau
             int gi;
             if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, (r & 3) + 8 * (r >> 2) + 4 * hh);
             else gi = (int)(a.item_base + il);
-            dma_candidate<ONE_TRIP, false, MG>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 31) == jl, tau_reg, margin);
+            dma_candidate<ONE_TRIP, false, MG, CM>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 31) == jl, tau_reg, margin, rt CRH_TRIP_ARG);
         }
     }
     // (no read-back of the thresholds: every insert above updated its user's lanes; padding columns keep their +inf)
@@ -395,7 +426,7 @@ __device__ __forceinline__ float pick8u(const f32x8& v, int r) {
 template <bool CM, int KC, bool FULL = false>
 __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& tau_reg, float* ls, int* li, int* cnt, int Krt, int ucol0,
                                                      int64_t slot0, const ScoreArgs& a, int64_t item0, int64_t split_end, int rows_left,
-                                                     int gi0, int lane, unsigned tb, const unsigned* rfilter, int idv, float margin) {
+                                                     int gi0, int lane, unsigned tb, const unsigned* rfilter, int idv, float margin, bool rt CRH_TRIP_PARAM) {
     static_assert(!FULL || KC != 0, "the full-list form is compiled for K'");
     const int K = KC ? KC : Krt;
     unsigned cm = gt_mask8(acc, tau_reg);
@@ -426,9 +457,9 @@ __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& ta
         else if constexpr (DMA_EVENT_TAIL64) gi = (int)(a.item_base + il);
         else gi = gi0 + row;
         if constexpr (FULL)
-            dma_candidate_full<KC>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin);
+            dma_candidate_full<KC, CM>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin, rt CRH_TRIP_ARG);
         else
-            dma_candidate<DMA_SCREEN_ONE_TRIP, true, true>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin);
+            dma_candidate<DMA_SCREEN_ONE_TRIP, true, true, CM>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin, rt CRH_TRIP_ARG);
     };
     if constexpr (FULL && DMA_EVENT_STRAIGHT && !DMA_EVENT_SLOT_TEST) {
         // (one s_bcnt1 and a compare.  Not `lanes & (lanes - 1)`: under a bitmap the masked rows may have left no hit lane at all)
@@ -538,7 +569,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     // a wave may lead the slowest reader by (NG - 2) / NG of a tile and the slowest refiller by one tile
     constexpr int PF = FL ? 2 : 3;
     static_assert(R == 4 && (!FL || sizeof(T) == 4) && !(CM && FL), "ring shape");
-    constexpr int SIDE_B = CM ? IDS_B : TBITS_B;        // the tile bits' or the ids' area behind the ring
+    constexpr int SIDE_B = CM ? IDS_B + RT_B : TBITS_B; // the tile bits' area behind the ring, or the ids' and the rated-tile flags'
     constexpr int ROWB = D * (int)sizeof(T);
     constexpr int NCH = ROWB / 32;
     constexpr int TILE_B = NCH * 1024;
@@ -565,6 +596,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 
     char* ring = smem;                                  // [R][TILE_B]
     unsigned* tbits = reinterpret_cast<unsigned*>(smem + R * TILE_B);   // [2][64]; CM: [IDS_SLOTS + 1][32] ids
+    [[maybe_unused]] unsigned* rtiles = tbits + IDS_B / 4;              // CM: [2][64] rated-tile flags of this workgroup
     unsigned* flags = tbits + SIDE_B / 4;             // FL: ready[R] at 0, done[R] at 8; slots of the prologue's tiles start ready
     if constexpr (FL) {
         // (published by the prologue's barrier.  Tiles 0 .. PF-2 of the prologue start complete; tile PF-1 is bumped by body 0 like
@@ -748,6 +780,16 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.idmap + e),
                                          (__attribute__((address_space(3))) void*)(tbits + (j & (IDS_SLOTS - 1)) * 32), 4, 0, 0);
     };
+    // CM: block blk of this workgroup's rated-tile flags -> rtiles[blk & 1], one word per lane (a block past the stream's last one is
+    // clamped: valid addresses, flags nobody reads).  Without the flags (or without rated lists) the two buffers are filled once, with
+    // ones (every tile takes the filter, as before) or zeros (no lists), and no fetch is ever issued.
+    [[maybe_unused]] const bool rt_fetch = CM && a.rated_tiles != nullptr && a.rated_rowptr != nullptr;
+    [[maybe_unused]] auto dma_rtiles = [&](int64_t blk) __attribute__((always_inline)) {
+        const int64_t nb = screen_rated_blocks(a.n_items);
+        const int64_t bc = blk < nb ? blk : nb - 1;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.rated_tiles + (((int64_t)(blockIdx.x / S) * nb + bc) << 6) + lane),
+                                         (__attribute__((address_space(3))) void*)(rtiles + (blk & 1) * 64), 4, 0, 0);
+    };
     const bool has_bits = !CM && a.bitmap != nullptr;   // without a candidate bitmap tile_bits points at readable filler
     auto dma_wait_all = [&]() __attribute__((always_inline)) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -841,19 +883,20 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 
 #ifdef CRH_PROFILE
     unsigned long long ev_ticks = 0, ev_count = 0;       // CRH_SCORE_TIMING
+    DmaTripProf tp = {0ull, 0ull};                       // ... and the memory trips inside the events
 #endif
     // M16: the event of user block u at tile ts, in the form the wave's flag selects -- one scalar branch per event
-    auto event16 = [&](const AccT& v, float& tau_u, int u, int64_t ts, int rows_left, int gi0, unsigned tb, int idv) __attribute__((always_inline)) {
+    auto event16 = [&](const AccT& v, float& tau_u, int u, int64_t ts, int rows_left, int gi0, unsigned tb, int idv, bool rt) __attribute__((always_inline)) {
         if constexpr (M16) {
             if constexpr (FULL_FORM) {
                 if (lists_full) {
                     tile_slow_path_dma16<CM, KC, true>(v, tau_u, ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, rows_left, gi0,
-                                                       lane, tb, rfilter, idv, margin);
+                                                       lane, tb, rfilter, idv, margin, rt CRH_TRIP_ARG);
                     return;
                 }
             }
             tile_slow_path_dma16<CM, KC>(v, tau_u, ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, rows_left, gi0, lane, tb,
-                                         rfilter, idv, margin);
+                                         rfilter, idv, margin, rt CRH_TRIP_ARG);
         }
     };
     // body j: MFMAs of tile j (ring slot s_cur) into accumulator set P, threshold test of tile j-1 out of set 1-P;
@@ -1023,6 +1066,9 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     const unsigned tb = has_bits ? tbits[((ts >> 6) & 1) * 64 + (ts & 63)] : 0u;
                     int idv = 0;                     // CM: the selected tile's ids, one LDS read per event (where tb's was)
                     if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
+                    // CM: the wave's bit of the tile's rated-tile flags, read with the ids (wave-uniform)
+                    bool rt = false;
+                    if constexpr (CM) rt = (__builtin_amdgcn_readfirstlane(rtiles[(int)((ts >> 9) & 1) * 64 + (int)((ts >> 3) & 63)]) >> (4 * (int)(ts & 7) + wave)) & 1u;
                     // M16: the rows of the selected tile inside the cut (the clamped last tile of a cut holds fewer than 32) and the id of
                     // its first row, once per event
                     const int64_t rl64 = split_end - (ts << 5);
@@ -1033,10 +1079,10 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                         // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
                         if ((M16 && !DMA_EVENT_REBALLOT) ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull) {
                             if constexpr (M16)
-                                event16(acc[Q][u], tau[u], u, ts, rows_left, gi0, tb, idv);
+                                event16(acc[Q][u], tau[u], u, ts, rows_left, gi0, tb, idv, rt);
                             else
                                 tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32, CM, MG>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a,
-                                                                                                ts << 5, split_end, lane, tb, rfilter, idv, margin);
+                                                                                                ts << 5, split_end, lane, tb, rfilter, idv, margin, rt CRH_TRIP_ARG);
                         }
                     // the list stores of the inserts are drained HERE: left pending, the compiler parks an lgkmcnt(0) at a
                     // later point of the common path, right behind the fragment reads of the barrier group
@@ -1188,6 +1234,9 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     const unsigned tb = has_bits ? tbits[((ts >> 6) & 1) * 64 + (ts & 63)] : 0u;
                     int idv = 0;                     // CM: the selected tile's ids, one LDS read per event (where tb's was)
                     if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
+                    // CM: the wave's bit of the tile's rated-tile flags, read with the ids (wave-uniform)
+                    bool rt = false;
+                    if constexpr (CM) rt = (__builtin_amdgcn_readfirstlane(rtiles[(int)((ts >> 9) & 1) * 64 + (int)((ts >> 3) & 63)]) >> (4 * (int)(ts & 7) + wave)) & 1u;
                     // the rows of the selected tile inside the cut (the clamped last tile of a cut holds fewer than 32) and the id of its
                     // first row, once per event
                     const int64_t rl64 = split_end - (ts << 5);
@@ -1198,7 +1247,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                         // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
                         if (!DMA_EVENT_REBALLOT ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull)
                             if constexpr (M16)       // (the other forms never call this body, but they parse it)
-                                event16(acc[Q][u], tau[u], u, ts, rows_left, gi0, tb, idv);
+                                event16(acc[Q][u], tau[u], u, ts, rows_left, gi0, tb, idv, rt);
                     // the list stores of the inserts are drained HERE (as in `body`); the fragment reads in flight land with them
                     __builtin_amdgcn_s_waitcnt(0xc07f);
 #ifdef CRH_PROFILE
@@ -1219,6 +1268,12 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         if constexpr (CM) {
             dma_ids(0);                                   // tiles 0 .. 3; body j brings tile j + 3 (and j + 4)
             dma_ids(2);
+            if (rt_fetch) {                               // the cut's first two blocks, by every wave (identical bytes)
+                dma_rtiles(t0 >> 9);
+                dma_rtiles((t0 >> 9) + 1);
+            } else {
+                for (int q = lane; q < RT_B / 4; q += 64) rtiles[q] = a.rated_rowptr != nullptr ? ~0u : 0u;
+            }
         } else {
             dma_tbits(t0 >> 6);
             dma_tbits((t0 >> 6) + 1);
@@ -1244,6 +1299,16 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
             if (win_steps < 2) win_steps = 2;
             next_sync = 0;
         }
+        // CM: the trip head's rare path serves two clocks, the lockstep windows (next_win) and wave 0's fetch of the next block of
+        // rated-tile flags (next_rt); next_sync, which the loop tests, is the earlier of the two.  Block b + 1 is asked for at the first
+        // trip head 64 tiles into block b: every wave has passed the barrier of the body before, so the last tile of block b - 1 -- the
+        // buffer's old content -- was selected long ago, and the wave's own counted DMA wait of the next body but one publishes the piece
+        // at that body's barrier, 440 tiles before its first reader.  Blocks t0 >> 9 and the next one come with the prologue.
+        [[maybe_unused]] int next_win = next_sync, next_rt = n_steps + 4;
+        if constexpr (CM) {
+            if (rt_fetch && wave == 0) next_rt = (int)(((((t0 >> 9) + 1) << 9) + 64) - t0);
+            next_sync = next_win < next_rt ? next_win : next_rt;
+        }
 #ifdef CRH_PROFILE
         unsigned long long t_prev = 0;                  // CRH_SCORE_TIMING: duration of every PAIR of tiles, histogrammed per wave
 #endif
@@ -1261,16 +1326,28 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 t_prev = t_now;
             }
 #endif
-            if (due) {       // j >= next_sync && j < n_steps: wave 0 only (next_sync stays beyond the range elsewhere)
+            auto window = [&](int& nxt) __attribute__((always_inline)) {
                 const int win = j / win_steps;
                 if (xcd_window_sync(sync_cnt, win, lane)) {
-                    next_sync += win_steps;
+                    nxt += win_steps;
                 } else {                // timed out: run free, and count this workgroup into every window it will not report
-                    next_sync = n_steps + 4;
+                    nxt = n_steps + 4;
                     const int n_win = (n_steps + win_steps - 1) / win_steps;
                     if (lane == 0)
                         for (int wdw = win; wdw < n_win; ++wdw)
                             __hip_atomic_fetch_add(sync_cnt + 1 + wdw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            };
+            if (due) {       // j >= next_sync && j < n_steps: wave 0 only (next_sync stays beyond the range elsewhere)
+                if constexpr (CM) {
+                    if (j >= next_rt) {
+                        dma_rtiles(((t0 + j) >> 9) + 1);
+                        next_rt += 512;
+                    }
+                    if (j >= next_win) window(next_win);
+                    next_sync = next_win < next_rt ? next_win : next_rt;
+                } else {
+                    window(next_sync);
                 }
             }
         };
@@ -1308,6 +1385,8 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     if (a.wave_clock != nullptr && blockIdx.x < 16 && lane == 0) {
         a.wave_clock[(size_t)16 * 4 * 64 + ((size_t)blockIdx.x * 4 + wave) * 2] = ev_ticks;
         a.wave_clock[(size_t)16 * 4 * 64 + ((size_t)blockIdx.x * 4 + wave) * 2 + 1] = ev_count;
+        a.wave_clock[(size_t)16 * 4 * 66 + ((size_t)blockIdx.x * 4 + wave) * 2] = tp.ticks;
+        a.wave_clock[(size_t)16 * 4 * 66 + ((size_t)blockIdx.x * 4 + wave) * 2 + 1] = tp.count;
     }
 #endif
     if (live) {
@@ -1342,7 +1421,7 @@ int launch_score_dma_t(const ScoreArgs& a, hipStream_t stream) {
 }  // namespace
 
 size_t score_dma_lds_bytes(int row_bytes, int k, int ring_slots, bool flags, bool compact) {
-    return (size_t)ring_slots * (row_bytes / 32) * 1024 + (compact ? IDS_B : TBITS_B) + (flags ? FLAGS_B : 0) + DMA_NW * dma_wave_lds_bytes(k);
+    return (size_t)ring_slots * (row_bytes / 32) * 1024 + (compact ? IDS_B + RT_B : TBITS_B) + (flags ? FLAGS_B : 0) + DMA_NW * dma_wave_lds_bytes(k);
 }
 
 // Ring slots of a launch, 0 = the lists do not fit beside the ring.  (A flag form with EIGHT slots for 256-byte rows -- prefetch

@@ -280,6 +280,36 @@ def score_topk_screen_map(cand_bitmap: torch.Tensor, item_emb: torch.Tensor, ite
     return out_map[:count.value], out_keys[:count.value]
 
 
+def score_topk_screen_rated_tiles(n_users: int, n_items: int, d: int, k: int, has_bitmap: bool = True, has_rated: bool = True) -> bool:
+    """Does a screened call of this shape gate the rated-list lookups of its fp16 pass by per-tile flags
+    (CRH_SCORE_SCREEN_RATED_TILES)?  True when the compaction is on, the call has rated lists and the workspace ``score_topk``
+    passes holds the flags and the inverse map."""
+    L = _lib.lib()
+    ws_bytes = L.crh_score_topk_workspace_bytes(n_users, n_items, d, k)
+    return bool(L.crh_score_topk_screen_rated_tiles(n_users, n_items, ws_bytes, 1 if has_bitmap else 0, 1 if has_rated else 0))
+
+
+def score_topk_screen_flags(cand_bitmap: torch.Tensor, item_emb: torch.Tensor, rated_rowptr: torch.Tensor, rated_col: torch.Tensor,
+                            item_base: int = 0, prefix: int = 0, ordered: bool = True) -> torch.Tensor:
+    """Only the rated-tile flags of the screened route (a test entry point): int32 device words ``[workgroups, blocks * 64]`` over
+    the map ``score_topk_screen_map`` returns for the same arguments -- tile ``t`` of the stream in word ``t >> 3``, nibble
+    ``4 * (t & 7)`` of its workgroup's row, bit ``w`` set iff a slot of wave ``w`` (128 slots) rated an item of the tile."""
+    _need_cuda(cand_bitmap, item_emb, rated_rowptr, rated_col)
+    assert cand_bitmap.dtype == torch.int32 and item_emb.dtype == torch.float32 and item_emb.shape[1] == 128
+    assert rated_rowptr.dtype == torch.int64 and rated_col.dtype == torch.int32
+    item_emb = item_emb.contiguous()
+    n_users, n_main = rated_rowptr.shape[0] - 1, item_emb.shape[0] - prefix
+    L = _lib.lib()
+    groups = ((n_users + 127) // 128 + 3) // 4
+    words = int(L.crh_score_topk_screen_flags_bytes(n_users, n_main)) // 4
+    out = torch.empty((groups, words // groups), dtype=torch.int32, device=item_emb.device)
+    rc = L.crh_score_topk_screen_flags(_lib.ptr(cand_bitmap), _lib.ptr(item_emb), item_emb.shape[0], item_base, prefix,
+                                       1 if ordered else 0, _lib.ptr(rated_rowptr), _lib.ptr(rated_col), n_users, _lib.ptr(out),
+                                       _lib.current_stream())
+    _lib.check(rc, "crh_score_topk_screen_flags")
+    return out
+
+
 def score_topk_uncertified(device=None) -> int:
     """Users the last screened ``score_topk`` call on this device and stream could not certify (they took the exact fallback).
     Synchronises the stream; only meaningful right after a call that ``score_topk_route(...)["screened"]`` reports."""

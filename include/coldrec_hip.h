@@ -114,6 +114,19 @@ int crh_score_topk_screen_plan(int64_t n_users, int64_t n_items, size_t workspac
 int crh_score_topk_screen_ordered(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap);
 int crh_score_topk_screen_map(const uint32_t* bitmap, const float* item_emb, int64_t n_items, int64_t item_base, int64_t prefix,
                               int ordered, int32_t* map_out, int32_t* keys_out, int64_t* count, void* stream);
+/* crh_score_topk_screen_rated_tiles: 1 if a screened call of this shape gates the rated-list lookups of its fp16 pass by
+ * per-tile flags (CRH_SCORE_SCREEN_RATED_TILES, read per call: 1 default, 0 off; results are identical either way): the compaction
+ * is on, the call has rated lists and the workspace holds the flags and the inverse of the streamed map.  The flags: per workgroup
+ * of 512 user slots one 256-byte piece per 512 tiles of the stream, tile t of the workgroup's run in word t >> 3, nibble 4 (t & 7),
+ * bit w set iff a slot of the workgroup's wave w (128 slots) rated an item whose live row lies in the tile.
+ * crh_score_topk_screen_flags_bytes: bytes of the flags of n_users slots over a main range of n_main items.
+ * crh_score_topk_screen_flags (tests): only those flags, over the map of crh_score_topk_screen_map with the same arguments, into
+ * a device buffer of that many bytes.  Allocates its own buffers and synchronises `stream`. */
+int crh_score_topk_screen_rated_tiles(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap, int has_rated);
+size_t crh_score_topk_screen_flags_bytes(int64_t n_users, int64_t n_main);
+int crh_score_topk_screen_flags(const uint32_t* bitmap, const float* item_emb, int64_t n_items, int64_t item_base, int64_t prefix,
+                                int ordered, const int64_t* rated_rowptr, const int32_t* rated_col, int64_t n_users,
+                                uint32_t* flags_out, void* stream);
 int crh_score_topk_screened(int elem_bytes, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes,
                             int has_bitmap, int n_splits);
 int64_t crh_score_topk_uncertified(const void* workspace, void* stream);
