@@ -689,6 +689,19 @@ size_t packed_bytes(int64_t n_items, int d, int esz) { return (size_t)((n_items 
 // window counters of the XCD lockstep: 8 XCDs x (1 + one per 8-tile window, the smallest window allowed)
 size_t tbits_bytes(int64_t n_items) { return (((size_t)((n_items + 31) / 32) * sizeof(uint32_t)) + 255) & ~(size_t)255; }
 size_t sync_bytes(int64_t n_items) { return ((size_t)((n_items + 255) / 256 + 2) * 8 * sizeof(unsigned) + 255) & ~(size_t)255; }
+// A fused stage's workspace, front to back: the partial lists (offset 0), the fragment-ordered copy of the shard, the lockstep
+// counters, the tiles' candidate bits (DMA kernel).  A stage runs with any front part of it (plan_route).
+struct FusedLayout {
+    size_t packed, sync, tbits, need;
+};
+FusedLayout fused_layout(int64_t n_users, int64_t n_items, int d, int k, int esz) {
+    FusedLayout L;
+    L.packed = lists_bytes(n_users, k);
+    L.sync = L.packed + packed_bytes(n_items, d, esz);
+    L.tbits = L.sync + sync_bytes(n_items);
+    L.need = L.tbits + tbits_bytes(n_items);
+    return L;
+}
 
 int pack_items(int esz, const void* item_emb, int64_t n_items, int d, void* pk, hipStream_t st, const uint32_t* bitmap,
                int64_t item_base) {
@@ -838,7 +851,6 @@ struct RoutePlan {
     int upw;           // users per wave
     int occ;           // waves per SIMD of the per-wave kernel
     size_t dense_b;    // bytes of the dense block (0: not applicable)
-    size_t tb_off;     // workspace offset of the tiles' candidate bits (DMA kernel)
     int no_pack;
 };
 
@@ -850,8 +862,8 @@ RoutePlan plan_route(int esz, int64_t n_users, int64_t n_items, int d, int k, bo
     // wave.  fp32: d = 128 (64 users per wave; +1.5 % over the per-wave kernel and 1/8 of its L2 -> CU traffic).
     static const int no_pack = CRH_TUNE_ENV("CRH_SCORE_NO_PACK") ? atoi(CRH_TUNE_ENV("CRH_SCORE_NO_PACK")) : 0;
     const int wg_mode = getenv("CRH_SCORE_WG") ? atoi(getenv("CRH_SCORE_WG")) : 1;   // per call: tests force 2
-    const bool can_pack = !no_pack && has_workspace &&
-                          workspace_bytes >= lists_bytes(n_users, k) + packed_bytes(n_items, d, esz);
+    const FusedLayout fl = fused_layout(n_users, n_items, d, k, esz);
+    const bool can_pack = !no_pack && has_workspace && workspace_bytes >= fl.sync;
     // one 8-wave workgroup per CU when its lists fit the 160 KiB of LDS, else two 4-wave workgroups (large k);
     // measured at k=20 (fp16): 8 waves 50.6 % / 45.7 % of the fp16 peak at d=256 / 128, two 4-wave groups
     // 46.5 % / 47.4 % (CRH_SCORE_WG=4 forces them)
@@ -870,14 +882,13 @@ RoutePlan plan_route(int esz, int64_t n_users, int64_t n_items, int d, int k, bo
     // Same box, 131 072 x 10 M: fp16 d=256 0.577 vs 0.535 for the ring kernel, fp32 d=128 0.920 vs 0.910.
     // CRH_SCORE_DMA (read per call): 0 never, anything else (default) on
     const int dma_mode = getenv("CRH_SCORE_DMA") ? atoi(getenv("CRH_SCORE_DMA")) : 1;
-    const size_t tb_off = lists_bytes(n_users, k) + packed_bytes(n_items, d, esz) + sync_bytes(n_items);   // the tiles' candidate bits
     // (fp16 d=128 was measured on it too, round 6: 0.482 against 0.479 of 2.5 PF for the ring kernel at 10 M items, 0.305
     // against 0.347 at 1.25 M -- a 1 024-cycle tile is too short for one barrier + one threshold test each: not routed)
     const bool dma_rows = esz == 2 ? d == 256 : (d == 128 || d == 64);
     // the form of the fp32 DMA kernel: CRH_SCORE_DMA = 2 flag form, 3 barrier form, anything else by stream length
     const int dma_form = dma_mode == 2 || dma_mode == 3 ? dma_mode : (esz == 4 && d == 128 && n_items < FP32_DMA_FLAG_MAX_ITEMS ? 2 : 3);
     const bool dma_shape = dma_mode && dma_rows && score_dma_ring_slots(esz, d, k, dma_form) > 0 &&
-                           (!has_bitmap || workspace_bytes >= tb_off + tbits_bytes(n_items));
+                           (!has_bitmap || workspace_bytes >= fl.need);      // (room for the tiles' candidate bits)
     // fp32 d=64 (the reference's default width) has no register-staged ring kernel: a workgroup kernel only as the DMA form
     const bool wg_shape = esz == 2 ? (d == 64 || d == 128 || d == 256) : ((d == 128 && wg_waves == 8) || (d == 64 && dma_shape));
     // fp32: the lockstep of 8 waves makes every slow-path event a stall of the whole CU, so the workgroup kernel only
@@ -916,7 +927,6 @@ RoutePlan plan_route(int esz, int64_t n_users, int64_t n_items, int d, int k, bo
     r.upw = upw;
     r.occ = occ;
     r.dense_b = dense_b;
-    r.tb_off = tb_off;
     r.no_pack = no_pack;
     return r;
 }
@@ -978,6 +988,22 @@ int64_t seed_route(int esz, int64_t n_users, int64_t n_items, int d) {
     if (!(cuts || small_cat || f16_stream || f32_stream || seed_mode == 2) || dense_block_bytes(n_users, P) == 0) return 0;
     return P;
 }
+// ... and does THIS workspace hold it?  The seed lists sit in front of the workspace of either stage (the prefix's dense block and
+// packed copy, the main range's lists and packed copy).  P = seed_route's prefix and the bytes of the seed lists, or 0 and 0.
+// ONE answer for the dispatcher (score_topk_any), crh_score_topk_route and screen_route.
+struct SeedFit {
+    int64_t P;
+    size_t seed_b;
+};
+SeedFit seed_fit(int esz, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes) {
+    const int64_t P = seed_route(esz, n_users, n_items, d);
+    if (P <= 0) return {0, 0};
+    const size_t sb = seed_bytes(n_users, k);
+    const size_t stage1 = dense_block_bytes(n_users, P) + packed_bytes(P, d, esz);
+    const size_t stage2 = lists_bytes(n_users, k) + packed_bytes(n_items - P, d, esz);
+    if (workspace_bytes < sb + std::max(stage1, stage2)) return {0, 0};
+    return {P, sb};
+}
 
 // The screened route (score_screen.hip): fp16 screen of K' candidates per user by the LDS-DMA kernel, exact
 // rescoring, a per-user certificate, exact fallback for the users without one.  Its workspace, front to back.
@@ -993,12 +1019,13 @@ int screen_splits(int64_t n_users, int64_t n_main, bool seeded) {
 }
 struct ScreenLayout {
     size_t stats, ustat, fail, uh, seed, cand, packed, tbits, sync, idmap, scan, rowkeys, skeys, idmap2, sorttmp, inv, rtiles, scratch, need;
+    size_t slots;       // entries of a map of the main range (screen_map_slots)
 };
 // compact: with the live-row map of the main range (one id per item, rounded up to whole tiles plus the one the id DMA of the
 // last tile may touch: screen_map_slots) and the block sums of its scan; ordered (needs compact): behind them the norm keys of
 // the shard's rows, the sort keys along both maps, the sorted map and the sort's temporary storage; rated_tiles (needs compact): the
 // inverse of the streamed map (sized like it) and the call's rated-tile flags (screen_rated_tiles_bytes)
-ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool compact = false, bool ordered = false,
+ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, int cuts, bool compact = false, bool ordered = false,
                            bool rated_tiles = false) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     ScreenLayout L;
@@ -1012,7 +1039,7 @@ ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool com
     L.tbits = L.packed + packed_bytes(n_items, 128, 2);
     L.sync = L.tbits + tbits_bytes(n_items);
     L.idmap = L.sync + sync_bytes(n_items);
-    const size_t slots = (size_t)screen_map_slots(n_items - P);
+    const size_t slots = L.slots = (size_t)screen_map_slots(n_items - P);
     L.scan = L.idmap + (compact ? al(slots * sizeof(int32_t)) : 0);
     L.rowkeys = L.scan + (compact ? al(screen_scan_bytes(n_items - P)) : 0);
     ordered = ordered && compact;
@@ -1024,8 +1051,7 @@ ScreenLayout screen_layout(int64_t n_users, int64_t n_items, int64_t P, bool com
     L.rtiles = L.inv + (rated_tiles ? al(slots * sizeof(int32_t)) : 0);
     L.scratch = L.rtiles + (rated_tiles ? al(screen_rated_tiles_bytes(n_users, n_items - P)) : 0);
     // scratch: the stage-1 split lists, the prefix's score block (one 64-user group at the least) and the fallback's slice lists
-    const int S = screen_splits(n_users, n_items - P, P > 0);
-    const size_t lists = S > 1 ? (size_t)S * n_users * SCREEN_KP * 8 : 0;
+    const size_t lists = cuts > 1 ? (size_t)cuts * n_users * SCREEN_KP * 8 : 0;
     const size_t dense = P > 0 ? (size_t)64 * (size_t)P * sizeof(float) : 0;
     const size_t part = (size_t)n_users * screen_fallback_slices(n_items) * 20 * 8;
     L.need = L.scratch + std::max(lists, std::max(dense, part));
@@ -1040,53 +1066,67 @@ int screen_mode() {
     const char* e = getenv("CRH_SCORE_SCREEN");
     return e ? atoi(e) : 1;
 }
+// The screened route's plan for one call: the fp16 prefix ranked first, the item-range cuts of the fp16 pass over the rest, how that
+// pass streams, and the workspace layout that goes with all of it.  Decided HERE and nowhere else -- for the route itself
+// (score_topk_screened), the prepared item half (crh_score_screen_items_prepare) and the three queries.  None of the switches
+// changes the route: it is decided without them (screen_route), and each option is taken only when the workspace holds its layout.
 // CRH_SCORE_SCREEN_COMPACT (read per call): 1 (default) a call with a candidate bitmap streams only the unmasked rows through the
-// fp16 pass (when the workspace holds the map: the route itself is decided without it, so the switch never changes the route);
-// 0 keeps the masked rows in the stream as rows of zeros.
-bool screen_compact(int64_t n_users, int64_t n_items, size_t workspace_bytes, bool has_bitmap) {
-    const char* e = getenv("CRH_SCORE_SCREEN_COMPACT");
-    if (!has_bitmap || (e && atoi(e) == 0)) return false;
-    return workspace_bytes >= screen_layout(n_users, n_items, screen_prefix(n_items), true).need;
-}
+// fp16 pass, when the workspace holds the map; 0 keeps the masked rows in the stream as rows of zeros.
 // CRH_SCORE_SCREEN_ORDER (read per call): 1 (default) a compacted call whose fp16 pass is ONE cut streams the live rows of the main
 // range by descending norm (ScreenOrder), when the workspace holds the sorted map as well; 0 streams them by ascending id.  With
 // cuts the bounds of a cut come from the ascending map and a count only the device knows, so those calls stay ascending.
-bool screen_ordered(int64_t n_users, int64_t n_items, size_t workspace_bytes, bool has_bitmap) {
-    const char* e = getenv("CRH_SCORE_SCREEN_ORDER");
-    if ((e && atoi(e) == 0) || !screen_compact(n_users, n_items, workspace_bytes, has_bitmap)) return false;
-    const int64_t P = screen_prefix(n_items);
-    if (screen_splits(n_users, n_items - P, P > 0) != 1) return false;
-    return workspace_bytes >= screen_layout(n_users, n_items, P, true, true).need;
-}
 // CRH_SCORE_SCREEN_RATED_TILES (read per call): 1 (default) a compacted call with rated lists flags, per workgroup of 512 users and
 // tile of the stream, the waves that rated a row of the tile, and stage 1 consults a user's filter (and on a hit its list) only in
-// flagged tiles -- when the workspace holds the flags and the inverse map as well; 0, or a workspace without the room, passes no
-// flags and the call runs as before.  Never changes the route, the compaction or the order.
-bool screen_rated_tiles(int64_t n_users, int64_t n_items, size_t workspace_bytes, bool has_bitmap, bool has_rated) {
-    const char* e = getenv("CRH_SCORE_SCREEN_RATED_TILES");
-    if (!has_rated || (e && atoi(e) == 0) || !screen_compact(n_users, n_items, workspace_bytes, has_bitmap)) return false;
-    const bool ordered = screen_ordered(n_users, n_items, workspace_bytes, has_bitmap);
-    return workspace_bytes >= screen_layout(n_users, n_items, screen_prefix(n_items), true, ordered, true).need;
+// flagged tiles -- when the workspace holds the flags and the inverse map as well, behind whatever order was decided; 0, or a
+// workspace without the room, passes no flags and the call runs as before.  Never changes the compaction or the order.
+struct ScreenPlan {
+    int64_t P;
+    int cuts;
+    bool compact, ordered, rated_tiles;
+    ScreenLayout L;
+};
+ScreenPlan plan_screen(int64_t n_users, int64_t n_items, size_t workspace_bytes, bool has_bitmap, bool has_rated) {
+    auto on = [](const char* name) {
+        const char* e = getenv(name);
+        return !(e && atoi(e) == 0);
+    };
+    ScreenPlan p;
+    p.P = screen_prefix(n_items);
+    p.cuts = screen_splits(n_users, n_items - p.P, p.P > 0);
+    p.L = screen_layout(n_users, n_items, p.P, p.cuts);
+    auto fits = [&](bool compact, bool ordered, bool rated_tiles) {      // takes the layout when the workspace holds it
+        const ScreenLayout L = screen_layout(n_users, n_items, p.P, p.cuts, compact, ordered, rated_tiles);
+        if (workspace_bytes < L.need) return false;
+        p.L = L;
+        return true;
+    };
+    p.compact = has_bitmap && on("CRH_SCORE_SCREEN_COMPACT") && fits(true, false, false);
+    p.ordered = p.compact && on("CRH_SCORE_SCREEN_ORDER") && p.cuts == 1 && fits(true, true, false);
+    p.rated_tiles = p.compact && has_rated && on("CRH_SCORE_SCREEN_RATED_TILES") && fits(true, p.ordered, true);
+    return p;
+}
+// The ScreenOrder record of an ordered plan: the sort's temporaries where the layout puts them, the sorted map into `sorted_map`.
+ScreenOrder screen_order(const ScreenLayout& L, char* ws, int32_t* sorted_map) {
+    ScreenOrder ord;
+    ord.rowkeys = reinterpret_cast<uint16_t*>(ws + L.rowkeys);
+    ord.skeys_in = reinterpret_cast<uint16_t*>(ws + L.skeys);
+    ord.skeys_out = reinterpret_cast<uint16_t*>(ws + L.skeys + (L.idmap2 - L.skeys) / 2);
+    ord.idmap = sorted_map;
+    ord.sort_tmp = ws + L.sorttmp;
+    ord.sort_tmp_bytes = screen_sort_bytes((int64_t)L.slots);
+    return ord;
 }
 bool screen_route(int esz, int64_t n_users, int64_t n_items, int d, int k, size_t workspace_bytes, bool has_bitmap, int n_splits) {
     const int mode = screen_mode();
     if (mode <= 0 || mode > 3 || esz != 4 || d != 128 || k < 1 || k > 20 || n_splits != 0 || n_users <= 0 || n_items <= 0 ||
         workspace_bytes == 0)
         return false;
-    if (workspace_bytes < screen_layout(n_users, n_items, screen_prefix(n_items)).need) return false;
+    if (workspace_bytes < plan_screen(n_users, n_items, workspace_bytes, false, false).L.need) return false;   // (no option taken)
     if (mode >= 2) return true;
     if (n_items < FP32_DMA_FLAG_MAX_ITEMS) return false;
     // today's route of the shape (crh_score_topk_route's evaluation): the DMA kernel in its barrier form
-    int64_t P = seed_route(esz, n_users, n_items, d);
-    size_t ws = workspace_bytes;
-    if (P > 0) {
-        const size_t sb = seed_bytes(n_users, k);
-        const size_t stage1 = dense_block_bytes(n_users, P) + packed_bytes(P, d, esz);
-        const size_t stage2 = lists_bytes(n_users, k) + packed_bytes(n_items - P, d, esz);
-        if (workspace_bytes >= sb + std::max(stage1, stage2)) ws = workspace_bytes - sb;
-        else P = 0;
-    }
-    const RoutePlan r = plan_route(esz, n_users, n_items - P, d, k, true, ws, has_bitmap, 0, P > 0);
+    const SeedFit sf = seed_fit(esz, n_users, n_items, d, k, workspace_bytes);
+    const RoutePlan r = plan_route(esz, n_users, n_items - sf.P, d, k, true, workspace_bytes - sf.seed_b, has_bitmap, 0, sf.P > 0);
     return !r.dense && r.use_dma && r.dma_mode == 3;
 }
 
@@ -1154,30 +1194,27 @@ int score_topk_any(int esz, const void* user_emb, const int32_t* users, int64_t 
         return score_topk_screened(reinterpret_cast<const float*>(user_emb), users, n_users, reinterpret_cast<const float*>(item_emb),
                                    n_items, rated_rowptr, rated_col, cand_bitmap, k, item_base, out_score, out_idx, workspace,
                                    workspace_bytes, stream, ev_kernel_start, ev_kernel_stop, who, prepared);
-    // the seeded route's own predicate and prefix (shared with the workspace query: seed_route)
-    const int64_t P = n_splits == 0 ? seed_route(esz, n_users, n_items, d) : 0;
-    if (P > 0 && user_emb && item_emb && out_score && out_idx && n_users > 0 && k >= 1 && k <= CRH_MAX_K && workspace) {
-        const size_t sb = seed_bytes(n_users, k);
-        const size_t stage1 = dense_block_bytes(n_users, P) + packed_bytes(P, d, esz);
-        const size_t stage2 = lists_bytes(n_users, k) + packed_bytes(n_items - P, d, esz);
-        if (workspace_bytes >= sb + std::max(stage1, stage2)) {
-            float* seed_s = reinterpret_cast<float*>(workspace);
-            int32_t* seed_i = reinterpret_cast<int32_t*>(seed_s + (size_t)n_users * k);
-            void* ws2 = reinterpret_cast<char*>(workspace) + sb;
-            hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-            if (ev_kernel_start) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_start), st));
-            int rc = score_topk_impl(esz, user_emb, users, n_users, item_emb, P, d, rated_rowptr, rated_col, cand_bitmap, k,
-                                     item_base, seed_s, seed_i, ws2, workspace_bytes - sb, stream, 0, nullptr, nullptr, who,
-                                     nullptr, nullptr);
-            if (rc != CRH_OK) return rc;
-            rc = score_topk_impl(esz, user_emb, users, n_users,
-                                 reinterpret_cast<const char*>(item_emb) + (size_t)P * d * esz, n_items - P, d, rated_rowptr,
-                                 rated_col, cand_bitmap, k, item_base + P, out_score, out_idx, ws2, workspace_bytes - sb, stream,
-                                 0, nullptr, nullptr, who, seed_s, seed_i);
-            if (rc != CRH_OK) return rc;
-            if (ev_kernel_stop) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_stop), st));
-            return CRH_OK;
-        }
+    // the seeded route's own predicate and prefix (shared with the workspace query: seed_route), in a workspace that holds it
+    const bool may_seed = n_splits == 0 && user_emb && item_emb && out_score && out_idx && n_users > 0 && k >= 1 && k <= CRH_MAX_K && workspace;
+    const SeedFit sf = may_seed ? seed_fit(esz, n_users, n_items, d, k, workspace_bytes) : SeedFit{0, 0};
+    if (sf.P > 0) {
+        const int64_t P = sf.P;
+        float* seed_s = reinterpret_cast<float*>(workspace);
+        int32_t* seed_i = reinterpret_cast<int32_t*>(seed_s + (size_t)n_users * k);
+        void* ws2 = reinterpret_cast<char*>(workspace) + sf.seed_b;
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        if (ev_kernel_start) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_start), st));
+        int rc = score_topk_impl(esz, user_emb, users, n_users, item_emb, P, d, rated_rowptr, rated_col, cand_bitmap, k,
+                                 item_base, seed_s, seed_i, ws2, workspace_bytes - sf.seed_b, stream, 0, nullptr, nullptr, who,
+                                 nullptr, nullptr);
+        if (rc != CRH_OK) return rc;
+        rc = score_topk_impl(esz, user_emb, users, n_users,
+                             reinterpret_cast<const char*>(item_emb) + (size_t)P * d * esz, n_items - P, d, rated_rowptr,
+                             rated_col, cand_bitmap, k, item_base + P, out_score, out_idx, ws2, workspace_bytes - sf.seed_b, stream,
+                             0, nullptr, nullptr, who, seed_s, seed_i);
+        if (rc != CRH_OK) return rc;
+        if (ev_kernel_stop) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_stop), st));
+        return CRH_OK;
     }
     return score_topk_impl(esz, user_emb, users, n_users, item_emb, n_items, d, rated_rowptr, rated_col, cand_bitmap, k,
                            item_base, out_score, out_idx, workspace, workspace_bytes, stream, n_splits, ev_kernel_start,
@@ -1290,10 +1327,7 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
 
     const RoutePlan rp = plan_route(esz, n_users, n_items, d, k, workspace != nullptr, workspace_bytes, cand_bitmap != nullptr,
                                     n_splits, seed_score != nullptr);
-    const bool use_wg = rp.use_wg, use_dma = rp.use_dma, can_pack = rp.can_pack;
-    const int wg_waves_l = rp.wg_waves_l, upw = rp.upw, occ = rp.occ, no_pack = rp.no_pack;
-    const size_t tb_off = rp.tb_off, dense_b = rp.dense_b;
-    ScoreArgs a;
+    ScoreArgs a = {};       // (margin, screen_k, rated_tiles stay off: the screen's rules, score_topk_screened)
     a.user_emb = user_emb;
     a.users = users;
     a.n_users = n_users;
@@ -1304,37 +1338,26 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
     a.bitmap = cand_bitmap;
     a.k = k;
     a.item_base = item_base;
-    a.n_ugroups = (n_users + upw - 1) / upw;
+    a.n_ugroups = (n_users + rp.upw - 1) / rp.upw;
     static const int ablate = CRH_PROFILE_ENV("CRH_SCORE_ABLATE");
     a.ablate = ablate;
-    a.dense = nullptr;
-    a.dense_stride = 0;
-    a.user_base = 0;
     a.seed_score = seed_score;
     a.seed_idx = seed_idx;
-    a.margin = nullptr;         // (the screen's rule: score_topk_screened)
-    a.screen_k = 0;
-    a.rated_tiles = nullptr;
     const int64_t T = (n_items + 31) / 32;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
     if (rp.dense) {   // small catalogues: score block + wave-per-user ranking (see plan_route)
         const int64_t stride = T * 32;
         const int upw_pw = users_per_wave(esz, d);
-        int64_t chunk = (int64_t)(dense_b / ((size_t)stride * sizeof(float)));
+        int64_t chunk = (int64_t)(rp.dense_b / ((size_t)stride * sizeof(float)));
         if (chunk > n_users) chunk = n_users;
-        a.packed = nullptr;
-        if (!no_pack && workspace_bytes >= dense_b + packed_bytes(n_items, d, esz)) {
-            void* pk = reinterpret_cast<char*>(workspace) + dense_b;
+        if (!rp.no_pack && workspace_bytes >= rp.dense_b + packed_bytes(n_items, d, esz)) {
+            void* pk = reinterpret_cast<char*>(workspace) + rp.dense_b;
             const int prc = pack_items(esz, item_emb, n_items, d, pk, st, cand_bitmap, item_base);
             if (prc != CRH_OK) return prc;
             a.packed = pk;
         }
         a.n_splits = 1;
-        a.xcd_sync = nullptr;
-        a.sync_window = 0;
-        a.sync_stride = 0;
-        a.wave_clock = nullptr;
 #ifdef CRH_PROFILE
         static const int timing_d = CRH_PROFILE_ENV("CRH_SCORE_TIMING");
 #endif
@@ -1352,7 +1375,7 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
             a.n_ugroups = (cu + upw_pw - 1) / upw_pw;
             // item-range splits cost nothing here (every wave writes its own columns of the block): as many as
             // fill the wave slots of the chip once
-            a.n_splits = (int)std::max<int64_t>(1, std::min<int64_t>(T, (1024 * occ) / a.n_ugroups));
+            a.n_splits = (int)std::max<int64_t>(1, std::min<int64_t>(T, (1024 * rp.occ) / a.n_ugroups));
             a.rated_rowptr = rated_rowptr ? rated_rowptr + u0 : nullptr;
 #ifdef CRH_PROFILE
             if (timing_d) {
@@ -1360,7 +1383,7 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
                 CRH_HIP(hipMemsetAsync(a.wave_clock, 0, (size_t)a.n_ugroups * a.n_splits * 48, st));
             }
 #endif
-            const int rc1 = launch_score_per_wave(esz, d, occ, a, st);
+            const int rc1 = launch_score_per_wave(esz, d, rp.occ, a, st);
             if (rc1 != CRH_OK) return rc1;
 #ifdef CRH_PROFILE
             if (timing_d) {
@@ -1392,9 +1415,9 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
     }
     // fragment-ordered copy of the shard (one HBM pass, ~0.1 % of a 128 K-user block at 10 M items) when the
     // workspace has room for it behind the partial lists
-    a.packed = nullptr;
-    if (can_pack) {
-        void* pk = reinterpret_cast<char*>(workspace) + lists_bytes(n_users, k);
+    const FusedLayout fl = fused_layout(n_users, n_items, d, k, esz);
+    if (rp.can_pack) {
+        void* pk = reinterpret_cast<char*>(workspace) + fl.packed;
         const int prc = pack_items(esz, item_emb, n_items, d, pk, st, cand_bitmap, item_base);
         if (prc != CRH_OK) return prc;
         a.packed = pk;
@@ -1406,67 +1429,60 @@ int score_topk_impl(int esz, const void* user_emb, const int32_t* users, int64_t
     // from THIS value -- an odd window made kernel and host disagree about the number of windows)
     static const int sync_win_raw = CRH_TUNE_ENV("CRH_SCORE_SYNC_WINDOW") ? atoi(CRH_TUNE_ENV("CRH_SCORE_SYNC_WINDOW")) : 128;
     static const int sync_win = sync_win_raw <= 0 ? 0 : std::max(2, sync_win_raw & ~1);
-    a.xcd_sync = nullptr;
     a.sync_window = sync_win;
-    a.sync_stride = 0;
-    const int64_t n_wg_launch = (a.n_ugroups + wg_waves_l - 1) / wg_waves_l;
+    const int64_t n_wg_launch = (a.n_ugroups + rp.wg_waves_l - 1) / rp.wg_waves_l;
     // Item-range cuts under SEEDED lists take part too (per-wave kernel): every cut walks its own range, window by window
     // from its own start, and the cuts' window counts differ by at most one, so no wave ever waits for a window another
     // wave will not report; the L2 of an XCD then holds two windows of each cut instead of the cuts' drifting streams.
-    const bool cuts_ok = a.n_splits == 1 || (seed_score && !use_wg && T / a.n_splits >= 4 * sync_win);
-    const bool sync_pw = !use_wg && occ == 2 && a.n_ugroups * a.n_splits <= 2048 && a.n_ugroups * a.n_splits > 256;
-    const bool sync_wg = use_wg && n_wg_launch <= rp.wg_slots_l && n_wg_launch > 8;   // one resident round
+    const bool cuts_ok = a.n_splits == 1 || (seed_score && !rp.use_wg && T / a.n_splits >= 4 * sync_win);
+    const bool sync_pw = !rp.use_wg && rp.occ == 2 && a.n_ugroups * a.n_splits <= 2048 && a.n_ugroups * a.n_splits > 256;
+    const bool sync_wg = rp.use_wg && n_wg_launch <= rp.wg_slots_l && n_wg_launch > 8;   // one resident round
     if (sync_win > 0 && (sync_pw || sync_wg) && cuts_ok && a.packed) {
         const int64_t n_win = (T / a.n_splits + 1 + sync_win - 1) / sync_win + 1;
-        const size_t need = lists_bytes(n_users, k) + packed_bytes(n_items, d, esz) + sync_bytes(n_items);
-        if (workspace_bytes >= need && (size_t)(n_win + 1) * 8 * sizeof(unsigned) <= sync_bytes(n_items)) {
+        if (workspace_bytes >= fl.tbits && (size_t)(n_win + 1) * 8 * sizeof(unsigned) <= fl.tbits - fl.sync) {
             a.sync_stride = n_win + 1;
-            a.xcd_sync = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + lists_bytes(n_users, k) +
-                                                     packed_bytes(n_items, d, esz));
+            a.xcd_sync = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + fl.sync);
             CRH_HIP(hipMemsetAsync(a.xcd_sync, 0, (size_t)a.sync_stride * 8 * sizeof(unsigned), st));
         }
     }
     a.tile_bits = reinterpret_cast<const uint32_t*>(a.packed);      // readable filler when there is no candidate bitmap
-    a.idmap = nullptr;
-    a.n_live = nullptr;
-    if (use_dma && cand_bitmap) {
-        uint32_t* tb = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + tb_off);
+    if (rp.use_dma && cand_bitmap) {
+        uint32_t* tb = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + fl.tbits);
         hipLaunchKernelGGL(tile_bits_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, cand_bitmap, item_base, n_items, T, tb);
         CRH_HIP(hipGetLastError());
         a.tile_bits = tb;
     }
-    a.wave_clock = nullptr;
 #ifdef CRH_PROFILE
     static const int timing = CRH_PROFILE_ENV("CRH_SCORE_TIMING");
     const int64_t n_waves = a.n_ugroups * a.n_splits;
-    if (timing && !use_wg) CRH_HIP(hipMalloc(&a.wave_clock, (size_t)n_waves * 48));   // profile build only: [wave][start,end], [wave][loop start,end], [wave][event ticks,events]
-    if (timing && use_dma) {
+    if (timing && !rp.use_wg) CRH_HIP(hipMalloc(&a.wave_clock, (size_t)n_waves * 48));   // profile build only: [wave][start,end], [wave][loop start,end], [wave][event ticks,events]
+    if (timing && rp.use_dma) {
         rc = dma_timing_begin(a, st);
         if (rc != CRH_OK) return rc;
     }
 #endif
     if (ev_kernel_start) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_start), st));
-    if (use_dma) {
+    if (rp.use_dma) {
         rc = launch_score_dma(esz, d, rp.dma_mode, a, st);
-    } else if (esz == 4 && use_wg) {
+    } else if (esz == 4 && rp.use_wg) {
         rc = launch_score_wg<float, 128, 2, 8>(a, st);
-    } else if (use_wg) {
+    } else if (rp.use_wg) {
         switch (d) {
-            case 64: rc = wg_waves_l == 4 ? launch_score_wg<_Float16, 64, 2, 4>(a, st) : launch_score_wg<_Float16, 64, 2, 8>(a, st); break;
-            case 128: rc = wg_waves_l == 4 ? launch_score_wg<_Float16, 128, 2, 4>(a, st) : launch_score_wg<_Float16, 128, 2, 8>(a, st); break;
-            default: rc = wg_waves_l == 4 ? launch_score_wg<_Float16, 256, 2, 4>(a, st) : launch_score_wg<_Float16, 256, 2, 8>(a, st); break;
+            case 64: rc = rp.wg_waves_l == 4 ? launch_score_wg<_Float16, 64, 2, 4>(a, st) : launch_score_wg<_Float16, 64, 2, 8>(a, st); break;
+            case 128: rc = rp.wg_waves_l == 4 ? launch_score_wg<_Float16, 128, 2, 4>(a, st) : launch_score_wg<_Float16, 128, 2, 8>(a, st); break;
+            default: rc = rp.wg_waves_l == 4 ? launch_score_wg<_Float16, 256, 2, 4>(a, st) : launch_score_wg<_Float16, 256, 2, 8>(a, st); break;
         }
     } else {
-        rc = launch_score_per_wave(esz, d, occ, a, st);
+        rc = launch_score_per_wave(esz, d, rp.occ, a, st);
     }
     if (rc != CRH_OK) return rc;
     if (ev_kernel_stop) CRH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_kernel_stop), st));
 #ifdef CRH_PROFILE
-    if (timing && use_dma) {
+    if (timing && rp.use_dma) {
         rc = dma_timing_report(a, esz, d, st);
         if (rc != CRH_OK) return rc;
     }
-    if (timing && !use_wg) {
+    if (timing && !rp.use_wg) {
         const int trc = print_wave_timing(a.wave_clock, n_waves, timing, st);
         if (trc != CRH_OK) return trc;
     }
@@ -1501,25 +1517,15 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     CRH_CHECK_ARG(rated_rowptr != nullptr || rated_col == nullptr, "%s: rated_col given without rated_rowptr", who);
     CRH_CHECK_ARG(item_base >= 0 && item_base + n_items < (int64_t)CRH_PAD_IDX, "%s: item ids exceed int32", who);
     constexpr int KP = SCREEN_KP, D = 128;
-    const int64_t P = screen_prefix(n_items);
-    const bool compact = screen_compact(n_users, n_items, workspace_bytes, cand_bitmap != nullptr);
-    const bool ordered = screen_ordered(n_users, n_items, workspace_bytes, cand_bitmap != nullptr);
-    const bool rated_tiles = screen_rated_tiles(n_users, n_items, workspace_bytes, cand_bitmap != nullptr, rated_rowptr != nullptr);
-    const ScreenLayout L = screen_layout(n_users, n_items, P, compact, ordered, rated_tiles);
+    const ScreenPlan plan = plan_screen(n_users, n_items, workspace_bytes, cand_bitmap != nullptr, rated_rowptr != nullptr);
+    const ScreenLayout& L = plan.L;
+    const int64_t P = plan.P;
+    const bool compact = plan.compact, ordered = plan.ordered;
     CRH_CHECK_ARG(workspace_bytes >= L.need, "%s: workspace %zu < %zu bytes (screened route)", who, workspace_bytes, L.need);
-    int32_t* idmap = compact ? reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + L.idmap) : nullptr;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(workspace);
-    ScreenOrder ord;
-    if (ordered) {
-        const size_t slots = (size_t)screen_map_slots(n_items - P);
-        ord.rowkeys = reinterpret_cast<uint16_t*>(ws + L.rowkeys);
-        ord.skeys_in = reinterpret_cast<uint16_t*>(ws + L.skeys);
-        ord.skeys_out = reinterpret_cast<uint16_t*>(ws + L.skeys + (L.idmap2 - L.skeys) / 2);
-        ord.idmap = reinterpret_cast<int32_t*>(ws + L.idmap2);
-        ord.sort_tmp = ws + L.sorttmp;
-        ord.sort_tmp_bytes = screen_sort_bytes((int64_t)slots);
-    }
+    int32_t* idmap = compact ? reinterpret_cast<int32_t*>(ws + L.idmap) : nullptr;
+    const ScreenOrder ord = screen_order(L, ws, reinterpret_cast<int32_t*>(ws + L.idmap2));       // (used when ordered)
     // a prepared item half built for this table, bitmap and plan: stage 0 runs its user half only, stage 1 reads the prepared copy
     const bool reuse = screen_items_match(prepared, item_emb, n_items, item_base, cand_bitmap, P, compact, ordered, st);
     const ScreenItemsLayout PL = screen_items_layout(n_items, cand_bitmap != nullptr);
@@ -1577,31 +1583,17 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
 
     // ---- stage 1: approximate top-K' on the fp16 copies -- the prefix ranked into seed lists (score block + crh_mask_topk_f32, as
     // the seeded route does), then the LDS-DMA kernel over the rest
-    ScoreArgs a;
+    // What stays zero: users (uh is in `users` order) and item_emb (both kernels read the packed copy only); idmap and n_live until
+    // the DMA launch (the prefix is not compacted); margin and screen_k until then (the prefix is ranked whole: the rule is stage
+    // 1's DMA launch's)
+    ScoreArgs a = {};
     a.user_emb = uh;
-    a.users = nullptr;
     a.n_users = n_users;
-    a.item_emb = nullptr;       // both kernels read the packed copy only
     a.rated_rowptr = rated_rowptr;
     a.rated_col = rated_col;
     a.bitmap = cand_bitmap;
     a.k = KP;
-    a.ablate = 0;
-    a.wave_clock = nullptr;
-    a.xcd_sync = nullptr;
-    a.sync_window = 0;
-    a.sync_stride = 0;
-    a.dense = nullptr;
-    a.dense_stride = 0;
-    a.user_base = 0;
-    a.seed_score = nullptr;
-    a.seed_idx = nullptr;
     a.tile_bits = reinterpret_cast<const uint32_t*>(pk);
-    a.idmap = nullptr;          // (the prefix is not compacted)
-    a.n_live = nullptr;
-    a.margin = nullptr;         // (the prefix is ranked whole: the rule is stage 1's DMA launch's)
-    a.screen_k = 0;
-    a.rated_tiles = nullptr;
     if (P > 0) {
         const int64_t stride = P;                       // P is a multiple of 32
         const int upw_pw = users_per_wave(2, D);
@@ -1639,7 +1631,7 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     a.item_base = item_base + P;
     a.n_ugroups = (n_users + 127) / 128;
     const int64_t n_wg = (a.n_ugroups + 3) / 4;
-    a.n_splits = screen_splits(n_users, n_main, P > 0);
+    a.n_splits = plan.cuts;
     a.margin = reinterpret_cast<const float*>(s.stats + SCREEN_STAT_MARGIN);
     a.screen_k = k;
     if (a.n_splits == 1) {
@@ -1664,7 +1656,7 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     if (compact) {               // the stream holds the unmasked rows only: no tile bits, the rows' ids instead
         a.idmap = stream_map;       // (ordered: one cut, the only launch that may stream another order)
         a.n_live = s.stats + SCREEN_STAT_LIVE;
-        if (rated_tiles) {          // the call's rated-tile flags: they depend on the users, so they are built per call
+        if (plan.rated_tiles) {     // the call's rated-tile flags: they depend on the users, so they are built per call
             // (and with them the inverse of the streamed map, prepared or not: a prepared state has no room for a second map --
             // its size is pinned to the copy and one id per row -- and the inverse costs a call 0.1 ms at 10 M rows)
             int32_t* inv = reinterpret_cast<int32_t*>(ws + L.inv);
@@ -1714,12 +1706,12 @@ namespace {
 // seed lists in front plus the prefix's own dense block
 size_t full_workspace_bytes(int64_t n_users, int64_t n_items, int d, int k, int esz, bool dim_ok) {
     if (n_users <= 0 || k <= 0) return 0;
-    const size_t tail = dim_ok && n_items > 0 ? packed_bytes(n_items, d, esz) + sync_bytes(n_items) + tbits_bytes(n_items) : 0;
-    size_t need = std::max(lists_bytes(n_users, k), dense_block_bytes(n_users, n_items)) + tail;
+    const size_t lists = lists_bytes(n_users, k);
+    const size_t fused = dim_ok && n_items > 0 ? fused_layout(n_users, n_items, d, k, esz).need : lists;
+    // (the dense stage: its block, then what the fused stage keeps behind its lists)
+    size_t need = std::max(fused, dense_block_bytes(n_users, n_items) + (fused - lists));
     const int64_t P = dim_ok ? seed_route(esz, n_users, n_items, d) : 0;      // only shapes that DO seed pay for the prefix
-    if (P > 0)
-        need = std::max(need, std::max(dense_block_bytes(n_users, P) + packed_bytes(P, d, esz), lists_bytes(n_users, k) + tail)) +
-               seed_bytes(n_users, k);
+    if (P > 0) need = std::max(need, dense_block_bytes(n_users, P) + packed_bytes(P, d, esz)) + seed_bytes(n_users, k);
     return need;
 }
 }  // namespace
@@ -1748,17 +1740,10 @@ extern "C" int crh_score_topk_route(int elem_bytes, int64_t n_users, int64_t n_i
                   "crh_score_topk_route: d=%d unsupported", d);
     CRH_CHECK_ARG(n_splits >= 0 && n_splits <= 64, "crh_score_topk_route: n_splits=%d outside 0..64", n_splits);
     const bool has_ws = workspace_bytes > 0;
-    int64_t P = n_splits == 0 && has_ws ? seed_route(elem_bytes, n_users, n_items, d) : 0;
-    size_t ws = workspace_bytes;
-    if (P > 0) {    // the seeded route needs room for the seeds in front of either stage (score_topk_any)
-        const size_t sb = seed_bytes(n_users, k);
-        const size_t stage1 = dense_block_bytes(n_users, P) + packed_bytes(P, d, elem_bytes);
-        const size_t stage2 = lists_bytes(n_users, k) + packed_bytes(n_items - P, d, elem_bytes);
-        if (workspace_bytes >= sb + std::max(stage1, stage2)) ws = workspace_bytes - sb;
-        else P = 0;
-    }
-    const int64_t n_main = n_items - P;
-    const RoutePlan r = plan_route(elem_bytes, n_users, n_main, d, k, has_ws, ws, has_bitmap != 0, n_splits, P > 0);
+    // the seeded route needs room for the seeds in front of either stage (seed_fit, as score_topk_any)
+    const SeedFit sf = n_splits == 0 && has_ws ? seed_fit(elem_bytes, n_users, n_items, d, k, workspace_bytes) : SeedFit{0, 0};
+    const int64_t P = sf.P, n_main = n_items - P;
+    const RoutePlan r = plan_route(elem_bytes, n_users, n_main, d, k, has_ws, workspace_bytes - sf.seed_b, has_bitmap != 0, n_splits, P > 0);
     int route = r.dense ? CRH_ROUTE_DENSE : (r.use_dma ? CRH_ROUTE_FUSED_DMA : (r.use_wg ? CRH_ROUTE_FUSED_WG : CRH_ROUTE_FUSED_WAVE));
     if (P > 0) route |= CRH_ROUTE_SEEDED;
     if (r.use_dma && !r.dense && r.dma_mode == 2) route |= CRH_ROUTE_DMA_FLAGS;
@@ -1779,9 +1764,9 @@ extern "C" int crh_score_topk_screened(int elem_bytes, int64_t n_users, int64_t 
 extern "C" int crh_score_topk_screen_plan(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap, int* cuts,
                                           int* compact) {
     CRH_CHECK_ARG(n_users > 0 && n_items > 0, "crh_score_topk_screen_plan: empty block");
-    const int64_t P = screen_prefix(n_items);
-    if (cuts) *cuts = screen_splits(n_users, n_items - P, P > 0);
-    if (compact) *compact = screen_compact(n_users, n_items, workspace_bytes, has_bitmap != 0) ? 1 : 0;
+    const ScreenPlan plan = plan_screen(n_users, n_items, workspace_bytes, has_bitmap != 0, false);
+    if (cuts) *cuts = plan.cuts;
+    if (compact) *compact = plan.compact ? 1 : 0;
     return CRH_OK;
 }
 
@@ -1789,14 +1774,14 @@ extern "C" int crh_score_topk_screen_plan(int64_t n_users, int64_t n_items, size
 // call: 1 default)?  Needs the compaction, a fp16 pass of one cut and a workspace that holds the sorted map.
 extern "C" int crh_score_topk_screen_ordered(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap) {
     if (n_users <= 0 || n_items <= 0) return 0;
-    return screen_ordered(n_users, n_items, workspace_bytes, has_bitmap != 0) ? 1 : 0;
+    return plan_screen(n_users, n_items, workspace_bytes, has_bitmap != 0, false).ordered ? 1 : 0;
 }
 
 // Would a screened call of this shape gate stage 1's rated lookups by per-tile flags (CRH_SCORE_SCREEN_RATED_TILES, read per call:
 // 1 default)?  Needs the compaction, rated lists and a workspace that holds the flags and the inverse map.
 extern "C" int crh_score_topk_screen_rated_tiles(int64_t n_users, int64_t n_items, size_t workspace_bytes, int has_bitmap, int has_rated) {
     if (n_users <= 0 || n_items <= 0) return 0;
-    return screen_rated_tiles(n_users, n_items, workspace_bytes, has_bitmap != 0, has_rated != 0) ? 1 : 0;
+    return plan_screen(n_users, n_items, workspace_bytes, has_bitmap != 0, has_rated != 0).rated_tiles ? 1 : 0;
 }
 
 // Bytes of the rated-tile flags of a call of n_users slots over a main range of n_main items: per workgroup of 512 slots one 256-byte
@@ -1864,25 +1849,17 @@ extern "C" int crh_score_screen_items_prepare(const float* item_emb, int64_t n_i
     const bool has_bitmap = cand_bitmap != nullptr;
     const ScreenItemsLayout PL = screen_items_layout(n_items, has_bitmap);
     CRH_CHECK_ARG(items_bytes >= PL.need, "%s: buffer %zu < %zu bytes", who, items_bytes, PL.need);
-    const int64_t P = screen_prefix(n_items);
-    const bool compact = screen_compact(n_users, n_items, workspace_bytes, has_bitmap);
-    const bool ordered = screen_ordered(n_users, n_items, workspace_bytes, has_bitmap);
-    const ScreenLayout L = screen_layout(n_users, n_items, P, compact, ordered);
+    const ScreenPlan plan = plan_screen(n_users, n_items, workspace_bytes, has_bitmap, false);    // (the flags are the calls' own)
+    const ScreenLayout& L = plan.L;
+    const int64_t P = plan.P;
+    const bool compact = plan.compact, ordered = plan.ordered;
     CRH_CHECK_ARG(workspace_bytes >= L.need, "%s: workspace %zu < %zu bytes (screened route)", who, workspace_bytes, L.need);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = reinterpret_cast<char*>(workspace);
     char* buf = reinterpret_cast<char*>(items_buf);
     int32_t* own_map = reinterpret_cast<int32_t*>(buf + PL.map);
-    ScreenOrder ord;
-    if (ordered) {       // the ascending map is a temporary of the sort; the state keeps the sorted one
-        const size_t slots = (size_t)screen_map_slots(n_items - P);
-        ord.rowkeys = reinterpret_cast<uint16_t*>(ws + L.rowkeys);
-        ord.skeys_in = reinterpret_cast<uint16_t*>(ws + L.skeys);
-        ord.skeys_out = reinterpret_cast<uint16_t*>(ws + L.skeys + (L.idmap2 - L.skeys) / 2);
-        ord.idmap = own_map;
-        ord.sort_tmp = ws + L.sorttmp;
-        ord.sort_tmp_bytes = screen_sort_bytes((int64_t)slots);
-    }
+    // ordered: the ascending map is a temporary of the sort; the state keeps the sorted one
+    const ScreenOrder ord = screen_order(L, ws, own_map);
     int32_t* idmap = compact ? (ordered ? reinterpret_cast<int32_t*>(ws + L.idmap) : own_map) : nullptr;
     ScreenArgs s = {};
     s.item_emb = item_emb;

@@ -78,6 +78,14 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return buf
 
 
+def _score_ws_bytes(n_users: int, n_items: int, d: int, k: int, half: bool = False, pack: bool = True) -> int:
+    """Bytes of the workspace ``score_topk`` passes for a block of this shape (``d`` a width the library supports)."""
+    L = _lib.lib()
+    if not pack:
+        return L.crh_score_topk_min_workspace_bytes(n_users, k)
+    return (L.crh_score_topk_f16_workspace_bytes if half else L.crh_score_topk_workspace_bytes)(n_users, n_items, d, k)
+
+
 def score_topk(user_emb: torch.Tensor, users: Optional[torch.Tensor], item_emb: torch.Tensor, k: int,
                rated_rowptr: Optional[torch.Tensor] = None, rated_col: Optional[torch.Tensor] = None,
                cand_bitmap: Optional[torch.Tensor] = None, item_base: int = 0, n_splits: int = 0,
@@ -113,8 +121,7 @@ def score_topk(user_emb: torch.Tensor, users: Optional[torch.Tensor], item_emb: 
         out = (torch.empty((n_users, k), dtype=torch.float32, device=dev),
                torch.empty((n_users, k), dtype=torch.int32, device=dev))
     L = _lib.lib()
-    full = L.crh_score_topk_f16_workspace_bytes if half else L.crh_score_topk_workspace_bytes
-    ws_bytes = full(n_users, n_items, d, k) if pack else L.crh_score_topk_min_workspace_bytes(n_users, k)
+    ws_bytes = _score_ws_bytes(n_users, n_items, d, k, half, pack)
     ws = _workspace(ws_bytes, dev)
     args = (_lib.ptr(user_emb), _lib.ptr(users), n_users, _lib.ptr(item_emb), n_items, d,
             _lib.ptr(rated_rowptr), _lib.ptr(rated_col), _lib.ptr(cand_bitmap), k,
@@ -187,7 +194,7 @@ class PreparedItems:
         """Build the native state now, for ``score_topk`` calls of ``n_users`` users and this ``k`` on the current stream."""
         if torch.cuda.current_stream(self.item_emb.device).cuda_stream != self.stream:
             raise RuntimeError("PreparedItems.build: not the stream the state was made on")
-        ws_bytes = int(_lib.lib().crh_score_topk_workspace_bytes(int(n_users), self.item_emb.shape[0], 128, int(k)))
+        ws_bytes = _score_ws_bytes(int(n_users), self.item_emb.shape[0], 128, int(k))
         self.handle_for(n_users, _workspace(ws_bytes, self.item_emb.device), ws_bytes)
         return self
 
@@ -223,12 +230,10 @@ def score_topk_route(n_users: int, n_items: int, d: int, k: int, half: bool = Fa
     would pass.  ``{"route", "seeded", "dma_form", "prefix_items", "n_splits", "kernel", "code", "screened"}``; ``kernel`` is the scoring
     kernel's name as rocprofv3 prints it; ``screened``: the call takes the screened route (fp16 screen, exact rescoring and
     certificate, exact fallback; crh_score_topk_screened), and route / kernel / code describe the exact route it replaces."""
-    import ctypes
     L = _lib.lib()
     d = d if d % 8 == 0 and (L.crh_score_topk_f16_supports_dim(d) if half else L.crh_score_topk_supports_dim(d)) else \
         next(w for w in (8, 16, 32, 64, 128, 256) if w >= d and (w >= 16 or not half))
-    full = L.crh_score_topk_f16_workspace_bytes if half else L.crh_score_topk_workspace_bytes
-    ws_bytes = full(n_users, n_items, d, k) if pack else L.crh_score_topk_min_workspace_bytes(n_users, k)
+    ws_bytes = _score_ws_bytes(n_users, n_items, d, k, half, pack)
     prefix, splits = ctypes.c_int64(0), ctypes.c_int(0)
     code = L.crh_score_topk_route(2 if half else 4, n_users, n_items, d, k, ws_bytes, 1 if has_bitmap else 0, n_splits,
                                   ctypes.byref(prefix), ctypes.byref(splits))
@@ -243,21 +248,16 @@ def score_topk_route(n_users: int, n_items: int, d: int, k: int, half: bool = Fa
 def score_topk_screen_plan(n_users: int, n_items: int, d: int, k: int, has_bitmap: bool = True) -> dict:
     """The screened route's plan for a call ``score_topk_route`` reports as screened: ``{"cuts", "compact"}`` -- the item-range
     cuts of its fp16 pass, and whether that pass streams only the rows the candidate bitmap leaves (CRH_SCORE_SCREEN_COMPACT)."""
-    import ctypes
-    L = _lib.lib()
-    ws_bytes = L.crh_score_topk_workspace_bytes(n_users, n_items, d, k)
     cuts, compact = ctypes.c_int32(0), ctypes.c_int32(0)
-    _lib.check(L.crh_score_topk_screen_plan(n_users, n_items, ws_bytes, 1 if has_bitmap else 0, ctypes.byref(cuts),
-                                            ctypes.byref(compact)), "crh_score_topk_screen_plan")
+    _lib.check(_lib.lib().crh_score_topk_screen_plan(n_users, n_items, _score_ws_bytes(n_users, n_items, d, k), 1 if has_bitmap else 0,
+                                                     ctypes.byref(cuts), ctypes.byref(compact)), "crh_score_topk_screen_plan")
     return {"cuts": int(cuts.value), "compact": bool(compact.value)}
 
 
 def score_topk_screen_ordered(n_users: int, n_items: int, d: int, k: int, has_bitmap: bool = True) -> bool:
     """Does a screened call of this shape stream the unmasked rows of its main range by descending norm (CRH_SCORE_SCREEN_ORDER)?
     True when the compaction is on, the fp16 pass is one cut and the workspace ``score_topk`` passes holds the sorted map."""
-    L = _lib.lib()
-    ws_bytes = L.crh_score_topk_workspace_bytes(n_users, n_items, d, k)
-    return bool(L.crh_score_topk_screen_ordered(n_users, n_items, ws_bytes, 1 if has_bitmap else 0))
+    return bool(_lib.lib().crh_score_topk_screen_ordered(n_users, n_items, _score_ws_bytes(n_users, n_items, d, k), 1 if has_bitmap else 0))
 
 
 def score_topk_screen_map(cand_bitmap: torch.Tensor, item_emb: torch.Tensor, item_base: int = 0, prefix: int = 0,
@@ -265,7 +265,6 @@ def score_topk_screen_map(cand_bitmap: torch.Tensor, item_emb: torch.Tensor, ite
     """Only the map construction of the screened route's stage 0 (a test entry point): ``(map, keys)``, int32 device tensors --
     the ids of the unmasked items of ``[item_base + prefix, item_base + n_items)`` in the order the fp16 pass streams them and
     the 16-bit norm keys of those rows."""
-    import ctypes
     _need_cuda(cand_bitmap, item_emb)
     assert cand_bitmap.dtype == torch.int32 and item_emb.dtype == torch.float32 and item_emb.shape[1] == 128
     item_emb = item_emb.contiguous()
@@ -284,9 +283,8 @@ def score_topk_screen_rated_tiles(n_users: int, n_items: int, d: int, k: int, ha
     """Does a screened call of this shape gate the rated-list lookups of its fp16 pass by per-tile flags
     (CRH_SCORE_SCREEN_RATED_TILES)?  True when the compaction is on, the call has rated lists and the workspace ``score_topk``
     passes holds the flags and the inverse map."""
-    L = _lib.lib()
-    ws_bytes = L.crh_score_topk_workspace_bytes(n_users, n_items, d, k)
-    return bool(L.crh_score_topk_screen_rated_tiles(n_users, n_items, ws_bytes, 1 if has_bitmap else 0, 1 if has_rated else 0))
+    return bool(_lib.lib().crh_score_topk_screen_rated_tiles(n_users, n_items, _score_ws_bytes(n_users, n_items, d, k),
+                                                             1 if has_bitmap else 0, 1 if has_rated else 0))
 
 
 def score_topk_screen_flags(cand_bitmap: torch.Tensor, item_emb: torch.Tensor, rated_rowptr: torch.Tensor, rated_col: torch.Tensor,
