@@ -1268,13 +1268,13 @@ int print_wave_timing(unsigned long long* dev, int64_t n_waves, int timing, hipS
 // first 16 workgroups' waves (64 buckets) + [wave][cycles in events, events] + [wave][cycles in the events' memory trips, trips],
 // printed to stderr after the launch
 int dma_timing_begin(ScoreArgs& a, hipStream_t st) {
-    CRH_HIP(hipMalloc(&a.wave_clock, (size_t)16 * 4 * 68 * 8));
-    CRH_HIP(hipMemsetAsync(a.wave_clock, 0, (size_t)16 * 4 * 68 * 8, st));
+    CRH_HIP(hipMalloc(&a.wave_clock, (size_t)16 * 4 * 80 * 8));      // (68 words a wave, then 11 a wave of the body's segments)
+    CRH_HIP(hipMemsetAsync(a.wave_clock, 0, (size_t)16 * 4 * 80 * 8, st));
     return CRH_OK;
 }
 int dma_timing_report(ScoreArgs& a, int esz, int d, hipStream_t st) {
     CRH_HIP(hipStreamSynchronize(st));
-    std::vector<unsigned long long> h((size_t)16 * 4 * 68);
+    std::vector<unsigned long long> h((size_t)16 * 4 * 80);
     CRH_HIP(hipMemcpy(h.data(), a.wave_clock, h.size() * 8, hipMemcpyDeviceToHost));
     CRH_HIP(hipFree(a.wave_clock));
     {
@@ -1302,6 +1302,22 @@ int dma_timing_report(ScoreArgs& a, int esz, int d, hipStream_t st) {
                     "%.0f cycles per wave = %.4f of the timed tile loop (64 waves)\n",
             (double)trip_n / 64.0, trip_n ? (double)trip_tk / (double)trip_n : 0.0, (double)trip_tk / 64.0,
             loop_cycles ? (double)trip_tk / (double)loop_cycles : 0.0);
+    {   // the hooked 16x16 body's segments (zeros from every other kernel): pairs of tiles without an event, 64 waves
+        unsigned long long pairs = 0, seg[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int q = 0; q < 64; ++q) {
+            pairs += h[(size_t)16 * 4 * 68 + (size_t)q * 11];
+            for (int sg = 0; sg < 10; ++sg) seg[sg] += h[(size_t)16 * 4 * 68 + (size_t)q * 11 + 1 + sg];
+        }
+        if (pairs) {
+            static const char* const nm[5] = {"group 0", "dma wait + barrier", "group 1", "group 2 + event test", "group 3 + trip edge"};
+            double sum = 0;
+            for (int sg = 0; sg < 10; ++sg) sum += (double)seg[sg] / (double)pairs;
+            fprintf(stderr, "[crh dma timing] segments of a pair without an event (%.0f pairs per wave, mean cycles; stamped, so longer than the "
+                            "histogram's tiles): pair %.0f =", (double)pairs / 64.0, sum);
+            for (int sg = 0; sg < 10; ++sg)
+                fprintf(stderr, " %s %s %.1f%s", sg < 5 ? "even" : "odd", nm[sg % 5], (double)seg[sg] / (double)pairs, sg == 9 ? "\n" : ",");
+        }
+    }
     a.wave_clock = nullptr;
     return CRH_OK;
 }
@@ -1675,6 +1691,7 @@ int score_topk_screened(const float* user_emb, const int32_t* users, int64_t n_u
     if (timing) {
         rc = dma_timing_begin(a, st);
         if (rc != CRH_OK) return rc;
+        if (timing >= 2) a.ablate |= 32;     // ... and the body's segment stamps, which lengthen the tiles the histogram times
     }
 #endif
     rc = launch_score_dma(2, D, 3, a, st);

@@ -230,6 +230,37 @@ constexpr bool DMA_M16_HOOKED = false;
 #else
 constexpr bool DMA_M16_HOOKED = true;
 #endif
+// Round 22 went through the listing of body16's common path.  Three steps, each with a switch that builds the form before it (variant
+// build, tools/ab_lib.sh):
+//   -DCRH_DMA_BODY_PADDED      the second pair of a block's maxima as two asm statements, and the counted fragment waits naming the
+//                              fragments they guard: hipcc pads each seam with an s_nop, twelve per tile.  Without it the pair is one
+//                              statement and the wait names nothing (the sched_barriers on both sides keep the MFMAs behind it)
+//   -DCRH_DMA_BODY_RECOMPUTE   the barrier group works out the fetch of tile j + 3 from j: clamped tile index, per-lane 64-bit addresses,
+//                              id slot and ring slot.  Without it the addresses are scalar bases carried from tile to tile plus a 32-bit
+//                              lane offset, the two LDS slots are carried offsets, the DMAs stand in gaps 0 - 2 and the state moves on
+//                              in the free gaps behind them, at most one vector and two scalar instructions each
+//   -DCRH_DMA_BODY_BRANCHY     the event inlined where it is tested and the trip's two bounds tested behind the bodies.  Without it the
+//                              event is marked unlikely and the tests are worked out (and pinned) in gaps of group 3
+#ifdef CRH_DMA_BODY_PADDED
+constexpr bool DMA_BODY_PADDED = true;
+#else
+constexpr bool DMA_BODY_PADDED = false;
+#endif
+#ifdef CRH_DMA_BODY_RECOMPUTE
+constexpr bool DMA_BODY_CARRY = false;
+#else
+constexpr bool DMA_BODY_CARRY = true;
+#endif
+// The second and the third are the COMPACTED kernel's alone (BODY_CARRY / BODY_STRAIGHT in the kernel).  In the uncompacted one each
+// of them measured slower than the form before it (a call without a bitmap: +2.2 and +1.9 ms per step, profiles/r22_body_ab.log):
+// with its events out of line and four more scalars alive across them hipcc reloads six times as many spilled SGPRs inside the loop.
+#ifdef CRH_DMA_BODY_BRANCHY
+constexpr bool DMA_BODY_STRAIGHT = false;
+#else
+constexpr bool DMA_BODY_STRAIGHT = true;
+#endif
+// a test whose branch leaves the common path where `straight` (the kernel's BODY_STRAIGHT) holds
+#define CRH_DMA_BODY_RARE(straight, x) ((straight) ? __builtin_expect(!!(x), 0) : (long)!!(x))
 // What the 16x16 event executes was shortened once more in round 17; the protocol, the inserts and their order are the same.  Each
 // step has a switch that builds the form before it (variant build, tools/ab_lib.sh):
 //   -DCRH_DMA_EVENT_RUNTIME_K    K' read from the launch's arguments.  Without it the 16x16 kernels are compiled for K' = SCREEN_KP (only
@@ -577,6 +608,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     constexpr int GR = 2, NG = NCH / GR;               // A fragments are read in groups of GR chunks, one group ahead
     constexpr int BG = NG / 2 - 1;                     // the group in front of which the ring barrier sits
     constexpr int TG = M16 ? 2 : 1;                    // the group behind which tile j-1's threshold test (and its events) sits
+    constexpr bool BODY_CARRY = DMA_BODY_CARRY && CM, BODY_STRAIGHT = DMA_BODY_STRAIGHT && CM;   // round 22, see the switches above
     static_assert(NCH % NW == 0 && NG % 4 == 0 && BG + 2 < NG, "row width not supported by the DMA kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -884,6 +916,29 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 #ifdef CRH_PROFILE
     unsigned long long ev_ticks = 0, ev_count = 0;       // CRH_SCORE_TIMING
     DmaTripProf tp = {0ull, 0ull};                       // ... and the memory trips inside the events
+    // ... and (round 22, the hooked 16x16 body) the segments of a pair of tiles: a stamp in front of each group and on both sides of
+    // the barrier, ten a pair.  Segment 5 b + s of body b (0 the even tile, 1 the odd one): s = 0 group 0, 1 the DMA wait and the
+    // barrier, 2 group 1, 3 group 2 with the event's test, 4 group 3 up to the next body's group 0 (the odd body's: with the trip head).
+    // A pair's ten are kept apart and added to the wave's sums at the trip head unless an event fell into the pair.  Each stamp is an
+    // s_memtime and waits for it with everything LDS in flight, which more than doubles a pair: the stamps are asked for on their own
+    // (CRH_SCORE_TIMING=2, the screen's stage 1) and show where the time is; the histogram of a run without them says how much there is.
+    unsigned seg_tmp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, seg_sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, seg_pairs = 0;
+    unsigned long long seg_prev = 0;
+    bool seg_ev = false;
+    // Compiled in by `make profile PFLAGS=-DCRH_DMA_BODY_STAMPS` only: even switched off, the ten tests and the scalars they keep alive
+    // lengthen the body the histogram times (the parent's form by a quarter).  Without the flag all of it folds away.
+#ifdef CRH_DMA_BODY_STAMPS
+    const bool seg_on = a.wave_clock != nullptr && blockIdx.x < 16 && (a.ablate & 32);     // CRH_SCORE_TIMING=2
+#else
+    constexpr bool seg_on = false;
+#endif
+    auto seg_stamp = [&](auto Kc) __attribute__((always_inline)) {
+        if (seg_on) {
+            const unsigned long long t = __builtin_amdgcn_s_memtime();
+            seg_tmp[decltype(Kc)::value] = (unsigned)(t - seg_prev);
+            seg_prev = t;
+        }
+    };
 #endif
     // M16: the event of user block u at tile ts, in the form the wave's flag selects -- one scalar branch per event
     auto event16 = [&](const AccT& v, float& tau_u, int u, int64_t ts, int rows_left, int gi0, unsigned tb, int idv, bool rt) __attribute__((always_inline)) {
@@ -1118,6 +1173,43 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     uint32_t ring_a = ring_lds;
     int next_sync = 0;           // first tile of the next lockstep window (wave 0; beyond the range elsewhere), set in front of the loop
     bool sync_due = false;       // the even body's trip head has a window to report: worked out in a gap of the odd body in front of it
+    // Round 22 (BODY_CARRY, the compacted kernel): the fetch of tile j + 3 is state carried from tile to tile and set in front of body 0.
+    // A DMA's global address is a scalar base plus a 32-bit lane offset (the saddr form), its LDS slot a scalar byte offset; the barrier
+    // group issues the three DMAs from this state and moves it on to tile j + 4 in the gaps behind them.
+    //   f_tile   this wave's pieces of the tile (clamped to the stream's last tile, as dma_tile clamps)
+    //   f_side   the tile's 32 ids (and the next tile's) in the map
+    //   f_soff   per lane, the byte offset of the lane's id from f_side (clamped like dma_ids).  It is worked out a body ahead, in the
+    //            gap of piece 1, from
+    //   f_sx     the lane clamp the body before that left: 252 bytes, or 124 at the stream's last tile, which has no next tile whose
+    //            ids lanes 32 .. 63 could bring
+    //   f_ids    LDS byte offset of the ids' slot in tbits;  f_ring  ... of the tile's ring slot
+    [[maybe_unused]] const char* f_tile = nullptr;
+    [[maybe_unused]] const char* f_side = nullptr;
+    [[maybe_unused]] unsigned f_soff = 0, f_sx = 0, f_ids = 0, f_ring = 0;
+    [[maybe_unused]] int f_jl = 0;          // body j moves the bases on while j < f_jl: tile t0 + j + 3 is not yet the stream's last
+    [[maybe_unused]] unsigned tb_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned*)tbits;
+    [[maybe_unused]] unsigned lane4 = (unsigned)lane * 4u, lane16 = (unsigned)lane * 16u;
+    // DMA_BODY_STRAIGHT: what the branch behind a body tests, worked out and pinned in a gap of its group 3.  Behind the odd body: the
+    // trip head has something to do or the stream has ended; behind the even body: the stream has ended
+    [[maybe_unused]] int trip_rare = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (M16 && DMA_M16_HOOKED && BODY_CARRY) {
+        asm volatile("" : "+v"(lane4));      // (opaque: one register each for the launch, not a shift per use nor a folded 64-bit pointer;
+        asm volatile("" : "+v"(lane16));     // tb_lds: one scalar add per M0, where the symbol's address plus an offset is two)
+        asm volatile("" : "+s"(tb_lds));
+    }
+#endif
+    auto lds_wait_bare = [&](auto Nc) __attribute__((always_inline)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (CRH_ABLATE(a.ablate) & 8) return;    // measurement only: what the fragment waits cost (results invalid)
+        // names no register: behind a statement that lists the fragments as outputs hipcc pads the group's first MFMA with an s_nop.
+        // The sched_barrier(0) on both sides keeps every MFMA that reads them behind it (cdna_hip_programming.md 5.7: form (iii)).
+        // Nothing but that and the register allocator's goodwill keeps a copy or a use of a fragment register from standing between
+        // its ds_read_b128 and this wait: tools/body_asm_report.py audits the listing for it (the line "fragment audit"), and the
+        // audit is to be repeated whenever hipcc or this body changes
+        asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(decltype(Nc)::value));
+#endif
+    };
     auto lds_read1 = [&](f32x4& dst, uint32_t addr, auto Oc) __attribute__((always_inline)) {
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(decltype(Oc)::value));
@@ -1131,9 +1223,11 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         float m[NU], a0[NU], a1[NU], a2[NU];
         unsigned long long hitm = 0ull;
         unsigned long long hitb[NU];
-        int tc = 0, tf = 0;
-        const unsigned* side = nullptr;
-        const char* gt = nullptr;
+        [[maybe_unused]] int tc = 0, tf = 0;
+        [[maybe_unused]] const unsigned* side = nullptr;
+        [[maybe_unused]] const char* gt = nullptr;
+        [[maybe_unused]] unsigned inc = 0, inct = 0;      // BODY_CARRY: steps of the carried state, from gap to gap
+        [[maybe_unused]] auto umin = [](unsigned x, unsigned y) __attribute__((always_inline)) { return x < y ? x : y; };
         auto hook = [&](auto Gc, auto Nc) __attribute__((always_inline)) {
             constexpr int g = decltype(Gc)::value, n = decltype(Nc)::value;
             if constexpr (g == 0 && !FIRST) {
@@ -1143,13 +1237,78 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 if constexpr ((n & 1) == 0) {
                     asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(a0[u]) : "v"(v[0]), "v"(v[1]), "v"(v[2]));
                     asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(a1[u]) : "v"(v[3]), "v"(v[4]), "v"(v[5]));
-                } else {
+                } else if constexpr (DMA_BODY_PADDED) {
                     asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(a2[u]) : "v"(v[6]), "v"(v[7]), "v"(a0[u]));
                     asm volatile("v_max_f32 %0, %1, %2" : "=v"(m[u]) : "v"(a1[u]), "v"(a2[u]));
+                } else {
+                    // one statement with one output (round 22).  Between two statements, the second reading what the first wrote, hipcc
+                    // puts an s_nop; and behind a statement with a scratch output it puts one too, because it hands the dead scratch
+                    // register to the next MFMA's result.  m[u] lives on to group 2: no MFMA of this body is given its register
+                    asm volatile("v_max3_f32 %0, %1, %2, %3\n\tv_max_f32 %0, %4, %0"
+                                 : "=&v"(m[u])
+                                 : "v"(v[6]), "v"(v[7]), "v"(a0[u]), "v"(a1[u]));
                 }
 #endif
             }
-            if constexpr (g == BG) {
+            if constexpr (g == BG && BODY_CARRY) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                // tile j+3 into the slot tile j-1 left, and its side band, in the issue order of `body`: side band, piece 0, piece 1 -- each
+                // out of the carried state, a gap to itself.  (Every step of the state below is pinned to its gap by an empty statement
+                // that names the scalar: left alone hipcc sinks all of them to the end of the trip, behind no MFMA.)
+                if constexpr (n == 0)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(f_side + f_soff),
+                                                     (__attribute__((address_space(3))) void*)(uintptr_t)(tb_lds + f_ids), 4, 0, 0);
+                // (The s_nop between a write of M0 and its DMA stays, twice a tile: the builtin's M0 write is glued to its DMA, so nothing
+                // written here can stand between them, and a statement that sets M0 itself would take the register from hipcc.)
+                if constexpr (n == 1 || n == 2) {
+                    asm volatile("" : "+v"(lane16));      // (opaque in the loop too: a scalar base and this offset, no 64-bit sum per lane)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(f_tile + lane16),
+                                                     (__attribute__((address_space(3))) void*)(ring + f_ring + (wave * CPW) * 1024), 16,
+                                                     (n - 1) * 1024, 0);
+                }
+                if constexpr (n == 2) {
+                    f_soff = umin(lane4, f_sx);           // the NEXT body's lane offset, from the clamp the body before left
+                    asm volatile("" : "+v"(f_soff));
+                }
+                // ... and on to tile j+4.  `inc`: the tile just fetched was not the stream's last (the clamp of dma_tile and dma_ids, scalar)
+                if constexpr (n == 3) {
+                    inc = j < f_jl ? 128u : 0u;                                     // ids: 32 words a tile
+                    asm volatile("" : "+s"(inc));
+                }
+                if constexpr (n == 4) {
+                    f_side += inc;
+                    asm volatile("" : "+s"(f_side));
+                }
+                if constexpr (n == 5) {
+                    f_sx = j < f_jl - 2 ? 252u : 124u;                              // the clamp of the body after the next: tile t0 + j + 5
+                    asm volatile("" : "+s"(f_sx));
+                }
+                if constexpr (n == 6) {
+                    inct = inc << 6;                                                // a tile: TILE_B = 64 * 128 bytes
+                    static_assert(TILE_B == 64 * 128 || !M16, "the tile's step is 64 times the ids'");
+                    if (CRH_ABLATE(a.ablate) & 2) inct = 0u;
+                    asm volatile("" : "+s"(inct));
+                }
+                if constexpr (n == 7) {
+                    f_tile += inct;
+                    asm volatile("" : "+s"(f_tile));
+                }
+                if constexpr (n == 8) lds_read1(c[3][0], ring_a, std::integral_constant<int, P * TILE_B + 3 * 2048>{});
+                if constexpr (n == 9) lds_read1(c[3][1], ring_a, std::integral_constant<int, P * TILE_B + 3 * 2048 + 256>{});
+                // odd body: that was the pair's last read; the next pair (and this body's look-ahead) starts at slot (j + 1) & 2, two slots
+                // from the one just refilled
+                if constexpr (n == 10 && P == 1) ring_a = ring_lds + (f_ring ^ (unsigned)(2 * TILE_B));
+                if constexpr (n == 11) {
+                    f_ids = (f_ids + 128u) & (unsigned)(IDS_SLOTS * 128 - 1);
+                    asm volatile("" : "+s"(f_ids));
+                }
+                if constexpr (n == 12) {
+                    f_ring = (f_ring + (unsigned)TILE_B) & (unsigned)(R * TILE_B - 1);
+                    asm volatile("" : "+s"(f_ring));
+                }
+#endif
+            }
+            if constexpr (g == BG && !BODY_CARRY) {
                 // tile j+3 into the slot tile j-1 left, and its side band, in the issue order of `body`: side band, piece 0, piece 1
                 if constexpr (n == 0) {
                     tc = (int)t0 + j + 3;
@@ -1198,17 +1357,43 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 if constexpr (n == 6) lds_read1(c[2][0], ring_a, std::integral_constant<int, LA + 2 * 2048>{});
                 if constexpr (n == 7) lds_read1(c[2][1], ring_a, std::integral_constant<int, LA + 2 * 2048 + 256>{});
                 if constexpr (n == 8 && P == 1) sync_due = (j + 1 >= next_sync) & (j + 1 < n_steps);
+                if constexpr (n == 9 && BODY_STRAIGHT && !FIRST) {
+                    // the test of the branch behind this body, here and not behind the last MFMA: written out, because hipcc sinks the
+                    // C++ form to its use.  Odd body: j + 1 has reached the next window (or rated-tile fetch) or passed the stream's end
+#if defined(__HIP_DEVICE_COMPILE__)
+                    int rare;
+                    if constexpr (P == 1)
+                        asm volatile("s_min_i32 %0, %1, %2\n\ts_cmp_ge_i32 %3, %0\n\ts_cselect_b32 %0, 1, 0"
+                                     : "=&s"(rare) : "s"(next_sync), "s"(n_steps + 1), "s"(j + 1) : "scc");
+                    else
+                        asm volatile("s_cmp_gt_i32 %1, %2\n\ts_cselect_b32 %0, 1, 0" : "=s"(rare) : "s"(j + 1), "s"(n_steps) : "scc");
+                    trip_rare = rare;
+#endif
+                }
             }
         };
         auto group = [&](auto Gc) __attribute__((always_inline)) {
             constexpr int g = decltype(Gc)::value;
+#ifdef CRH_PROFILE
+            // CRH_SCORE_TIMING: the segment that ends here (the front of group 0 ends the group 3 of the body before)
+            if constexpr (g == 0) seg_stamp(std::integral_constant<int, 5 * (1 - P) + 4>{});
+            else if constexpr (g == BG) seg_stamp(std::integral_constant<int, 5 * P + 0>{});
+            else seg_stamp(std::integral_constant<int, 5 * P + g>{});
+#endif
             if constexpr (g == BG) {
                 dma_wait_but_newest_tile();             // my pieces of tile j+1 (issued two tiles ago) have landed
                 if (!(CRH_ABLATE(a.ablate) & 4)) __builtin_amdgcn_s_barrier();
+#ifdef CRH_PROFILE
+                seg_stamp(std::integral_constant<int, 5 * P + 1>{});
+#endif
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (g == 0) lds_wait(c[g], std::integral_constant<int, 4>{});
-            else lds_wait(c[g], std::integral_constant<int, 2>{});
+            if constexpr (DMA_BODY_PADDED) {
+                if constexpr (g == 0) lds_wait(c[g], std::integral_constant<int, 4>{});
+                else lds_wait(c[g], std::integral_constant<int, 2>{});
+            } else {
+                lds_wait_bare(std::integral_constant<int, g == 0 ? 4 : 2>{});
+            }
             __builtin_amdgcn_sched_barrier(0);
             [&]<int... N>(std::integer_sequence<int, N...>) __attribute__((always_inline)) {
                 (([&]() __attribute__((always_inline)) {
@@ -1226,9 +1411,11 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                  ...);
             }(std::make_integer_sequence<int, 16>{});
             if constexpr (g == TG && !FIRST) {
-                if (hitm != 0ull && !(CRH_ABLATE(a.ablate) & 1)) {
+                // (BODY_STRAIGHT: an event is rare, one tile in 26 at the headline -- its code stands behind the loop's common path)
+                if (CRH_DMA_BODY_RARE(BODY_STRAIGHT, hitm != 0ull && !(CRH_ABLATE(a.ablate) & 1))) {
 #ifdef CRH_PROFILE
                     const unsigned long long ev_t0 = a.wave_clock != nullptr ? __builtin_amdgcn_s_memtime() : 0ull;
+                    seg_ev = true;
 #endif
                     const int64_t ts = t0 + j - 1;                                      // the tile being selected
                     const unsigned tb = has_bits ? tbits[((ts >> 6) & 1) * 64 + (ts & 63)] : 0u;
@@ -1324,6 +1511,13 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     atomicAdd(&a.wave_clock[((size_t)blockIdx.x * 4 + wave) * 64 + dt], 1ull);
                 }
                 t_prev = t_now;
+                // the pair's segments (the hooked 16x16 body stamps them), pairs with an event left out
+                if (seg_on && j >= 64 && !seg_ev) {
+#pragma unroll
+                    for (int q = 0; q < 10; ++q) seg_sum[q] += seg_tmp[q];
+                    seg_pairs += 1;
+                }
+                seg_ev = false;
             }
 #endif
             auto window = [&](int& nxt) __attribute__((always_inline)) {
@@ -1354,14 +1548,40 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         if constexpr (M16 && DMA_M16_HOOKED) {
             // body 0 peeled; a trip is then the odd body and the even one behind it, with the trip's head (an even j, as ever) between them
             lds_group(c[2], ring_lds, std::integral_constant<int, 2>{});
+            if constexpr (BODY_CARRY) {
+                // the carried fetch state for body 0: tile t0 + 3 into ring slot 3, its ids into slot 3
+                const int last = n_tiles32 - 1, t3 = (int)t0 + 3;
+                const int tc0 = t3 < last ? t3 : last;
+                f_jl = last - t3;
+                f_tile = packed + (wave * CPW) * 1024 + (int64_t)((CRH_ABLATE(a.ablate) & 2) ? 0 : tc0) * TILE_B;
+                f_ring = 3u * (unsigned)TILE_B;
+                f_side = reinterpret_cast<const char*>(a.idmap) + (int64_t)tc0 * 128;
+                const unsigned lim0 = t3 < last ? 252u : 124u;
+                f_soff = lane4 < lim0 ? lane4 : lim0;
+                f_sx = t3 + 1 < last ? 252u : 124u;           // body 1's
+                f_ids = 3u * 128u;
+            }
             trip_head(0, 0 >= next_sync);
             body16(std::integral_constant<int, 0>{}, std::true_type{}, 0);
             for (int j = 1;; j += 2) {                    // (n_steps >= 1: body 1 always runs)
                 body16(std::integral_constant<int, 1>{}, std::false_type{}, j);
-                if (j + 1 > n_steps) break;
-                trip_head(j + 1, sync_due);
-                body16(std::integral_constant<int, 0>{}, std::false_type{}, j + 1);
-                if (j + 2 > n_steps) break;
+                if constexpr (BODY_STRAIGHT) {
+                    // one test, worked out in the body: a trip falls through odd body, head and even body and takes the back edge alone
+                    if (CRH_DMA_BODY_RARE(BODY_STRAIGHT, trip_rare != 0)) {
+                        if (j + 1 > n_steps) break;
+                        trip_head(j + 1, sync_due);
+                    }
+#ifdef CRH_PROFILE
+                    else trip_head(j + 1, false);             // (its stamp)
+#endif
+                    body16(std::integral_constant<int, 0>{}, std::false_type{}, j + 1);
+                    if (CRH_DMA_BODY_RARE(BODY_STRAIGHT, trip_rare != 0)) break;
+                } else {
+                    if (j + 1 > n_steps) break;
+                    trip_head(j + 1, sync_due);
+                    body16(std::integral_constant<int, 0>{}, std::false_type{}, j + 1);
+                    if (j + 2 > n_steps) break;
+                }
             }
         } else {
             for (int j = 0; j <= n_steps; j += 2) {
@@ -1387,6 +1607,9 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         a.wave_clock[(size_t)16 * 4 * 64 + ((size_t)blockIdx.x * 4 + wave) * 2 + 1] = ev_count;
         a.wave_clock[(size_t)16 * 4 * 66 + ((size_t)blockIdx.x * 4 + wave) * 2] = tp.ticks;
         a.wave_clock[(size_t)16 * 4 * 66 + ((size_t)blockIdx.x * 4 + wave) * 2 + 1] = tp.count;
+        // the segments' own region, behind everything the other reports read: [wave][pairs, ten sums]
+        a.wave_clock[(size_t)16 * 4 * 68 + ((size_t)blockIdx.x * 4 + wave) * 11] = seg_pairs;
+        for (int q = 0; q < 10; ++q) a.wave_clock[(size_t)16 * 4 * 68 + ((size_t)blockIdx.x * 4 + wave) * 11 + 1 + q] = seg_sum[q];
     }
 #endif
     if (live) {
