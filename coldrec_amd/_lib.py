@@ -127,6 +127,10 @@ SIGNATURES = {
     "crh_mtpr_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64, _i64]),
     "crh_mtpr_f32": (_i32, [_vp, _i64, _vp, _i64] + [_vp] * 6 + [_i32] * 4 + [_vp] * 5 + [_i64, _i64] + [_vp] * 5 +
                             [_i64, _i64, _i64, _i32, _i32, _f32, _f32] + [_vp] * 7 + [_sz, _vp]),
+    "crh_vbpr_chunk_rows": (_i32, []),
+    "crh_vbpr_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64, _i64]),
+    "crh_vbpr_f32": (_i32, [_vp, _i64, _vp, _i64] + [_vp] * 6 + [_i32] * 4 + [_vp] * 5 + [_i64, _i64] + [_vp] * 5 +
+                            [_i64, _i64, _i64, _i32, _i32, _f32, _f32, _f32] + [_vp] * 8 + [_sz, _vp]),
     "crh_adagrad_rows_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _vp]),
     "crh_ngcf_workspace_bytes": (_sz, [_i64, _i32]),
     "crh_ngcf_layer_fwd_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _f32, _vp, _f32, _vp]),

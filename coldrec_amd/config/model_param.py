@@ -94,4 +94,10 @@ def model_specific_param(model_name, parser, available_models):
         parser.add_argument('--p_ctx', type=_lr_wd_pair, default=[0.05, 0.01],
                             help='lr and weight decay of the content projection W and of weu')
         parser.add_argument('--p_proj', type=_lr_wd_pair, default=[0.05, 0.01], help='lr and weight decay of wei')
+    if model_name in ('VBPR', 'AMR'):      # config/model_param.py:292-299
+        parser.add_argument('--p_emb', type=_lr_wd_pair, default=[0.05, 0.0], help='lr and weight decay of the three id tables')
+        parser.add_argument('--p_ctx', type=_lr_wd_pair, default=[0.05, 0.01], help='lr and weight decay of the content projection W')
+    if model_name == 'AMR':
+        parser.add_argument('--eps', type=float, default=0.1, help='Length of the adversarial shift of a content row')
+        parser.add_argument('--lmd', type=float, default=1, help='Weight of the adversarial term')
     return parser

@@ -1,4 +1,4 @@
-"""What the trainers around a fused HIP loss (CLCRec, CCFCRec, ALDI, GAR, MTPR) share: the epoch loop, the checkpoint of
+"""What the trainers around a fused HIP loss (CLCRec, CCFCRec, ALDI, GAR, MTPR, VBPR, AMR) share: the epoch loop, the checkpoint of
 the published tables, ``--save_emb``, the stock ``predict`` pair, and the loading of a backbone's saved tables.
 
 A trainer states the names of its loss terms and of the tables it publishes, and supplies ``_optimizers``,
@@ -36,9 +36,34 @@ def load_backbone_tables(who, args, data, emb_size=None, save_flag=' --save_emb 
     return tables
 
 
+VBPR_FILES = {'user_emb_main': 'user_emb_main_P', 'item_emb_main': 'item_emb_main_Q', 'user_emb_aux': 'user_emb_aux',
+              'item_emb_aux': 'item_emb_aux', 'w_value': 'W'}      # table -> the reference's file name (model/VBPR.py:50-54)
+
+
+def load_vbpr_tables(who, args, data, emb_size, content_dim):
+    """The five tensors a VBPR run saved under ./emb (either implementation's: the file names are the reference's), float32
+    on the CPU, in VBPR_FILES' order; ``who`` fronts the messages."""
+    stem = f'./emb/{args.dataset}_cold_{args.cold_object}_VBPR'
+    paths = [f'{stem}_{suffix}.pt' for suffix in VBPR_FILES.values()]
+    for p in paths:
+        if not os.path.isfile(p):
+            raise FileNotFoundError(
+                f'{who} requires {p}. Train VBPR first '
+                f'(e.g. main.py --model VBPR --dataset {args.dataset} --cold_object {args.cold_object} '
+                f'--emb_size {emb_size} --save_emb true).')
+    tensors = [torch.load(p, map_location='cpu').detach().float().contiguous() for p in paths]
+    shapes = [(data.user_num, emb_size), (data.item_num, emb_size), (data.user_num, emb_size), (data.item_num, emb_size),
+              (content_dim, emb_size)]
+    for p, t, shape in zip(paths, tensors, shapes):
+        if tuple(t.shape) != shape:
+            raise ValueError(f'{who}: {p} is {tuple(t.shape)}, this dataset and --emb_size {emb_size} need {shape}')
+    return tensors
+
+
 class FusedLossTrainer(BaseColdStartTrainer):
     LOSS_TERMS = ()                         # the names of model.last_terms' entries; the last one is the step's total
     TABLES = ('user_emb', 'item_emb')       # the attributes _current_tables() fills, in its order
+    SAVE_FILES = None                       # {table: file name's last part} of --save_emb; None: every table as '<table>.pt'
     UPLOAD_BATCHES = 64                     # _block_batches: batches of ids uploaded at once
 
     def _optimizers(self, model):
@@ -117,8 +142,8 @@ class FusedLossTrainer(BaseColdStartTrainer):
             a = self.args
             os.makedirs('./emb', exist_ok=True)
             stem = f'./emb/{a.dataset}_cold_{a.cold_object}_{a.model}'
-            for name in self.TABLES:
-                torch.save(getattr(self, name), f'{stem}_{name}.pt')
+            for name, last in (self.SAVE_FILES or {name: name for name in self.TABLES}).items():
+                torch.save(getattr(self, name), f'{stem}_{last}.pt')
 
     def save(self):
         with torch.no_grad():

@@ -1509,6 +1509,99 @@ def mtpr(user_table: torch.Tensor, item_table: torch.Tensor, h: torch.Tensor, we
     return loss, grad_user, grad_item, grad_h, grad_weu, grad_wei
 
 
+# ---- the two-tower BPR loss of VBPR and AMR (vbpr.hip) ---------------------------------------------------------------
+
+def vbpr_chunk_rows() -> int:
+    return int(_lib.lib().crh_vbpr_chunk_rows())
+
+
+def vbpr_workspace_bytes(batch: int, d: int, cold_user: bool, n_items: int, n_users: int) -> int:
+    return int(_lib.lib().crh_vbpr_workspace_bytes(int(batch), int(d), int(bool(cold_user)), int(n_items), int(n_users)))
+
+
+def vbpr_workspace(batch: int, d: int, cold_user: bool, n_items: int, n_users: int, device) -> torch.Tensor:
+    return torch.empty(max(vbpr_workspace_bytes(batch, d, cold_user, n_items, n_users), 1), dtype=torch.uint8,
+                       device=device)
+
+
+def vbpr_plan(users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_users: Optional[int] = None,
+              n_items: Optional[int] = None, id_range=None, chunk: Optional[int] = None) -> dict:
+    """The index side of one crh_vbpr_f32 step: ``gar_plan``'s arrays (same arguments, same id_range shortcut, same
+    errors) with the owners' occurrences cut into chunks of crh_vbpr_chunk_rows().  user_ids / item_ids are the distinct
+    ids, ascending: what ``adagrad_rows`` steps and the order of ``vbpr``'s grad_hsum rows."""
+    return _triple_plan("vbpr_plan", vbpr_chunk_rows, users, pos, neg, n_users, n_items, id_range, chunk)
+
+
+def vbpr(user_table: torch.Tensor, item_table: torch.Tensor, aux_table: torch.Tensor, h: torch.Tensor, plan: dict,
+         wd1: float, h_adv: Optional[torch.Tensor] = None, lmd: float = 1.0, cold_user: bool = False, scale: float = 1.0,
+         want_user: bool = True, want_item: bool = True, want_aux: bool = True, want_h: bool = True,
+         want_h_adv: bool = True, want_hsum: bool = False, want_loss: bool = True, grad_user=None, grad_item=None,
+         grad_aux=None, grad_h=None, grad_h_adv=None, grad_hsum=None, loss=None, workspace=None):
+    """The two-tower BPR loss of VBPR / AMR and its gradients in one call (crh_vbpr_f32).  user_table (nu, d), item_table
+    (ni, d); d % 4 == 0, 4 <= d <= 256.  Item mode: aux_table (nu, d), h (2 B, d) = the content projections of the
+    positives, then of the negatives; h_adv = None or the projections of the perturbed content, h's shape.  User mode
+    (cold_user): aux_table (ni, d), h (B, d) = the users' content projections, no h_adv.  fp32 contiguous; plan:
+    ``vbpr_plan``.  Returns (loss4 = [L_bpr, L_adv, R_emb, sum], grad_user, grad_item, grad_aux, grad_h, grad_h_adv,
+    grad_hsum); gradients are d sum / d . * scale.  The table gradients are written at the rows the batch touches ONLY: a
+    caller's buffer keeps every other row as it was (a new one is zeroed).  grad_hsum (n_items or n_users of the plan, d):
+    row s = grad_h's (+ grad_h_adv's) rows summed over the occurrences of the plan's item_ids[s] (user mode: user_ids[s]).
+    An output that is neither given nor wanted is not computed (None); want_h_adv counts only with h_adv; with
+    want_loss=False and no ``loss`` the loss is not computed either -- ``vbpr(..., want_user=False, want_item=False,
+    want_aux=False, want_h=False, want_hsum=True, want_loss=False)`` computes grad_hsum alone."""
+    _need_cuda(user_table, item_table, aux_table, h, h_adv, plan["users"], grad_user, grad_item, grad_aux, grad_h,
+               grad_h_adv, grad_hsum, loss, workspace)
+    dev = user_table.device
+    _check_2d_f32("vbpr", "tables and content rows", user_table, item_table, aux_table, h,
+                  *(() if h_adv is None else (h_adv,)))
+    cold_user = bool(cold_user)
+    d = user_table.shape[1]
+    _check_width("vbpr", d)
+    B = plan["batch"]
+    if cold_user and (h_adv is not None or grad_h_adv is not None):
+        raise RuntimeError("vbpr: h_adv is item mode's only (the reference's AMR cannot train cold users)")
+    if h_adv is None and grad_h_adv is not None:
+        raise RuntimeError("vbpr: grad_h_adv without h_adv")
+    aux_rows, hr = (item_table.shape[0], B) if cold_user else (user_table.shape[0], 2 * B)
+    if item_table.shape[1] != d or aux_table.shape != (aux_rows, d) or h.shape != (hr, d) \
+            or (h_adv is not None and h_adv.shape != h.shape):
+        raise RuntimeError("vbpr: item mode takes tables (nu, d), (ni, d), aux (nu, d) and h, h_adv (2 B, d); user mode aux "
+                           "(ni, d) and h (B, d), B the plan's batch")
+    _check_one_device("vbpr", "the tables'", dev, item_table, aux_table, h, h_adv, plan["users"], grad_user, grad_item,
+                      grad_aux, grad_h, grad_h_adv, grad_hsum, loss, workspace)
+    (u_lo, u_hi), (i_lo, i_hi) = plan["user_range"], plan["item_range"]
+    _check_ids_in_tables("vbpr", "ids", (u_lo, u_hi), (i_lo, i_hi), user_table, item_table)
+
+    what = "the shapes of the tables and the content rows"
+    grad_user = _grad_buffer("vbpr", what, grad_user, user_table, want_user, False)
+    grad_item = _grad_buffer("vbpr", what, grad_item, item_table, want_item, False)
+    grad_aux = _grad_buffer("vbpr", what, grad_aux, aux_table, want_aux, False)
+    grad_h = _grad_buffer("vbpr", what, grad_h, h, want_h, True)
+    if h_adv is not None:
+        grad_h_adv = _grad_buffer("vbpr", what, grad_h_adv, h_adv, want_h_adv, True)
+    n_own = plan["n_users"] if cold_user else plan["n_items"]
+    if grad_hsum is None:
+        grad_hsum = torch.empty((n_own, d), dtype=torch.float32, device=dev) if want_hsum else None
+    elif grad_hsum.dtype != torch.float32 or not grad_hsum.is_contiguous() or grad_hsum.shape != (n_own, d):
+        raise RuntimeError("vbpr: grad_hsum must be a contiguous float32 tensor of (the plan's distinct cold objects, d)")
+    if loss is not None or want_loss:
+        loss = _loss_buffer("vbpr", loss, 4, dev)
+    if all(t is None for t in (grad_user, grad_item, grad_aux, grad_h, grad_h_adv, grad_hsum, loss)):
+        raise RuntimeError("vbpr: nothing to compute")
+    workspace = _workspace_arg("vbpr", workspace, vbpr_workspace, B, d, cold_user, plan["n_items"], plan["n_users"], dev)
+    p = plan
+    _lib.check(_lib.lib().crh_vbpr_f32(
+        _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]),
+        _lib.ptr(aux_table), _lib.ptr(h), _lib.ptr(h_adv), _lib.ptr(p["users"]), _lib.ptr(p["pos"]), _lib.ptr(p["neg"]),
+        int(u_lo), int(u_hi), int(i_lo), int(i_hi), _lib.ptr(p["item_ids"]), _lib.ptr(p["item_ptr"]),
+        _lib.ptr(p["item_occ"]), _lib.ptr(p["item_chunk_ptr"]), _lib.ptr(p["item_chunk_own"]), int(p["n_items"]),
+        int(p["n_item_chunks"]), _lib.ptr(p["user_ids"]), _lib.ptr(p["user_ptr"]), _lib.ptr(p["user_occ"]),
+        _lib.ptr(p["user_chunk_ptr"]), _lib.ptr(p["user_chunk_own"]), int(p["n_users"]), int(p["n_user_chunks"]), int(B),
+        int(d), int(cold_user), float(wd1), float(lmd), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item),
+        _lib.ptr(grad_aux), _lib.ptr(grad_h), _lib.ptr(grad_h_adv), _lib.ptr(grad_hsum), _lib.ptr(loss),
+        _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_vbpr_f32")
+    return loss, grad_user, grad_item, grad_aux, grad_h, grad_h_adv, grad_hsum
+
+
 def adagrad_rows(p: torch.Tensor, g: torch.Tensor, state_sum: torch.Tensor, ids: torch.Tensor, lr: float,
                  eps: float = 1e-10, zero_grad: bool = True) -> None:
     """One step of torch.optim.Adagrad's defaults over the rows ``ids`` (int32, distinct) of p, in place:

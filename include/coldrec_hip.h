@@ -793,6 +793,48 @@ int crh_mtpr_f32(const float* user_table, int64_t user_rows, const float* item_t
                  void* stream);
 
 /*
+ * The two-tower BPR loss of VBPR and AMR (reference model/VBPR.py:127-165, model/AMR.py:137-202), forward and backward in
+ * one call (csrc/vbpr.hip).  d = the embedding width, 4 <= d <= 256, d % 4 == 0; per record b a user u, a positive i, a
+ * negative j; user_table P (user_rows, d), item_table Q (item_rows, d); base = <P[u], Q[i] - Q[j]>.
+ *   cold_user == 0  aux_table A (user_rows, d), h (2 batch, d): row o < batch = the content projection of the positive of
+ *                   record o, row batch + o of its negative; h_adv = NULL or the projections of the perturbed content, h's
+ *                   shape:  x = base + <A[u], h_i - h_j>,  x_adv = base + <A[u], hadv_i - hadv_j>
+ *   cold_user != 0  aux_table A (item_rows, d), h (batch, d): the content projection of the record's user; h_adv must be
+ *                   NULL (an argument error otherwise):  x = base + <h_b, A[i] - A[j]>
+ *   sp(t) = softplus(-t) = max(-t, 0) + log1p(exp(-|t|)); all sums over the batch, no means:
+ *     L_bpr = sum sp(x)    L_adv = lmd sum sp(x_adv)  (0 without h_adv)
+ *     R_emb = wd1 sum_b (|P[u]|^2 + |Q[i]|^2 + |Q[j]|^2 + |A[u]|^2), user mode |A[i]|^2 + |A[j]|^2 in |A[u]|^2's place
+ *             (a row counts once per occurrence)
+ *   loss_out       4 device floats: L_bpr, L_adv, R_emb, their sum (not scaled); NULL = not written
+ *   grad_user, grad_item, grad_aux  d sum / d table * scale, written at the touched rows ONLY: every other row of the
+ *                  caller's buffer keeps what it held; duplicate ids are summed in the plan's order
+ *   grad_h, grad_h_adv  d sum / d . * scale, h's shape, every row written; grad_h_adv without h_adv is an argument error
+ *   grad_hsum      (n_items, d) in item mode, (n_users, d) in user mode: row s = the sum of grad_h's (+ grad_h_adv's) rows
+ *                  over the occurrences of the s-th distinct cold object, in the order of item_ids / user_ids -- what AMR
+ *                  adds to its noise.  It does not need grad_h: it may be the only output asked for
+ *                  Any output may be NULL: it is not computed and the others keep their bits; all NULL is an error
+ *   ids and inverse indices: as crh_gar_f32's, with chunks of crh_vbpr_chunk_rows() (ops.vbpr_plan builds them)
+ *   workspace      crh_vbpr_workspace_bytes(batch, d, cold_user, n_items, n_users) bytes (0 = a refused shape), 256-byte
+ *                  aligned: the per-occurrence gradient rows, the records' terms, the owner chunks' partials
+ * 1 <= batch < 2^30; every float pointer 16-byte aligned.  A record whose id leaves a table contributes nothing.  No
+ * atomics, every sum in an order fixed by (batch, d) and the plan: two identical calls give identical bits.  One lane
+ * group per record, one workgroup for the loss, then one wave per chunk of an owner's occurrences and the chunks'
+ * partial sums added in chunk order.
+ */
+int crh_vbpr_chunk_rows(void);
+size_t crh_vbpr_workspace_bytes(int64_t batch, int d, int cold_user, int64_t n_items, int64_t n_users);
+int crh_vbpr_f32(const float* user_table, int64_t user_rows, const float* item_table, int64_t item_rows,
+                 const float* aux_table, const float* h, const float* h_adv, const int32_t* users, const int32_t* pos,
+                 const int32_t* neg, int user_min, int user_max, int item_min, int item_max, const int32_t* item_ids,
+                 const int32_t* item_ptr, const int32_t* item_occ, const int32_t* item_chunk_ptr,
+                 const int32_t* item_chunk_own, int64_t n_items, int64_t n_item_chunks, const int32_t* user_ids,
+                 const int32_t* user_ptr, const int32_t* user_occ, const int32_t* user_chunk_ptr,
+                 const int32_t* user_chunk_own, int64_t n_users, int64_t n_user_chunks, int64_t batch, int d, int cold_user,
+                 float wd1, float lmd, float scale, float* grad_user, float* grad_item, float* grad_aux, float* grad_h,
+                 float* grad_h_adv, float* grad_hsum, float* loss_out, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
+/*
  * torch.optim.Adagrad's defaults (lr_decay = 0, weight_decay = 0, accumulator 0) over n_ids DISTINCT rows of a (n_rows, d)
  * table, d % 4 == 0, 4 <= d <= 256 (csrc/adagrad.hip).  Per element, every operation rounded on its own:
  *     s <- s + g * g ;  p <- p + (-lr) * (g / (sqrt(s) + eps))          (lr and eps rounded to fp32)
