@@ -16,7 +16,7 @@
 //            leave the record: x1 = a / tau (what q^_b = q_b / |q_b| is weighted with) and x2 = a cos / tau (what the
 //            owner's own row is weighted with); pass B re-reads the rows for sum a v / |v| and writes grad_q[b] whole (the
 //            cosines pushed through |q_b|, plus L_r2's term), the record's rank vectors for i_b and for u_b / k_b, and q^_b;
-//   item     one wave per chunk of at most CCF_CHUNK occurrences of one item, in index order: sum x1 q^_b, sum x2 and the
+//   item     one wave per chunk of at most LG_CHUNK occurrences of one item, in index order: sum x1 q^_b, sum x2 and the
 //            rank vectors of the occurrences with r = 0 -> one partial per chunk; then one lane group per item adds its
 //            chunks in chunk order and applies the item's own norm once: (sum x1 q^) / |v| - (sum x2) v / |v|^2;
 //   user     the same over the 2B occurrences (u_b with +, k_b with -) of the records' rank vectors;
@@ -28,7 +28,6 @@
 namespace {
 
 constexpr int CCF_MAX_ROWS = 4096;  // R: three LDS arrays of R floats per record (dynamic LDS, 48 KiB at the limit)
-constexpr int CCF_CHUNK = 256;      // occurrences of one owner summed by one wave
 
 // softplus(-z) and its derivative by z, -sigmoid(-z), from e = exp(-|z|)
 __device__ __forceinline__ float ccf_softplus_neg(float z, float* dz) {
@@ -164,8 +163,8 @@ __global__ __launch_bounds__(64) void ccf_item_chunk_kernel(const int32_t* __res
     f32x4 acc_q = {0.f, 0.f, 0.f, 0.f}, acc_r = acc_q;
     float acc_x = 0.f;
     if (s >= 0 && s < n_own) {                          // (uniform: a malformed plan sums nothing instead of reading wild)
-        const int64_t k_begin = (int64_t)own_ptr[s] + (ch - chunk_ptr[s]) * CCF_CHUNK;
-        int64_t k_end = k_begin + CCF_CHUNK;
+        const int64_t k_begin = (int64_t)own_ptr[s] + (ch - chunk_ptr[s]) * LG_CHUNK;
+        int64_t k_end = k_begin + LG_CHUNK;
         if (k_end > own_ptr[s + 1]) k_end = own_ptr[s + 1];
         const int64_t total = batch * rows;
         for (int64_t k0 = k_begin; k0 < k_end; k0 += 64) {
@@ -239,8 +238,8 @@ __global__ __launch_bounds__(64) void ccf_user_chunk_kernel(const int32_t* __res
     const int s = chunk_own[ch];
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     if (s >= 0 && s < n_own) {
-        const int64_t k_begin = (int64_t)own_ptr[s] + (ch - chunk_ptr[s]) * CCF_CHUNK;
-        int64_t k_end = k_begin + CCF_CHUNK;
+        const int64_t k_begin = (int64_t)own_ptr[s] + (ch - chunk_ptr[s]) * LG_CHUNK;
+        int64_t k_end = k_begin + LG_CHUNK;
         if (k_end > own_ptr[s + 1]) k_end = own_ptr[s + 1];
         for (int64_t k0 = k_begin; k0 < k_end; k0 += 64) {
             const int mine = k0 + lane < k_end ? own_rows[k0 + lane] : -1;
@@ -258,6 +257,7 @@ __global__ __launch_bounds__(64) void ccf_user_chunk_kernel(const int32_t* __res
     if (grp == 0 && ok) *reinterpret_cast<f32x4*>(part + ch * d + col) = acc;
 }
 
+// (its own kernel: the bare sum at row own_ids[s] would be a fourth finish of lg_owner_finish_kernel for this file alone)
 template <int LPR>
 __global__ __launch_bounds__(64) void ccf_user_finish_kernel(const int32_t* __restrict__ own_ids,
                                                              const int32_t* __restrict__ chunk_ptr, int64_t n_own, int d,
@@ -314,8 +314,8 @@ CcfWs ccf_layout(void* base, int64_t batch, int64_t rows, int d, int64_t n_items
     w.gi = c.take(batch * d);
     w.gu = c.take(batch * d);
     w.rec = c.take(batch * 4);
-    w.part_i = c.take(lg_max_chunks(m, n_items, CCF_CHUNK) * (2 * d + 4));
-    w.part_u = c.take(lg_max_chunks(2 * batch, n_users, CCF_CHUNK) * d);
+    w.part_i = c.take(lg_max_chunks(m, n_items, LG_CHUNK) * (2 * d + 4));
+    w.part_u = c.take(lg_max_chunks(2 * batch, n_users, LG_CHUNK) * d);
     w.bytes = c.bytes;
     return w;
 }
@@ -356,7 +356,7 @@ void ccf_launch(const CcfWs& w, const CcfArgs& a, hipStream_t st) {
 
 extern "C" int crh_ccfcrec_max_rows(void) { return CCF_MAX_ROWS; }
 
-extern "C" int crh_ccfcrec_chunk_rows(void) { return CCF_CHUNK; }
+extern "C" int crh_ccfcrec_chunk_rows(void) { return LG_CHUNK; }
 
 extern "C" size_t crh_ccfcrec_workspace_bytes(int64_t batch, int n_pos, int n_neg, int n_self, int d, int64_t n_items,
                                               int64_t n_users) {
@@ -388,7 +388,7 @@ extern "C" int crh_ccfcrec_f32(const float* user_table, int64_t user_rows, const
                   CCF_MAX_ROWS);
     CRH_CHECK_ARG(batch >= 1 && batch * rows < ((int64_t)1 << 31),
                   "crh_ccfcrec_f32: batch = %lld: batch * rows must lie in [1, 2^31)", (long long)batch);
-    LG_CHECK_OWNER_COUNTS("crh_ccfcrec_f32", io, batch * rows, "batch * rows", uo, 2 * batch, "2 batch", CCF_CHUNK);
+    LG_CHECK_OWNER_COUNTS("crh_ccfcrec_f32", io, batch * rows, "batch * rows", uo, 2 * batch, "2 batch", LG_CHUNK);
     LG_CHECK_IDS("crh_ccfcrec_f32", "user", user_min, user_max, user_rows);
     LG_CHECK_IDS("crh_ccfcrec_f32", "item", item_min, item_max, item_rows);
     CRH_CHECK_ARG(tau > 0.f && isfinite(tau), "crh_ccfcrec_f32: tau must be finite and > 0");

@@ -15,7 +15,7 @@
 //            p - 1 formed as -l_off / l, never as a difference of two numbers near 1).  Pass B: sum_g a2 X (the user's
 //            gradient of this record, plus its regulariser) and sum_g a1 Z pushed through normalize's backward (the
 //            positive's embedding gradient).  Written per record: u_b, h_b, both partial gradients, the loss terms;
-//   slot     one wave per chunk of at most CLC_CHUNK occurrences of one feat slot, occurrences in index order:
+//   slot     one wave per chunk of at most LG_CHUNK occurrences of one feat slot, occurrences in index order:
 //            sum a1 h_b, sum c a2 u_b, sum [c = 0] a2 u_b and the positives' gradients -> one partial per chunk;
 //   finish   one wave per slot adds its chunks' partials in chunk order, applies normalize's backward of F and the item
 //            regulariser times the occurrence count, writes grad_feat[slot] and grad_item[slot_item[slot]];
@@ -28,7 +28,6 @@
 namespace {
 
 constexpr int CLC_MAX_NEG = 1024;   // G: three LDS arrays of 1 + G floats per record (dynamic LDS, 12 KiB at the limit)
-constexpr int CLC_CHUNK = 256;      // occurrences of one slot summed by one wave
 constexpr float CLC_EPS = 1e-12f;   // F.normalize's clamp_min
 
 // softmax statistics of 1 + G scores held in LDS: returns the row's loss term lse - s_0 and turns every score into its
@@ -167,8 +166,8 @@ __global__ __launch_bounds__(64) void clc_slot_kernel(const int32_t* __restrict_
     const int s = chunk_slot[ch];
     f32x4 acc_a = {0.f, 0.f, 0.f, 0.f}, acc_c = acc_a, acc_d = acc_a, acc_p = acc_a;
     if (s >= 0 && s < n_slots) {                        // (uniform: a malformed plan sums nothing instead of reading wild)
-        const int64_t k_begin = (int64_t)slot_ptr[s] + (ch - chunk_ptr[s]) * CLC_CHUNK;
-        int64_t k_end = k_begin + CLC_CHUNK;
+        const int64_t k_begin = (int64_t)slot_ptr[s] + (ch - chunk_ptr[s]) * LG_CHUNK;
+        int64_t k_end = k_begin + LG_CHUNK;
         if (k_end > slot_ptr[s + 1]) k_end = slot_ptr[s + 1];
         for (int64_t k0 = k_begin; k0 < k_end; k0 += 64) {
             const int mine = k0 + lane < k_end ? slot_rows[k0 + lane] : -1;
@@ -293,7 +292,7 @@ struct ClcWs {
 };
 
 int64_t clc_max_chunks(int64_t batch, int n_neg, int64_t n_slots) {
-    return n_slots + batch * (n_neg + 1) / CLC_CHUNK;
+    return n_slots + batch * (n_neg + 1) / LG_CHUNK;
 }
 
 ClcWs clc_layout(void* base, int64_t batch, int n_neg, int d, int64_t n_slots) {
@@ -342,7 +341,7 @@ void clc_launch(const ClcWs& w, const float* ut, const float* vt, const float* f
 
 extern "C" int crh_clcrec_max_neg(void) { return CLC_MAX_NEG; }
 
-extern "C" int crh_clcrec_chunk_rows(void) { return CLC_CHUNK; }
+extern "C" int crh_clcrec_chunk_rows(void) { return LG_CHUNK; }
 
 extern "C" size_t crh_clcrec_workspace_bytes(int64_t batch, int n_neg, int d, int64_t n_slots) {
     if (!clc_shape_ok(batch, n_neg, d, n_slots)) return 0;
@@ -372,7 +371,7 @@ extern "C" int crh_clcrec_f32(const float* user_table, const float* item_table, 
     CRH_CHECK_ARG(n_users >= 1 && n_users <= batch, "crh_clcrec_f32: n_users = %lld out of [1, batch]", (long long)n_users);
     CRH_CHECK_ARG(n_chunks >= n_slots && n_chunks <= clc_max_chunks(batch, n_neg, n_slots),
                   "crh_clcrec_f32: n_chunks = %lld out of [n_slots, n_slots + batch * (1 + n_neg) / %d]",
-                  (long long)n_chunks, CLC_CHUNK);
+                  (long long)n_chunks, LG_CHUNK);
     CRH_CHECK_ARG(temp > 0.f && isfinite(temp), "crh_clcrec_f32: temp must be finite and > 0");
     CRH_CHECK_ARG(isfinite(lr_lambda) && isfinite(reg) && isfinite(scale), "crh_clcrec_f32: lr_lambda, reg and scale must be finite");
     CRH_CHECK_ARG(lg_aligned16(user_table, item_table, feat, grad_user, grad_item, grad_feat),

@@ -15,11 +15,13 @@
 // Plain launches on one stream (no atomics, every sum in an order fixed by the shape -> two identical calls give
 // identical bits).  A lane group of LPR = pow2(d / 4) lanes holds one row, four columns per lane (16-byte loads):
 //   record   one lane group per record: the dots, the three bpr terms and their slopes, the five sums of squares; the
-//            record's three gradient rows without R's part (for Ur, Pr, Nr) into the workspace and grad_gen's row;
+//            record's three gradient rows without R's part into the workspace (Ur's in gu, Pr's at row b and Nr's at row
+//            B + b of gq) and grad_gen's row;
 //   loss     one workgroup adds the B records' terms in index order -> loss_out and the four factors reg / (B |block|_F);
 //   gen      grad_gen += factor_G G, every row;
-//   user     one wave per chunk of at most GAR_CHUNK records of one user, in index order -> one partial per chunk; then
-//            one lane group per distinct user adds its chunks in chunk order and R's part, count x factor_U x U[u];
+//   user     loss_common.h's owner pass: one wave per chunk of at most LG_CHUNK records of one user, in index order ->
+//            one partial per chunk; then one lane group per distinct user adds its chunks in chunk order and R's part,
+//            count x factor_U x U[u] (LgFinishNorms);
 //   item     the same over the 2B occurrences (o < B: the positive of record o, else the negative of record o - B), with
 //            the chunk's count of positives so that R's part is (n_pos factor_P + n_neg factor_N) V[i].
 #include <math.h>
@@ -27,8 +29,6 @@
 #include "loss_common.h"
 
 namespace {
-
-constexpr int GAR_CHUNK = 256;      // occurrences of one owner summed by one wave
 
 // bpr(x) = -log(1e-5 + sigmoid(x)) and its derivative, from e = exp(-|x|)
 __device__ __forceinline__ float gar_bpr(float x, float* dx) {
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void gar_record_kernel(
     const float* __restrict__ ut, int64_t user_rows, const float* __restrict__ vt, int64_t item_rows,
     const int32_t* __restrict__ users, const int32_t* __restrict__ pos, const int32_t* __restrict__ neg,
     const float* __restrict__ gen, int64_t batch, int d, int cold_user, float w1, float w2, float w3, float wm,
-    float* __restrict__ gu, float* __restrict__ gp, float* __restrict__ gn, float* __restrict__ grad_gen,
+    float* __restrict__ gu, float* __restrict__ gq, float* __restrict__ grad_gen,
     float* __restrict__ rec_a, float* __restrict__ rec_b) {
     constexpr int RG = 64 / LPR;
     const auto [lane, cl, grp, col] = lg_coords<LPR>();
@@ -80,8 +80,10 @@ __global__ __launch_bounds__(64) void gar_record_kernel(
     }
     if (live && ok) {
         if (gu) *reinterpret_cast<f32x4*>(gu + o) = du;
-        if (gp) *reinterpret_cast<f32x4*>(gp + o) = dp;
-        if (gn) *reinterpret_cast<f32x4*>(gn + o) = ur * -c3;
+        if (gq) {
+            *reinterpret_cast<f32x4*>(gq + o) = dp;
+            *reinterpret_cast<f32x4*>(gq + batch * d + o) = ur * -c3;
+        }
         if (grad_gen) *reinterpret_cast<f32x4*>(grad_gen + o) = dg;
     }
     if (live && cl == 0) {
@@ -131,107 +133,21 @@ __global__ __launch_bounds__(256) void gar_gen_add_kernel(const float* __restric
     }
 }
 
-// ---- owner passes: one wave per chunk of one owner's occurrences ----------------------------------------------------
-// An occurrence o < B takes row o of `first`, otherwise row o - B of `second` (the user side has B occurrences and no
-// second block).  part[chunk] = d + 4 floats: the sum, then the chunk's count of o < B as an integer's bits.
-// (offsets and occurrences are read as unsigned: the item side's run to 2 B < 2^32)
-template <int LPR>
-__global__ __launch_bounds__(64) void gar_chunk_kernel(const uint32_t* __restrict__ own_ptr,
-                                                       const uint32_t* __restrict__ own_rows,
-                                                       const int32_t* __restrict__ chunk_ptr,
-                                                       const int32_t* __restrict__ chunk_own, int64_t n_own,
-                                                       int64_t batch, int64_t occurrences, int d,
-                                                       const float* __restrict__ first, const float* __restrict__ second,
-                                                       float* __restrict__ part) {
-    constexpr int RG = 64 / LPR;
-    const int64_t ch = blockIdx.x;
-    const auto [lane, cl, grp, col] = lg_coords<LPR>();
-    const bool ok = col < d;
-    const int s = chunk_own[ch];
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int n_first = 0;
-    if (s >= 0 && s < n_own) {                          // (uniform: a malformed plan sums nothing instead of reading wild)
-        const int64_t k_begin = (int64_t)own_ptr[s] + (ch - chunk_ptr[s]) * GAR_CHUNK;
-        int64_t k_end = k_begin + GAR_CHUNK;
-        if (k_end > own_ptr[s + 1]) k_end = own_ptr[s + 1];
-        if (k_end > occurrences) k_end = occurrences;
-        for (int64_t k0 = k_begin; k0 < k_end; k0 += 64) {
-            const bool have = k0 + lane < k_end;
-            const uint32_t mine = have ? own_rows[k0 + lane] : 0u;
-#pragma unroll 4
-            for (int j = 0; j < LPR; ++j) {
-                const int src = j * RG + grp;
-                const int64_t o = __shfl(mine, src);
-                if (!__shfl((int)have, src) || o >= occurrences || !ok) continue;
-                if (o < batch) {
-                    acc += *reinterpret_cast<const f32x4*>(first + o * d + col);
-                    ++n_first;
-                } else {
-                    acc += *reinterpret_cast<const f32x4*>(second + (o - batch) * d + col);
-                }
-            }
-        }
-    }
-    if constexpr (LPR < 64) {
-        acc = lg_cross_sum<LPR>(acc);
-#pragma unroll
-        for (int off = 32; off >= LPR; off >>= 1) n_first += __shfl_xor(n_first, off);
-    }
-    if (grp == 0 && ok) {
-        float* p = part + ch * (d + 4);
-        *reinterpret_cast<f32x4*>(p + col) = acc;
-        if (cl == 0) *reinterpret_cast<f32x4*>(p + d) = f32x4{__int_as_float(n_first), 0.f, 0.f, 0.f};
-    }
-}
-
-// one lane group per distinct owner: the chunks in chunk order, then R's part with the owner's own row
-template <int LPR>
-__global__ __launch_bounds__(64) void gar_finish_kernel(const float* __restrict__ table, int64_t table_rows,
-                                                        const int32_t* __restrict__ own_ids,
-                                                        const uint32_t* __restrict__ own_ptr,
-                                                        const int32_t* __restrict__ chunk_ptr, int64_t n_own, int d,
-                                                        const float* __restrict__ part, const float* __restrict__ rinv,
-                                                        int r_first, int r_second, float* __restrict__ grad) {
-    constexpr int RG = 64 / LPR;
-    const auto [lane, cl, grp, col] = lg_coords<LPR>();
-    const int64_t s = (int64_t)blockIdx.x * RG + grp;
-    if (col >= d || s >= n_own) return;
-    const int64_t id = own_ids[s];
-    if (id < 0 || id >= table_rows) return;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int64_t n_first = 0;
-    for (int64_t ch = chunk_ptr[s]; ch < chunk_ptr[s + 1]; ++ch) {
-        const float* p = part + ch * (d + 4);
-        acc += *reinterpret_cast<const f32x4*>(p + col);
-        n_first += __float_as_int(p[d]);
-    }
-    const int64_t n_all = (int64_t)own_ptr[s + 1] - (int64_t)own_ptr[s];
-    const float w = (float)n_first * rinv[r_first] + (float)(n_all - n_first) * rinv[r_second];
-    const f32x4 row = *reinterpret_cast<const f32x4*>(table + id * d + col);
-    *reinterpret_cast<f32x4*>(grad + id * d + col) = acc + row * w;
-}
-
 struct GarWs {
-    float *gu, *gp, *gn, *rec_a, *rec_b, *rinv, *part_u, *part_i;
+    float *gu, *gq, *rec_a, *rec_b, *rinv, *part_u, *part_i;
     size_t bytes;
 };
-
-bool gar_shape_ok(int64_t batch, int d, int64_t n_items, int64_t n_users) {
-    return batch >= 1 && batch < ((int64_t)1 << 31) && lg_width_ok(d) && n_items >= 1 && n_items <= 2 * batch &&
-           n_users >= 1 && n_users <= batch;
-}
 
 GarWs gar_layout(void* base, int64_t batch, int d, int64_t n_items, int64_t n_users) {
     GarWs w;
     WsCarver c(base);
     w.gu = c.take(batch * d);
-    w.gp = c.take(batch * d);
-    w.gn = c.take(batch * d);
+    w.gq = c.take(2 * batch * d);
     w.rec_a = c.take(batch * 4);
     w.rec_b = c.take(batch * 4);
     w.rinv = c.take(4);
-    w.part_u = c.take(lg_max_chunks(batch, n_users, GAR_CHUNK) * (d + 4));
-    w.part_i = c.take(lg_max_chunks(2 * batch, n_items, GAR_CHUNK) * (d + 4));
+    w.part_u = c.take(lg_max_chunks(batch, n_users, LG_CHUNK) * (d + 4));
+    w.part_i = c.take(lg_max_chunks(2 * batch, n_items, LG_CHUNK) * (d + 4));
     w.bytes = c.bytes;
     return w;
 }
@@ -255,7 +171,7 @@ void gar_launch(const GarWs& w, const GarArgs& a, hipStream_t st) {
                        a.vt, a.item_rows, a.users, a.pos, a.neg, a.gen, a.batch, a.d, a.cold_user,
                        a.scale * (1.f - a.alpha) * inv_b, a.scale * (1.f - a.beta) * inv_b, a.scale * a.beta * inv_b,
                        a.scale * 2.f * a.alpha * inv_b / (float)a.d, a.grad_user ? w.gu : nullptr,
-                       a.grad_item ? w.gp : nullptr, a.grad_item ? w.gn : nullptr, a.grad_gen, w.rec_a, w.rec_b);
+                       a.grad_item ? w.gq : nullptr, a.grad_gen, w.rec_a, w.rec_b);
     hipLaunchKernelGGL(gar_loss_kernel, dim3(1), dim3(256), 0, st, w.rec_a, w.rec_b, a.batch, a.d, a.alpha, a.beta, a.reg,
                        a.scale, a.loss, w.rinv);
     if (a.grad_gen) {
@@ -263,28 +179,21 @@ void gar_launch(const GarWs& w, const GarArgs& a, hipStream_t st) {
         hipLaunchKernelGGL(gar_gen_add_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, a.gen, w.rinv,
                            quads, a.grad_gen);
     }
-    if (a.grad_user) {
-        const LgOwners& o = a.uo;
-        hipLaunchKernelGGL((gar_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, lg_u32(o.ptr), lg_u32(o.occ),
-                           o.chunk_ptr, o.chunk_own, o.n, a.batch, a.batch, a.d, w.gu, w.gu, w.part_u);
-        hipLaunchKernelGGL((gar_finish_kernel<LPR>), dim3((unsigned)((o.n + RG - 1) / RG)), dim3(64), 0, st, a.ut, a.user_rows,
-                           o.ids, lg_u32(o.ptr), o.chunk_ptr, o.n, a.d, w.part_u, w.rinv, 0, 0, a.grad_user);
-    }
-    if (a.grad_item) {
-        const LgOwners& o = a.io;
-        hipLaunchKernelGGL((gar_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, lg_u32(o.ptr), lg_u32(o.occ),
-                           o.chunk_ptr, o.chunk_own, o.n, a.batch, 2 * a.batch, a.d, w.gp, w.gn, w.part_i);
-        hipLaunchKernelGGL((gar_finish_kernel<LPR>), dim3((unsigned)((o.n + RG - 1) / RG)), dim3(64), 0, st, a.vt, a.item_rows,
-                           o.ids, lg_u32(o.ptr), o.chunk_ptr, o.n, a.d, w.part_i, w.rinv, 1, 2, a.grad_item);
-    }
+    // (every occurrence of a user lies below `first` = B: R's part is count x factor_U)
+    if (a.grad_user)
+        lg_owner_pass(a.uo, a.ut, a.user_rows, a.batch, a.d, w.gu, w.part_u, LgFinishNorms{w.rinv, 0, 0}, a.grad_user, st,
+                      a.batch);
+    if (a.grad_item)
+        lg_owner_pass(a.io, a.vt, a.item_rows, 2 * a.batch, a.d, w.gq, w.part_i, LgFinishNorms{w.rinv, 1, 2}, a.grad_item, st,
+                      a.batch);
 }
 
 }  // namespace
 
-extern "C" int crh_gar_chunk_rows(void) { return GAR_CHUNK; }
+extern "C" int crh_gar_chunk_rows(void) { return LG_CHUNK; }
 
 extern "C" size_t crh_gar_workspace_bytes(int64_t batch, int d, int64_t n_items, int64_t n_users) {
-    if (!gar_shape_ok(batch, d, n_items, n_users)) return 0;
+    if (!lg_triple_shape_ok(batch, 31, d, 256, n_items, n_users)) return 0;
     return gar_layout(nullptr, batch, d, n_items, n_users).bytes;
 }
 
@@ -298,17 +207,12 @@ extern "C" int crh_gar_f32(const float* user_table, int64_t user_rows, const flo
                            float beta, float reg, float scale, float* grad_user, float* grad_item, float* grad_gen,
                            float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
     CRH_CHECK_ARG(user_table && item_table && gen, "crh_gar_f32: NULL table pointer");
-    CRH_CHECK_ARG(users && pos && neg, "crh_gar_f32: NULL id pointer");
     const LgOwners io{item_ids, item_ptr, item_occ, item_chunk_ptr, item_chunk_own, n_items, n_item_chunks};
     const LgOwners uo{user_ids, user_ptr, user_occ, user_chunk_ptr, user_chunk_own, n_users, n_user_chunks};
-    LG_CHECK_OWNER_PTRS("crh_gar_f32", io, uo);
+    LG_CHECK_TRIPLE_PTRS("crh_gar_f32", users, pos, neg, io, uo);
     CRH_CHECK_ARG(grad_user || grad_item || grad_gen || loss_out, "crh_gar_f32: NULL gradients and loss: nothing to compute");
     LG_CHECK_WIDTH("crh_gar_f32", d);
-    CRH_CHECK_ARG(batch >= 1 && batch < ((int64_t)1 << 31), "crh_gar_f32: batch = %lld must lie in [1, 2^31)",
-                  (long long)batch);
-    LG_CHECK_OWNER_COUNTS("crh_gar_f32", io, 2 * batch, "2 batch", uo, batch, "batch", GAR_CHUNK);
-    LG_CHECK_IDS("crh_gar_f32", "user", user_min, user_max, user_rows);
-    LG_CHECK_IDS("crh_gar_f32", "item", item_min, item_max, item_rows);
+    LG_CHECK_TRIPLE_SHAPE("crh_gar_f32", batch, 31, io, uo, user_min, user_max, user_rows, item_min, item_max, item_rows);
     CRH_CHECK_ARG(isfinite(alpha) && isfinite(beta) && isfinite(reg) && isfinite(scale),
                   "crh_gar_f32: alpha, beta, reg and scale must be finite");
     CRH_CHECK_ARG(lg_aligned16(user_table, item_table, gen, grad_user, grad_item, grad_gen),

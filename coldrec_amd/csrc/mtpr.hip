@@ -48,17 +48,16 @@
 //            every weight element twice, so a copy in LDS would be read no more often than it is written.
 //   reduce   two small kernels add the partials: chunks of 32 consecutive partials, then the chunk sums, in order.
 //   loss     one workgroup adds the B records' terms in index order -> loss6.
-//   owner    one wave per chunk of at most MTPR_CHUNK occurrences of one user (item: over the 2 B occurrences, o < B the
-//            positive of record o), in index order -> one partial per chunk; then one lane group per distinct owner adds
-//            its chunks in chunk order and 2 wd1 scale count x the owner's row.  Rows the batch does not touch are not
-//            written.
+//   owner    loss_common.h's owner pass: one wave per chunk of at most LG_CHUNK occurrences of one user (item: over the
+//            2 B occurrences, o < B the positive of record o), in index order -> one partial per chunk; then one lane
+//            group per distinct owner adds its chunks in chunk order and 2 wd1 scale count x the owner's row
+//            (LgFinishReg).  Rows the batch does not touch are not written.
 #include <math.h>
 
 #include "loss_common.h"
 
 namespace {
 
-constexpr int MTPR_CHUNK = 256;          // occurrences of one owner summed by one wave
 constexpr int MTPR_MAX_PARTS = 512;      // workgroups of the tile launch = weight-gradient partials
 constexpr int MTPR_SUM_CHUNK = 32;       // partials per first-stage sum
 
@@ -479,75 +478,12 @@ __global__ __launch_bounds__(256) void mtpr_loss_kernel(const float* __restrict_
     }
 }
 
-// ---- owner passes: one wave per chunk of one owner's occurrences ----------------------------------------------------
-// occurrence o takes row o of `rows` (w floats); part[chunk] = w floats
-// (offsets and occurrences are read as unsigned: the item side's run to 2 B < 2^32)
-template <int LPR>
-__global__ __launch_bounds__(64) void mtpr_chunk_kernel(const uint32_t* __restrict__ own_ptr,
-                                                        const uint32_t* __restrict__ own_rows,
-                                                        const int32_t* __restrict__ chunk_ptr,
-                                                        const int32_t* __restrict__ chunk_own, int64_t n_own,
-                                                        int64_t occurrences, int w, const float* __restrict__ rows,
-                                                        float* __restrict__ part) {
-    constexpr int RG = 64 / LPR;
-    const int64_t ch = blockIdx.x;
-    const auto [lane, cl, grp, col] = lg_coords<LPR>();
-    const bool ok = col < w;
-    const int s = chunk_own[ch];
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (s >= 0 && s < n_own) {                          // (uniform: a malformed plan sums nothing instead of reading wild)
-        const int64_t k_begin = (int64_t)own_ptr[s] + (ch - chunk_ptr[s]) * MTPR_CHUNK;
-        int64_t k_end = k_begin + MTPR_CHUNK;
-        if (k_end > own_ptr[s + 1]) k_end = own_ptr[s + 1];
-        if (k_end > occurrences) k_end = occurrences;
-        for (int64_t k0 = k_begin; k0 < k_end; k0 += 64) {
-            const bool have = k0 + lane < k_end;
-            const uint32_t mine = have ? own_rows[k0 + lane] : 0u;
-#pragma unroll 4
-            for (int j = 0; j < LPR; ++j) {
-                const int src = j * RG + grp;
-                const int64_t o = __shfl(mine, src);
-                if (!__shfl((int)have, src) || o >= occurrences || !ok) continue;
-                acc += *reinterpret_cast<const f32x4*>(rows + o * w + col);
-            }
-        }
-    }
-    if constexpr (LPR < 64) acc = lg_cross_sum<LPR>(acc);
-    if (grp == 0 && ok) *reinterpret_cast<f32x4*>(part + ch * w + col) = acc;
-}
-
-// one lane group per distinct owner: the chunks in chunk order, then R_emb's part with the owner's own row
-template <int LPR>
-__global__ __launch_bounds__(64) void mtpr_finish_kernel(const float* __restrict__ table, int64_t table_rows,
-                                                         const int32_t* __restrict__ own_ids,
-                                                         const uint32_t* __restrict__ own_ptr,
-                                                         const int32_t* __restrict__ chunk_ptr, int64_t n_own, int w,
-                                                         const float* __restrict__ part, float reg2,
-                                                         float* __restrict__ grad) {
-    constexpr int RG = 64 / LPR;
-    const auto [lane, cl, grp, col] = lg_coords<LPR>();
-    const int64_t s = (int64_t)blockIdx.x * RG + grp;
-    if (col >= w || s >= n_own) return;
-    const int64_t id = own_ids[s];
-    if (id < 0 || id >= table_rows) return;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t ch = chunk_ptr[s]; ch < chunk_ptr[s + 1]; ++ch) acc += *reinterpret_cast<const f32x4*>(part + ch * w + col);
-    const float cnt = (float)((int64_t)own_ptr[s + 1] - (int64_t)own_ptr[s]);
-    const f32x4 row = *reinterpret_cast<const f32x4*>(table + id * w + col);
-    *reinterpret_cast<f32x4*>(grad + id * w + col) = acc + row * (reg2 * cnt);
-}
-
 struct MtprWs {
     float *gp, *gq, *rec_a, *rec_b, *part, *chunk, *part_u, *part_i;
     size_t bytes;
 };
 
 bool mtpr_width_ok(int d) { return d >= 4 && d <= 128 && d % 4 == 0; }
-
-bool mtpr_shape_ok(int64_t batch, int d, int64_t n_items, int64_t n_users) {
-    return batch >= 1 && batch < ((int64_t)1 << 30) && mtpr_width_ok(d) && n_items >= 1 && n_items <= 2 * batch &&
-           n_users >= 1 && n_users <= batch;
-}
 
 MtprWs mtpr_layout(void* base, int64_t batch, int d, int cold_user, int64_t n_items, int64_t n_users) {
     const int64_t wp = cold_user ? d : 2 * d, wq = cold_user ? 2 * d : d;
@@ -563,8 +499,8 @@ MtprWs mtpr_layout(void* base, int64_t batch, int d, int cold_user, int64_t n_it
     w.rec_b = c.take(batch * 4);
     w.part = c.take(parts * pe);
     w.chunk = c.take((parts + MTPR_SUM_CHUNK - 1) / MTPR_SUM_CHUNK * pe);
-    w.part_u = c.take(lg_max_chunks(batch, n_users, MTPR_CHUNK) * wp);
-    w.part_i = c.take(lg_max_chunks(2 * batch, n_items, MTPR_CHUNK) * wq);
+    w.part_u = c.take(lg_max_chunks(batch, n_users, LG_CHUNK) * wp);
+    w.part_i = c.take(lg_max_chunks(2 * batch, n_items, LG_CHUNK) * wq);
     w.bytes = c.bytes;
     return w;
 }
@@ -580,23 +516,12 @@ void mtpr_launch_tiles(const MtprK& k, hipStream_t st) {
     }
 }
 
-void mtpr_owner_pass(const LgOwners& o, const float* table, int64_t table_rows, int64_t occurrences, int w,
-                     const float* rows, float* part, float reg2, float* grad, hipStream_t st) {
-    lg_dispatch_lpr(w, [&](auto lpr) {
-        constexpr int LPR = decltype(lpr)::value, RG = 64 / LPR;
-        hipLaunchKernelGGL((mtpr_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, lg_u32(o.ptr), lg_u32(o.occ),
-                           o.chunk_ptr, o.chunk_own, o.n, occurrences, w, rows, part);
-        hipLaunchKernelGGL((mtpr_finish_kernel<LPR>), dim3((unsigned)((o.n + RG - 1) / RG)), dim3(64), 0, st, table,
-                           table_rows, o.ids, lg_u32(o.ptr), o.chunk_ptr, o.n, w, part, reg2, grad);
-    });
-}
-
 }  // namespace
 
-extern "C" int crh_mtpr_chunk_rows(void) { return MTPR_CHUNK; }
+extern "C" int crh_mtpr_chunk_rows(void) { return LG_CHUNK; }
 
 extern "C" size_t crh_mtpr_workspace_bytes(int64_t batch, int d, int cold_user, int64_t n_items, int64_t n_users) {
-    if (!mtpr_shape_ok(batch, d, n_items, n_users)) return 0;
+    if (!lg_triple_shape_ok(batch, 30, d, 128, n_items, n_users)) return 0;
     return mtpr_layout(nullptr, batch, d, cold_user != 0, n_items, n_users).bytes;
 }
 
@@ -611,18 +536,13 @@ extern "C" int crh_mtpr_f32(const float* user_table, int64_t user_rows, const fl
                             float* grad_user, float* grad_item, float* grad_h, float* grad_weu, float* grad_wei,
                             float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
     CRH_CHECK_ARG(user_table && item_table && h && weu && wei, "crh_mtpr_f32: NULL table, content or projection pointer");
-    CRH_CHECK_ARG(users && pos && neg, "crh_mtpr_f32: NULL id pointer");
     const LgOwners io{item_ids, item_ptr, item_occ, item_chunk_ptr, item_chunk_own, n_items, n_item_chunks};
     const LgOwners uo{user_ids, user_ptr, user_occ, user_chunk_ptr, user_chunk_own, n_users, n_user_chunks};
-    LG_CHECK_OWNER_PTRS("crh_mtpr_f32", io, uo);
+    LG_CHECK_TRIPLE_PTRS("crh_mtpr_f32", users, pos, neg, io, uo);
     CRH_CHECK_ARG(grad_user || grad_item || grad_h || grad_weu || grad_wei || loss_out,
                   "crh_mtpr_f32: NULL gradients and loss: nothing to compute");
     CRH_CHECK_ARG(mtpr_width_ok(d), "crh_mtpr_f32: d = %d must be a multiple of 4 in [4, 128]", d);
-    CRH_CHECK_ARG(batch >= 1 && batch < ((int64_t)1 << 30), "crh_mtpr_f32: batch = %lld must lie in [1, 2^30)",
-                  (long long)batch);
-    LG_CHECK_OWNER_COUNTS("crh_mtpr_f32", io, 2 * batch, "2 batch", uo, batch, "batch", MTPR_CHUNK);
-    LG_CHECK_IDS("crh_mtpr_f32", "user", user_min, user_max, user_rows);
-    LG_CHECK_IDS("crh_mtpr_f32", "item", item_min, item_max, item_rows);
+    LG_CHECK_TRIPLE_SHAPE("crh_mtpr_f32", batch, 30, io, uo, user_min, user_max, user_rows, item_min, item_max, item_rows);
     CRH_CHECK_ARG(isfinite(wd1) && isfinite(scale), "crh_mtpr_f32: wd1 and scale must be finite");
     CRH_CHECK_ARG(lg_aligned16(user_table, item_table, h, weu, wei, grad_user, grad_item, grad_h, grad_weu, grad_wei),
                   "crh_mtpr_f32: tables, content rows, projections and gradients must be 16-byte aligned");
@@ -652,9 +572,9 @@ extern "C" int crh_mtpr_f32(const float* user_table, int64_t user_rows, const fl
                            grad_weu, grad_wei);
     }
     if (loss_out) hipLaunchKernelGGL(mtpr_loss_kernel, dim3(1), dim3(256), 0, st, w.rec_a, w.rec_b, batch, wd1, loss_out);
-    const float reg2 = 2.f * wd1 * scale;
-    if (grad_user) mtpr_owner_pass(uo, user_table, user_rows, batch, wp, w.gp, w.part_u, reg2, grad_user, st);
-    if (grad_item) mtpr_owner_pass(io, item_table, item_rows, 2 * batch, wq, w.gq, w.part_i, reg2, grad_item, st);
+    const LgFinishReg reg{2.f * wd1 * scale};
+    if (grad_user) lg_owner_pass(uo, user_table, user_rows, batch, wp, w.gp, w.part_u, reg, grad_user, st);
+    if (grad_item) lg_owner_pass(io, item_table, item_rows, 2 * batch, wq, w.gq, w.part_i, reg, grad_item, st);
     CRH_HIP(hipGetLastError());
     return CRH_OK;
 }

@@ -25,16 +25,15 @@
 //   record   one lane group per record: the dots, the terms and their slopes, the sums of squares; the record's
 //            per-occurrence gradient rows (without R_emb's part) into the workspace, dH and dHadv straight out;
 //   loss     one workgroup adds the B records' terms in index order -> loss4;
-//   owner    one wave per chunk of at most VBPR_CHUNK occurrences of one owner, in index order -> one partial per chunk;
-//            then one lane group per distinct owner adds its chunks in chunk order and, for a table, 2 wd1 scale count x
-//            the owner's row.  Table rows the batch does not touch are not written; hsum has one row per owner.
+//   owner    loss_common.h's owner pass: one wave per chunk of at most LG_CHUNK occurrences of one owner, in index order
+//            -> one partial per chunk; then one lane group per distinct owner adds its chunks in chunk order and, for a
+//            table, 2 wd1 scale count x the owner's row (LgFinishReg; hsum: LgFinishSum).  Table rows the batch does not
+//            touch are not written; hsum has one row per owner.
 #include <math.h>
 
 #include "loss_common.h"
 
 namespace {
-
-constexpr int VBPR_CHUNK = 256;          // occurrences of one owner summed by one wave
 
 struct VbprK {
     const float *P, *Q, *A, *H, *Hadv;
@@ -143,78 +142,10 @@ __global__ __launch_bounds__(256) void vbpr_loss_kernel(const float* __restrict_
     }
 }
 
-// ---- owner passes: one wave per chunk of one owner's occurrences ----------------------------------------------------
-// occurrence o takes row o of `rows` (d floats); part[chunk] = d floats
-// (offsets and occurrences are read as unsigned: the item side's run to 2 B < 2^32)
-template <int LPR>
-__global__ __launch_bounds__(64) void vbpr_chunk_kernel(const uint32_t* __restrict__ own_ptr,
-                                                        const uint32_t* __restrict__ own_rows,
-                                                        const int32_t* __restrict__ chunk_ptr,
-                                                        const int32_t* __restrict__ chunk_own, int64_t n_own,
-                                                        int64_t occurrences, int d, const float* __restrict__ rows,
-                                                        float* __restrict__ part) {
-    constexpr int RG = 64 / LPR;
-    const int64_t ch = blockIdx.x;
-    const auto [lane, cl, grp, col] = lg_coords<LPR>();
-    const bool ok = col < d;
-    const int s = chunk_own[ch];
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (s >= 0 && s < n_own) {                          // (uniform: a malformed plan sums nothing instead of reading wild)
-        const int64_t k_begin = (int64_t)own_ptr[s] + (ch - chunk_ptr[s]) * VBPR_CHUNK;
-        int64_t k_end = k_begin + VBPR_CHUNK;
-        if (k_end > own_ptr[s + 1]) k_end = own_ptr[s + 1];
-        if (k_end > occurrences) k_end = occurrences;
-        for (int64_t k0 = k_begin; k0 < k_end; k0 += 64) {
-            const bool have = k0 + lane < k_end;
-            const uint32_t mine = have ? own_rows[k0 + lane] : 0u;
-#pragma unroll 4
-            for (int j = 0; j < LPR; ++j) {
-                const int src = j * RG + grp;
-                const int64_t o = __shfl(mine, src);
-                if (!__shfl((int)have, src) || o >= occurrences || !ok) continue;
-                acc += *reinterpret_cast<const f32x4*>(rows + o * d + col);
-            }
-        }
-    }
-    if constexpr (LPR < 64) acc = lg_cross_sum<LPR>(acc);
-    if (grp == 0 && ok) *reinterpret_cast<f32x4*>(part + ch * d + col) = acc;
-}
-
-// one lane group per distinct owner: the chunks in chunk order; with a table, R_emb's part with the owner's own row added
-// and the sum written at the owner's row of the table's gradient; without one, the sum written at row s (hsum)
-template <int LPR>
-__global__ __launch_bounds__(64) void vbpr_finish_kernel(const float* __restrict__ table, int64_t table_rows,
-                                                         const int32_t* __restrict__ own_ids,
-                                                         const uint32_t* __restrict__ own_ptr,
-                                                         const int32_t* __restrict__ chunk_ptr, int64_t n_own, int d,
-                                                         const float* __restrict__ part, float reg2,
-                                                         float* __restrict__ out) {
-    constexpr int RG = 64 / LPR;
-    const auto [lane, cl, grp, col] = lg_coords<LPR>();
-    const int64_t s = (int64_t)blockIdx.x * RG + grp;
-    if (col >= d || s >= n_own) return;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t ch = chunk_ptr[s]; ch < chunk_ptr[s + 1]; ++ch) acc += *reinterpret_cast<const f32x4*>(part + ch * d + col);
-    if (!table) {
-        *reinterpret_cast<f32x4*>(out + s * d + col) = acc;
-        return;
-    }
-    const int64_t id = own_ids[s];
-    if (id < 0 || id >= table_rows) return;
-    const float cnt = (float)((int64_t)own_ptr[s + 1] - (int64_t)own_ptr[s]);
-    const f32x4 row = *reinterpret_cast<const f32x4*>(table + id * d + col);
-    *reinterpret_cast<f32x4*>(out + id * d + col) = acc + row * (reg2 * cnt);
-}
-
 struct VbprWs {
     float *gp, *gq, *ga, *gs, *rec_a, *rec_b, *part_u, *part_i;
     size_t bytes;
 };
-
-bool vbpr_shape_ok(int64_t batch, int d, int64_t n_items, int64_t n_users) {
-    return batch >= 1 && batch < ((int64_t)1 << 30) && lg_width_ok(d) && n_items >= 1 && n_items <= 2 * batch &&
-           n_users >= 1 && n_users <= batch;
-}
 
 VbprWs vbpr_layout(void* base, int64_t batch, int d, int cold_user, int64_t n_items, int64_t n_users) {
     VbprWs w;
@@ -226,30 +157,18 @@ VbprWs vbpr_layout(void* base, int64_t batch, int d, int cold_user, int64_t n_it
     w.rec_a = c.take(batch * 4);
     w.rec_b = c.take(batch * 4);
     // (a side's passes run one after the other on the stream and share the side's partials)
-    w.part_u = c.take(lg_max_chunks(batch, n_users, VBPR_CHUNK) * d);
-    w.part_i = c.take(lg_max_chunks(2 * batch, n_items, VBPR_CHUNK) * d);
+    w.part_u = c.take(lg_max_chunks(batch, n_users, LG_CHUNK) * d);
+    w.part_i = c.take(lg_max_chunks(2 * batch, n_items, LG_CHUNK) * d);
     w.bytes = c.bytes;
     return w;
 }
 
-// table == NULL: the sums go to row s of `out` (hsum)
-void vbpr_owner_pass(const LgOwners& o, const float* table, int64_t table_rows, int64_t occurrences, int d,
-                     const float* rows, float* part, float reg2, float* out, hipStream_t st) {
-    lg_dispatch_lpr(d, [&](auto lpr) {
-        constexpr int LPR = decltype(lpr)::value, RG = 64 / LPR;
-        hipLaunchKernelGGL((vbpr_chunk_kernel<LPR>), dim3((unsigned)o.n_chunks), dim3(64), 0, st, lg_u32(o.ptr), lg_u32(o.occ),
-                           o.chunk_ptr, o.chunk_own, o.n, occurrences, d, rows, part);
-        hipLaunchKernelGGL((vbpr_finish_kernel<LPR>), dim3((unsigned)((o.n + RG - 1) / RG)), dim3(64), 0, st, table,
-                           table_rows, o.ids, lg_u32(o.ptr), o.chunk_ptr, o.n, d, part, reg2, out);
-    });
-}
-
 }  // namespace
 
-extern "C" int crh_vbpr_chunk_rows(void) { return VBPR_CHUNK; }
+extern "C" int crh_vbpr_chunk_rows(void) { return LG_CHUNK; }
 
 extern "C" size_t crh_vbpr_workspace_bytes(int64_t batch, int d, int cold_user, int64_t n_items, int64_t n_users) {
-    if (!vbpr_shape_ok(batch, d, n_items, n_users)) return 0;
+    if (!lg_triple_shape_ok(batch, 30, d, 256, n_items, n_users)) return 0;
     return vbpr_layout(nullptr, batch, d, cold_user != 0, n_items, n_users).bytes;
 }
 
@@ -264,21 +183,16 @@ extern "C" int crh_vbpr_f32(const float* user_table, int64_t user_rows, const fl
                             float* grad_user, float* grad_item, float* grad_aux, float* grad_h, float* grad_h_adv,
                             float* grad_hsum, float* loss_out, void* workspace, size_t workspace_bytes, void* stream) {
     CRH_CHECK_ARG(user_table && item_table && aux_table && h, "crh_vbpr_f32: NULL table or content pointer");
-    CRH_CHECK_ARG(users && pos && neg, "crh_vbpr_f32: NULL id pointer");
     const LgOwners io{item_ids, item_ptr, item_occ, item_chunk_ptr, item_chunk_own, n_items, n_item_chunks};
     const LgOwners uo{user_ids, user_ptr, user_occ, user_chunk_ptr, user_chunk_own, n_users, n_user_chunks};
-    LG_CHECK_OWNER_PTRS("crh_vbpr_f32", io, uo);
+    LG_CHECK_TRIPLE_PTRS("crh_vbpr_f32", users, pos, neg, io, uo);
     const int cu = cold_user != 0;
     CRH_CHECK_ARG(!(cu && h_adv), "crh_vbpr_f32: h_adv is item mode's (cold_user == 0) only");
     CRH_CHECK_ARG(h_adv || !grad_h_adv, "crh_vbpr_f32: grad_h_adv without h_adv");
     CRH_CHECK_ARG(grad_user || grad_item || grad_aux || grad_h || grad_h_adv || grad_hsum || loss_out,
                   "crh_vbpr_f32: NULL gradients and loss: nothing to compute");
     LG_CHECK_WIDTH("crh_vbpr_f32", d);
-    CRH_CHECK_ARG(batch >= 1 && batch < ((int64_t)1 << 30), "crh_vbpr_f32: batch = %lld must lie in [1, 2^30)",
-                  (long long)batch);
-    LG_CHECK_OWNER_COUNTS("crh_vbpr_f32", io, 2 * batch, "2 batch", uo, batch, "batch", VBPR_CHUNK);
-    LG_CHECK_IDS("crh_vbpr_f32", "user", user_min, user_max, user_rows);
-    LG_CHECK_IDS("crh_vbpr_f32", "item", item_min, item_max, item_rows);
+    LG_CHECK_TRIPLE_SHAPE("crh_vbpr_f32", batch, 30, io, uo, user_min, user_max, user_rows, item_min, item_max, item_rows);
     CRH_CHECK_ARG(isfinite(wd1) && isfinite(lmd) && isfinite(scale), "crh_vbpr_f32: wd1, lmd and scale must be finite");
     CRH_CHECK_ARG(lg_aligned16(user_table, item_table, aux_table, h, h_adv, grad_user, grad_item, grad_aux, grad_h,
                                grad_h_adv, grad_hsum),
@@ -304,15 +218,15 @@ extern "C" int crh_vbpr_f32(const float* user_table, int64_t user_rows, const fl
     if (loss_out)
         hipLaunchKernelGGL(vbpr_loss_kernel, dim3(1), dim3(256), 0, st, w.rec_a, w.rec_b, batch, wd1, lmd, h_adv != nullptr,
                            loss_out);
-    const float reg2 = 2.f * wd1 * scale;
-    if (grad_user) vbpr_owner_pass(uo, user_table, user_rows, batch, d, w.gp, w.part_u, reg2, grad_user, st);
-    if (grad_item) vbpr_owner_pass(io, item_table, item_rows, 2 * batch, d, w.gq, w.part_i, reg2, grad_item, st);
+    const LgFinishReg reg{2.f * wd1 * scale};
+    if (grad_user) lg_owner_pass(uo, user_table, user_rows, batch, d, w.gp, w.part_u, reg, grad_user, st);
+    if (grad_item) lg_owner_pass(io, item_table, item_rows, 2 * batch, d, w.gq, w.part_i, reg, grad_item, st);
     if (cu) {
-        if (grad_aux) vbpr_owner_pass(io, aux_table, item_rows, 2 * batch, d, w.ga, w.part_i, reg2, grad_aux, st);
-        if (grad_hsum) vbpr_owner_pass(uo, nullptr, 0, batch, d, w.gs, w.part_u, 0.f, grad_hsum, st);
+        if (grad_aux) lg_owner_pass(io, aux_table, item_rows, 2 * batch, d, w.ga, w.part_i, reg, grad_aux, st);
+        if (grad_hsum) lg_owner_pass(uo, nullptr, 0, batch, d, w.gs, w.part_u, LgFinishSum{}, grad_hsum, st);
     } else {
-        if (grad_aux) vbpr_owner_pass(uo, aux_table, user_rows, batch, d, w.ga, w.part_u, reg2, grad_aux, st);
-        if (grad_hsum) vbpr_owner_pass(io, nullptr, 0, 2 * batch, d, w.gs, w.part_i, 0.f, grad_hsum, st);
+        if (grad_aux) lg_owner_pass(uo, aux_table, user_rows, batch, d, w.ga, w.part_u, reg, grad_aux, st);
+        if (grad_hsum) lg_owner_pass(io, nullptr, 0, 2 * batch, d, w.gs, w.part_i, LgFinishSum{}, grad_hsum, st);
     }
     CRH_HIP(hipGetLastError());
     return CRH_OK;

@@ -965,6 +965,11 @@ def _loss_buffer(op: str, loss, n: int, device) -> torch.Tensor:
     return loss
 
 
+def _new_workspace(nbytes: int, device) -> torch.Tensor:
+    """Private scratch of one fused-loss shape (the caching allocator hands out 512-byte aligned blocks)."""
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
 def _workspace_arg(op: str, workspace, make, *shape) -> torch.Tensor:
     """The workspace given (checked), else ``make(*shape)``."""
     if workspace is None:
@@ -981,8 +986,8 @@ def infonce_workspace_bytes(n_max: int, d: int) -> int:
 
 
 def infonce_workspace(n_max: int, d: int, device) -> torch.Tensor:
-    """Private scratch of one crh_infonce_f32 shape (the caching allocator hands out 512-byte aligned blocks)."""
-    return torch.empty(max(infonce_workspace_bytes(n_max, d), 1), dtype=torch.uint8, device=device)
+    """Private scratch of one crh_infonce_f32 shape."""
+    return _new_workspace(infonce_workspace_bytes(n_max, d), device)
 
 
 def infonce(view1: torch.Tensor, view2: torch.Tensor, tau: float, b_cos: bool = True, rows1=None, rows2=None, n_dev=None,
@@ -1033,7 +1038,7 @@ def table_nce_workspace_bytes(batch_max: int, n_rows: int, d: int) -> int:
 
 def table_nce_workspace(batch_max: int, n_rows: int, d: int, device) -> torch.Tensor:
     """Private scratch of one crh_table_nce_f32 shape: linear in n_rows, nothing of size batch x n_rows."""
-    return torch.empty(max(table_nce_workspace_bytes(batch_max, n_rows, d), 1), dtype=torch.uint8, device=device)
+    return _new_workspace(table_nce_workspace_bytes(batch_max, n_rows, d), device)
 
 
 def table_nce(ctx: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, tau: float, n_dev=None,
@@ -1084,7 +1089,7 @@ def clcrec_workspace_bytes(batch: int, n_neg: int, d: int, n_slots: int) -> int:
 
 
 def clcrec_workspace(batch: int, n_neg: int, d: int, n_slots: int, device) -> torch.Tensor:
-    return torch.empty(max(clcrec_workspace_bytes(batch, n_neg, d, n_slots), 1), dtype=torch.uint8, device=device)
+    return _new_workspace(clcrec_workspace_bytes(batch, n_neg, d, n_slots), device)
 
 
 def _grouped(ids: torch.Tensor):
@@ -1120,6 +1125,25 @@ def _owner_index(items: torch.Tensor, users: torch.Tensor, chunk: int) -> dict:
     return out
 
 
+def _owner_args(plan: dict) -> tuple:
+    """The inverse-index arguments of crh_ccfcrec_f32, crh_gar_f32, crh_mtpr_f32 and crh_vbpr_f32 in ABI order: the item
+    side's five arrays and two counts, then the user side's."""
+    p, ptr = plan, _lib.ptr
+    return (ptr(p["item_ids"]), ptr(p["item_ptr"]), ptr(p["item_occ"]), ptr(p["item_chunk_ptr"]), ptr(p["item_chunk_own"]),
+            int(p["n_items"]), int(p["n_item_chunks"]),
+            ptr(p["user_ids"]), ptr(p["user_ptr"]), ptr(p["user_occ"]), ptr(p["user_chunk_ptr"]), ptr(p["user_chunk_own"]),
+            int(p["n_users"]), int(p["n_user_chunks"]))
+
+
+def _triple_plan_checks(op: str, plan: dict, user_table, item_table, *others) -> tuple:
+    """What ``gar``, ``mtpr`` and ``vbpr`` check of their plan: its arrays on the tables' device with the call's other
+    tensors, its ids inside the tables.  Returns (user min, user max, item min, item max) as the ABI takes them."""
+    _check_one_device(op, "the tables'", user_table.device, item_table, *others, plan["users"])
+    (u_lo, u_hi), (i_lo, i_hi) = plan["user_range"], plan["item_range"]
+    _check_ids_in_tables(op, "ids", (u_lo, u_hi), (i_lo, i_hi), user_table, item_table)
+    return int(u_lo), int(u_hi), int(i_lo), int(i_hi)
+
+
 def _check_ids_in_plan(op: str, user_range, item_range, n_users: Optional[int], n_items: Optional[int]) -> None:
     if n_users is not None and (user_range[0] < 0 or user_range[1] >= n_users):
         raise RuntimeError(f"{op}: user id outside the user table")
@@ -1142,10 +1166,8 @@ def clcrec_plan(users: torch.Tensor, items: torch.Tensor, n_users: Optional[int]
         raise RuntimeError("clcrec_plan: users and items must be integer tensors on one device")
     flat = items.reshape(-1).long()
     ulong = users.long()
-    if n_users is not None and (int(ulong.min()) < 0 or int(ulong.max()) >= n_users):
-        raise RuntimeError("clcrec_plan: user id outside the user table")
-    if n_items is not None and (int(flat.min()) < 0 or int(flat.max()) >= n_items):
-        raise RuntimeError("clcrec_plan: item id outside the item table")
+    user_range, item_range = (int(ulong.min()), int(ulong.max())), (int(flat.min()), int(flat.max()))
+    _check_ids_in_plan("clcrec_plan", user_range, item_range, n_users, n_items)
 
     chunk = int(_lib.lib().crh_clcrec_chunk_rows())
     slot_item, slot_rows, slot_ptr, chunk_ptr, chunk_slot, slot = _owner_chunks(flat, chunk)
@@ -1153,7 +1175,7 @@ def clcrec_plan(users: torch.Tensor, items: torch.Tensor, n_users: Optional[int]
     c = lambda t: t.to(torch.int32).contiguous()
     return dict(batch=int(users.shape[0]), n_neg=int(items.shape[1] - 1), n_slots=int(slot_item.shape[0]),
                 n_chunks=int(chunk_slot.shape[0]), n_users=int(user_ids.shape[0]),
-                user_range=(int(user_ids[0]), int(user_ids[-1])), item_range=(int(slot_item[0]), int(slot_item[-1])),
+                user_range=user_range, item_range=item_range,
                 users=c(ulong), items=c(flat), slot=c(slot), slot_item=c(slot_item), slot_ptr=c(slot_ptr),
                 slot_rows=c(slot_rows), chunk_ptr=c(chunk_ptr), chunk_slot=c(chunk_slot), user_ids=c(user_ids),
                 user_ptr=c(user_ptr), user_recs=c(user_recs))
@@ -1217,8 +1239,7 @@ def ccfcrec_workspace_bytes(batch: int, n_pos: int, n_neg: int, n_self: int, d: 
 
 def ccfcrec_workspace(batch: int, n_pos: int, n_neg: int, n_self: int, d: int, n_items: int, n_users: int,
                       device) -> torch.Tensor:
-    return torch.empty(max(ccfcrec_workspace_bytes(batch, n_pos, n_neg, n_self, d, n_items, n_users), 1),
-                       dtype=torch.uint8, device=device)
+    return _new_workspace(ccfcrec_workspace_bytes(batch, n_pos, n_neg, n_self, d, n_items, n_users), device)
 
 
 def ccfcrec_plan(users: torch.Tensor, items: torch.Tensor, neg_users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
@@ -1285,12 +1306,9 @@ def ccfcrec(user_table: torch.Tensor, item_table: torch.Tensor, q: torch.Tensor,
     _lib.check(_lib.lib().crh_ccfcrec_f32(
         _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]), _lib.ptr(q),
         _lib.ptr(p["users"]), _lib.ptr(p["neg_users"]), _lib.ptr(p["items"]), int(p["user_range"][0]),
-        int(p["user_range"][1]), int(p["item_range"][0]), int(p["item_range"][1]), _lib.ptr(p["item_ids"]),
-        _lib.ptr(p["item_ptr"]), _lib.ptr(p["item_occ"]), _lib.ptr(p["item_chunk_ptr"]), _lib.ptr(p["item_chunk_own"]),
-        int(p["n_items"]), int(p["n_item_chunks"]), _lib.ptr(p["user_ids"]), _lib.ptr(p["user_ptr"]), _lib.ptr(p["user_occ"]),
-        _lib.ptr(p["user_chunk_ptr"]), _lib.ptr(p["user_chunk_own"]), int(p["n_users"]), int(p["n_user_chunks"]), int(B),
-        int(P), int(N), int(S), int(d), float(tau), float(lambda1), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item),
-        _lib.ptr(grad_q), _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_ccfcrec_f32")
+        int(p["user_range"][1]), int(p["item_range"][0]), int(p["item_range"][1]), *_owner_args(p), int(B), int(P), int(N),
+        int(S), int(d), float(tau), float(lambda1), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item), _lib.ptr(grad_q),
+        _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_ccfcrec_f32")
     return loss, grad_user, grad_item, grad_q
 
 
@@ -1301,7 +1319,7 @@ def aldi_workspace_bytes(batch: int, d: int) -> int:
 
 
 def aldi_workspace(batch: int, d: int, device) -> torch.Tensor:
-    return torch.empty(max(aldi_workspace_bytes(batch, d), 1), dtype=torch.uint8, device=device)
+    return _new_workspace(aldi_workspace_bytes(batch, d), device)
 
 
 def aldi(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
@@ -1363,7 +1381,7 @@ def gar_workspace_bytes(batch: int, d: int, n_items: int, n_users: int) -> int:
 
 
 def gar_workspace(batch: int, d: int, n_items: int, n_users: int, device) -> torch.Tensor:
-    return torch.empty(max(gar_workspace_bytes(batch, d, n_items, n_users), 1), dtype=torch.uint8, device=device)
+    return _new_workspace(gar_workspace_bytes(batch, d, n_items, n_users), device)
 
 
 def _triple_plan(op: str, chunk_rows, users, pos, neg, n_users, n_items, id_range, chunk) -> dict:
@@ -1412,10 +1430,7 @@ def gar(user_table: torch.Tensor, item_table: torch.Tensor, gen: torch.Tensor, p
     B = plan["batch"]
     if item_table.shape[1] != d or gen.shape != (B, d):
         raise RuntimeError("gar: the generator's output must be (B, d) of the tables' width, one row per record of the plan")
-    _check_one_device("gar", "the tables'", dev, item_table, gen, plan["users"], grad_user, grad_item, grad_gen, loss,
-                      workspace)
-    (u_lo, u_hi), (i_lo, i_hi) = plan["user_range"], plan["item_range"]
-    _check_ids_in_tables("gar", "ids", (u_lo, u_hi), (i_lo, i_hi), user_table, item_table)
+    id_range = _triple_plan_checks("gar", plan, user_table, item_table, gen, grad_user, grad_item, grad_gen, loss, workspace)
 
     grad_user = _grad_buffer("gar", "the tables' and the generator output's shapes", grad_user, user_table, want_user, False)
     grad_item = _grad_buffer("gar", "the tables' and the generator output's shapes", grad_item, item_table, want_item, False)
@@ -1425,13 +1440,9 @@ def gar(user_table: torch.Tensor, item_table: torch.Tensor, gen: torch.Tensor, p
     p = plan
     _lib.check(_lib.lib().crh_gar_f32(
         _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]), _lib.ptr(gen),
-        _lib.ptr(p["users"]), _lib.ptr(p["pos"]), _lib.ptr(p["neg"]), int(u_lo), int(u_hi), int(i_lo), int(i_hi),
-        _lib.ptr(p["item_ids"]), _lib.ptr(p["item_ptr"]), _lib.ptr(p["item_occ"]), _lib.ptr(p["item_chunk_ptr"]),
-        _lib.ptr(p["item_chunk_own"]), int(p["n_items"]), int(p["n_item_chunks"]), _lib.ptr(p["user_ids"]),
-        _lib.ptr(p["user_ptr"]), _lib.ptr(p["user_occ"]), _lib.ptr(p["user_chunk_ptr"]), _lib.ptr(p["user_chunk_own"]),
-        int(p["n_users"]), int(p["n_user_chunks"]), int(B), int(d), int(bool(cold_user)), float(alpha), float(beta),
-        float(reg), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item), _lib.ptr(grad_gen), _lib.ptr(loss),
-        _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_gar_f32")
+        _lib.ptr(p["users"]), _lib.ptr(p["pos"]), _lib.ptr(p["neg"]), *id_range, *_owner_args(p), int(B), int(d),
+        int(bool(cold_user)), float(alpha), float(beta), float(reg), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item),
+        _lib.ptr(grad_gen), _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_gar_f32")
     return loss, grad_user, grad_item, grad_gen
 
 
@@ -1446,8 +1457,7 @@ def mtpr_workspace_bytes(batch: int, d: int, cold_user: bool, n_items: int, n_us
 
 
 def mtpr_workspace(batch: int, d: int, cold_user: bool, n_items: int, n_users: int, device) -> torch.Tensor:
-    return torch.empty(max(mtpr_workspace_bytes(batch, d, cold_user, n_items, n_users), 1), dtype=torch.uint8,
-                       device=device)
+    return _new_workspace(mtpr_workspace_bytes(batch, d, cold_user, n_items, n_users), device)
 
 
 def mtpr_plan(users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_users: Optional[int] = None,
@@ -1483,10 +1493,8 @@ def mtpr(user_table: torch.Tensor, item_table: torch.Tensor, h: torch.Tensor, we
     if user_table.shape[1] != wp or item_table.shape[1] != wq or h.shape != (hr, d):
         raise RuntimeError("mtpr: item mode takes tables (nu, 2 d), (ni, d) and h (2 B, d); user mode (nu, d), (ni, 2 d) "
                            "and h (B, d), B the plan's batch")
-    _check_one_device("mtpr", "the tables'", dev, item_table, h, weu, wei, plan["users"], grad_user, grad_item, grad_h,
-                      grad_weu, grad_wei, loss, workspace)
-    (u_lo, u_hi), (i_lo, i_hi) = plan["user_range"], plan["item_range"]
-    _check_ids_in_tables("mtpr", "ids", (u_lo, u_hi), (i_lo, i_hi), user_table, item_table)
+    id_range = _triple_plan_checks("mtpr", plan, user_table, item_table, h, weu, wei, grad_user, grad_item, grad_h, grad_weu,
+                                   grad_wei, loss, workspace)
 
     what = "the shapes of the tables, the content rows and the projections"
     grad_user = _grad_buffer("mtpr", what, grad_user, user_table, want_user, False)
@@ -1499,13 +1507,10 @@ def mtpr(user_table: torch.Tensor, item_table: torch.Tensor, h: torch.Tensor, we
     p = plan
     _lib.check(_lib.lib().crh_mtpr_f32(
         _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]), _lib.ptr(h),
-        _lib.ptr(weu), _lib.ptr(wei), _lib.ptr(p["users"]), _lib.ptr(p["pos"]), _lib.ptr(p["neg"]), int(u_lo), int(u_hi),
-        int(i_lo), int(i_hi), _lib.ptr(p["item_ids"]), _lib.ptr(p["item_ptr"]), _lib.ptr(p["item_occ"]),
-        _lib.ptr(p["item_chunk_ptr"]), _lib.ptr(p["item_chunk_own"]), int(p["n_items"]), int(p["n_item_chunks"]),
-        _lib.ptr(p["user_ids"]), _lib.ptr(p["user_ptr"]), _lib.ptr(p["user_occ"]), _lib.ptr(p["user_chunk_ptr"]),
-        _lib.ptr(p["user_chunk_own"]), int(p["n_users"]), int(p["n_user_chunks"]), int(B), int(d), int(cold_user),
-        float(wd1), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item), _lib.ptr(grad_h), _lib.ptr(grad_weu),
-        _lib.ptr(grad_wei), _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_mtpr_f32")
+        _lib.ptr(weu), _lib.ptr(wei), _lib.ptr(p["users"]), _lib.ptr(p["pos"]), _lib.ptr(p["neg"]), *id_range,
+        *_owner_args(p), int(B), int(d), int(cold_user), float(wd1), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item),
+        _lib.ptr(grad_h), _lib.ptr(grad_weu), _lib.ptr(grad_wei), _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(),
+        _lib.current_stream()), "crh_mtpr_f32")
     return loss, grad_user, grad_item, grad_h, grad_weu, grad_wei
 
 
@@ -1520,8 +1525,7 @@ def vbpr_workspace_bytes(batch: int, d: int, cold_user: bool, n_items: int, n_us
 
 
 def vbpr_workspace(batch: int, d: int, cold_user: bool, n_items: int, n_users: int, device) -> torch.Tensor:
-    return torch.empty(max(vbpr_workspace_bytes(batch, d, cold_user, n_items, n_users), 1), dtype=torch.uint8,
-                       device=device)
+    return _new_workspace(vbpr_workspace_bytes(batch, d, cold_user, n_items, n_users), device)
 
 
 def vbpr_plan(users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_users: Optional[int] = None,
@@ -1566,10 +1570,8 @@ def vbpr(user_table: torch.Tensor, item_table: torch.Tensor, aux_table: torch.Te
             or (h_adv is not None and h_adv.shape != h.shape):
         raise RuntimeError("vbpr: item mode takes tables (nu, d), (ni, d), aux (nu, d) and h, h_adv (2 B, d); user mode aux "
                            "(ni, d) and h (B, d), B the plan's batch")
-    _check_one_device("vbpr", "the tables'", dev, item_table, aux_table, h, h_adv, plan["users"], grad_user, grad_item,
-                      grad_aux, grad_h, grad_h_adv, grad_hsum, loss, workspace)
-    (u_lo, u_hi), (i_lo, i_hi) = plan["user_range"], plan["item_range"]
-    _check_ids_in_tables("vbpr", "ids", (u_lo, u_hi), (i_lo, i_hi), user_table, item_table)
+    id_range = _triple_plan_checks("vbpr", plan, user_table, item_table, aux_table, h, h_adv, grad_user, grad_item, grad_aux,
+                                   grad_h, grad_h_adv, grad_hsum, loss, workspace)
 
     what = "the shapes of the tables and the content rows"
     grad_user = _grad_buffer("vbpr", what, grad_user, user_table, want_user, False)
@@ -1592,13 +1594,9 @@ def vbpr(user_table: torch.Tensor, item_table: torch.Tensor, aux_table: torch.Te
     _lib.check(_lib.lib().crh_vbpr_f32(
         _lib.ptr(user_table), int(user_table.shape[0]), _lib.ptr(item_table), int(item_table.shape[0]),
         _lib.ptr(aux_table), _lib.ptr(h), _lib.ptr(h_adv), _lib.ptr(p["users"]), _lib.ptr(p["pos"]), _lib.ptr(p["neg"]),
-        int(u_lo), int(u_hi), int(i_lo), int(i_hi), _lib.ptr(p["item_ids"]), _lib.ptr(p["item_ptr"]),
-        _lib.ptr(p["item_occ"]), _lib.ptr(p["item_chunk_ptr"]), _lib.ptr(p["item_chunk_own"]), int(p["n_items"]),
-        int(p["n_item_chunks"]), _lib.ptr(p["user_ids"]), _lib.ptr(p["user_ptr"]), _lib.ptr(p["user_occ"]),
-        _lib.ptr(p["user_chunk_ptr"]), _lib.ptr(p["user_chunk_own"]), int(p["n_users"]), int(p["n_user_chunks"]), int(B),
-        int(d), int(cold_user), float(wd1), float(lmd), float(scale), _lib.ptr(grad_user), _lib.ptr(grad_item),
-        _lib.ptr(grad_aux), _lib.ptr(grad_h), _lib.ptr(grad_h_adv), _lib.ptr(grad_hsum), _lib.ptr(loss),
-        _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_vbpr_f32")
+        *id_range, *_owner_args(p), int(B), int(d), int(cold_user), float(wd1), float(lmd), float(scale),
+        _lib.ptr(grad_user), _lib.ptr(grad_item), _lib.ptr(grad_aux), _lib.ptr(grad_h), _lib.ptr(grad_h_adv),
+        _lib.ptr(grad_hsum), _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_vbpr_f32")
     return loss, grad_user, grad_item, grad_aux, grad_h, grad_h_adv, grad_hsum
 
 
@@ -1629,7 +1627,7 @@ def ngcf_workspace_bytes(n_rows: int, d: int) -> int:
 
 def ngcf_workspace(n_rows: int, d: int, device) -> torch.Tensor:
     """Private scratch of one crh_ngcf_layer_bwd_f32 shape: the weight-gradient partials (at most 2048) and their sums."""
-    return torch.empty(max(ngcf_workspace_bytes(n_rows, d), 1), dtype=torch.uint8, device=device)
+    return _new_workspace(ngcf_workspace_bytes(n_rows, d), device)
 
 
 def _ngcf_checks(op: str, x: torch.Tensor, w: torch.Tensor, same_shape, others) -> None:
