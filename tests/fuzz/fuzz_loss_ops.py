@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Randomised parity fuzzing of the four fused loss kernels (csrc/clcrec.hip, csrc/ccfcrec.hip, csrc/aldi.hip,
-csrc/infonce.hip) against their float64 restatements (tests/clcrec_restate.py, tests/ccfcrec_restate.py,
-tests/aldi_restate.py, tests/infonce_restate.py).
+"""Randomised parity fuzzing of seven fused loss kernels (csrc/clcrec.hip, csrc/ccfcrec.hip, csrc/aldi.hip,
+csrc/infonce.hip, csrc/gar.hip, csrc/mtpr.hip, csrc/vbpr.hip) against their float64 restatements
+(tests/clcrec_restate.py, tests/ccfcrec_restate.py, tests/aldi_restate.py, tests/infonce_restate.py, and the three named
+below).
 
 CLCRec, CCFCRec, ALDI, per case: a width from every multiple of 4 in [4, 256], small B, G, P, N and S (now and then a batch long enough for an
 owner to split into chunks), an id pattern per id tensor from {uniform, a few hot ids, one owner}, a scale per table from
@@ -24,10 +25,21 @@ on pre-filled tables}.  Row ids are permutations (the op wants them unique).  Th
     max(8x the float32 restatement's rho, 1e-4); a row the restatement leaves all zero must be all zero;
   * a second, identical call bit-equal; every table row outside the batch untouched; scale (a power of two) + accumulate
     equal to pre + scale * g bit for bit.
+GAR, MTPR, VBPR (kinds ``gar``, ``mtpr``, ``vbpr``: csrc/gar.hip, csrc/mtpr.hip, csrc/vbpr.hip, which end in loss_common.h's
+owner pass; tests/gar_restate.py, tests/mtpr_restate.py, tests/vbpr_restate.py), per case: a width from every multiple of
+4 in [4, 256] (MTPR: [4, 128], its kernel's range; its tables are d and 2 d wide); B in [1, 100] and, in about one case in
+seven, B in [300, 700] with a ``hot`` or ``one`` pattern on every id tensor, so that owners split into chunks of 256; an id
+pattern per id tensor and a scale per table from the same sets (GAR: raw, G = tanh of a table; MTPR: its restatement's
+sizes times the scale; VBPR: rows sized so that a dot product is of order 4 x the two scales at every width); a mode
+(cold user or cold item; VBPR in item mode with or without h_adv); alpha, beta from {0, .., 1}, wd1 from {0, 0.01, 0.05},
+lmd from {0, 0.7, 1}; for GAR reg from {0, 1e-4, 1e-2, 1, B}.  Judged as the others, over the total as ALDI: against the
+float64 restatement with the case's bar 8x the float32 restatement's distance and no lower than the kernel file's fixed
+bars (LOSS_BAR / GRAD_BAR of tests/test_gar_gpu.py, tests/test_mtpr_gpu.py, tests/test_vbpr_gpu.py), every gradient the call
+returns (VBPR's grad_hsum among them; none where there is no h_adv); a second, identical call bit-equal.
 On a mismatch the seed and the drawn parameters are printed and the exit status is 1.  Without --only every case draws its
-kind from all four; with it, from the kinds named, in the order named.
+kind from all seven; with it, from the kinds named, in the order named.
 
-    python tests/fuzz/fuzz_loss_ops.py --cases 200 [--seed 0] [--only clcrec,ccfcrec,aldi,infonce]
+    python tests/fuzz/fuzz_loss_ops.py --cases 200 [--seed 0] [--only clcrec,ccfcrec,aldi,infonce,gar,mtpr,vbpr]
 """
 import argparse
 import os
@@ -39,9 +51,13 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from coldrec_amd import ops  # noqa: E402
-from tests import aldi_restate, ccfcrec_restate, clcrec_restate, infonce_restate  # noqa: E402
+from tests import aldi_restate, ccfcrec_restate, clcrec_restate, gar_restate, infonce_restate  # noqa: E402
+from tests import mtpr_restate, vbpr_restate  # noqa: E402
 from tests import test_aldi_gpu as ald  # noqa: E402
 from tests import test_ccfcrec_gpu as ccf  # noqa: E402
+from tests import test_gar_gpu as gar  # noqa: E402
+from tests import test_mtpr_gpu as mtpr  # noqa: E402
+from tests import test_vbpr_gpu as vbpr  # noqa: E402
 
 DEV = torch.device("cuda:0")
 SCALES = [0.05, 0.3, 1.5]
@@ -71,14 +87,18 @@ def table(rng, rows, d, scale):
 
 
 def distances(got, want, over_total=False):
-    """(worst loss-term error, worst gradient error / maximum) of (terms, g1, g2, g3) numpy tuples; the last term is the
-    total.  A gradient whose reference is all zero counts with its own largest entry."""
+    """(worst loss-term error, worst gradient error / maximum) of (terms, g1, g2, ...) numpy tuples; the last term is the
+    total.  A gradient whose reference is all zero counts with its own largest entry; one that is None on both sides is
+    skipped."""
     terms, ref = np.asarray(got[0], np.float64), np.asarray(want[0], np.float64)
     total = abs(ref[-1])
     den = total if over_total else np.maximum(np.abs(ref), 1e-6 * total)
     rel = float((np.abs(terms - ref) / den).max())
     errs = []
     for g, w in zip(got[1:], want[1:]):
+        if w is None:
+            assert g is None
+            continue
         g = np.asarray(g, np.float64)
         top = np.abs(w).max()
         errs.append(float(np.abs(g - w).max() / top) if top > 0 else float(np.abs(g).max()))
@@ -86,18 +106,23 @@ def distances(got, want, over_total=False):
 
 
 def judge(kind, params, fused, want, f32, fixed, over_total=False):
-    """``fused()`` -> (loss, g1, g2, g3) device tensors; called twice."""
+    """``fused()`` -> (loss, g1, g2, ...) device tensors, any number of gradients, a None where the call has none (the
+    restatement must have None there too); called twice."""
     a, b = fused(), fused()
     torch.cuda.synchronize()
-    if not all(torch.equal(x, y) for x, y in zip(a, b)):
+    if not all((x is None and y is None) or torch.equal(x, y) for x, y in zip(a, b)):
         fail(kind + ": two identical calls differ in their bits", **params)
-    got = tuple(t.cpu().numpy() for t in a)
-    if not all(np.isfinite(t).all() for t in got):
+    got = tuple(None if t is None else t.cpu().numpy() for t in a)
+    if len(got) != len(want) or any((g is None) != (w is None) for g, w in zip(got, want)):
+        fail(kind + ": the call and the restatement return different gradients", **params)
+    if not all(np.isfinite(t).all() for t in got if t is not None):
         fail(kind + ": output not finite", **params)
     ref_rel, ref_err = distances(f32, want, over_total)
     bars = (max(8 * ref_rel, fixed[0]), max(8 * ref_err, fixed[1]))
     rel, err = distances(got, want, over_total)
     for g, w in zip(got[1:], want[1:]):
+        if w is None:
+            continue
         zero = (w == 0).all(1)
         if g[zero].any():
             fail(kind + ": gradient not zero where the restatement's row is", **params)
@@ -279,7 +304,82 @@ def case_infonce(rng):
         fail("infonce against the float64 restatement", loss=rel, rho=rho, bars=bars, float32=(rel32, rho32), **params)
 
 
-KINDS = {"clcrec": case_clcrec, "ccfcrec": case_ccfcrec, "aldi": case_aldi, "infonce": case_infonce}
+def draw_triples(rng, d_max=256):
+    """What a case of the three (user, positive, negative) kernels starts from: (d, B, nu, ni, patterns, users, pos, neg).
+    B in [1, 100]; about one case in seven B in [300, 700] with hot or single ids, so that owners split into chunks.
+    neg != pos in every record, as a sampled negative is: an item met only in records with pos = neg has the gradient
+    +g - g, which autograd forms as s + (-s) = 0 exactly and no other summation order does."""
+    d = 4 * int(rng.integers(1, d_max // 4 + 1))
+    B, pool = int(rng.integers(1, 101)), PATTERNS
+    if rng.random() < 1 / 7:
+        B, pool = int(rng.integers(300, 701)), ["hot", "one"]
+    pats = tuple(str(rng.choice(pool)) for _ in range(3))
+    nu, ni = int(rng.integers(1, 30)), int(rng.integers(2, 60))
+    users, pos, neg = draw_ids(rng, nu, (B,), pats[0]), draw_ids(rng, ni, (B,), pats[1]), draw_ids(rng, ni, (B,), pats[2])
+    neg = torch.where(neg == pos, (pos + 1) % ni, neg)
+    return d, B, nu, ni, pats, users, pos, neg
+
+
+def case_gar(rng):
+    d, B, nu, ni, pats, users, pos, neg = draw_triples(rng)
+    su, sv, sg = (float(rng.choice(SCALES)) for _ in range(3))
+    cold_user = bool(rng.random() < 0.5)
+    alpha, beta = float(rng.choice([0.0, 0.05, 0.5, 1.0])), float(rng.choice([0.0, 0.1, 0.5, 1.0]))
+    reg = float(rng.choice([0.0, 1e-4, 1e-2, 1.0, float(B)]))
+    params = dict(d=d, B=B, nu=nu, ni=ni, scales=(su, sv, sg), ids=pats, cold_user=cold_user, coef=(alpha, beta, reg))
+    U, V = table(rng, nu, d, su), table(rng, ni, d, sv)
+    G = torch.tanh(table(rng, B, d, sg))                           # the generator ends in a tanh
+    inp = (U, V, users, pos, neg, G)
+    want = gar_restate.step(*inp, alpha, beta, reg, cold_user)
+    f32 = gar_restate.step(*inp, alpha, beta, reg, cold_user, dtype=torch.float32)
+    plan = ops.gar_plan(users.to(DEV), pos.to(DEV), neg.to(DEV), nu, ni)
+    dev = [t.to(DEV) for t in (U, V, G)]
+    judge("gar", params, lambda: ops.gar(*dev, plan, alpha, beta, reg, cold_user=cold_user), want, f32,
+          (gar.LOSS_BAR, gar.GRAD_BAR), over_total=True)
+
+
+def case_mtpr(rng):
+    d, B, nu, ni, pats, users, pos, neg = draw_triples(rng, d_max=128)     # MTPR's d <= 128: its tables are d and 2 d wide
+    st, sh, sw = (float(rng.choice(SCALES)) for _ in range(3))
+    cold_user = bool(rng.random() < 0.5)
+    wd1 = float(rng.choice([0.0, 0.01, 0.05]))
+    params = dict(d=d, B=B, nu=nu, ni=ni, scales=(st, sh, sw), ids=pats, cold_user=cold_user, wd1=wd1)
+    wp, wq, hr = (d, 2 * d, B) if cold_user else (2 * d, d, 2 * B)
+    # tests/mtpr_restate.py's sizes times the scale: rows of 0.5, projections xavier-sized
+    P, Q, h = table(rng, nu, wp, 0.5 * st), table(rng, ni, wq, 0.5 * st), table(rng, hr, d, 0.5 * sh)
+    weu, wei = table(rng, 2 * d, d, sw / d ** 0.5), table(rng, 2 * d, d, sw / d ** 0.5)
+    inp = (P, Q, h, weu, wei, users, pos, neg)
+    want = mtpr_restate.step(*inp, wd1, cold_user)
+    f32 = mtpr_restate.step(*inp, wd1, cold_user, dtype=torch.float32)
+    plan = ops.mtpr_plan(users.to(DEV), pos.to(DEV), neg.to(DEV), nu, ni)
+    dev = [t.to(DEV) for t in (P, Q, h, weu, wei)]
+    judge("mtpr", params, lambda: ops.mtpr(*dev, plan, wd1, cold_user=cold_user), want, f32, (mtpr.LOSS_BAR, mtpr.GRAD_BAR),
+          over_total=True)
+
+
+def case_vbpr(rng):
+    d, B, nu, ni, pats, users, pos, neg = draw_triples(rng)
+    st, sa, sh = (float(rng.choice(SCALES)) for _ in range(3))
+    cold_user = bool(rng.random() < 0.5)
+    adv = bool(not cold_user and rng.random() < 0.5)
+    wd1, lmd = float(rng.choice([0.0, 0.01, 0.05])), float(rng.choice([0.0, 0.7, 1.0]))
+    params = dict(d=d, B=B, nu=nu, ni=ni, scales=(st, sa, sh), ids=pats, cold_user=cold_user, h_adv=adv, wd1=wd1, lmd=lmd)
+    w = 2.0 * d ** -0.25                     # a dot product of two rows: of order 4 x the two scales at every width
+    P, Q = table(rng, nu, d, w * st), table(rng, ni, d, w * st)
+    A = table(rng, ni if cold_user else nu, d, w * sa)
+    h = table(rng, B if cold_user else 2 * B, d, w * sh)
+    h_adv = h + table(rng, h.shape[0], d, 0.1 * w * sh) if adv else None
+    inp = (P, Q, A, h, h_adv, users, pos, neg)
+    want = vbpr_restate.step(*inp, wd1, cold_user, lmd)
+    f32 = vbpr_restate.step(*inp, wd1, cold_user, lmd, dtype=torch.float32)
+    plan = ops.vbpr_plan(users.to(DEV), pos.to(DEV), neg.to(DEV), nu, ni)
+    dev = [None if t is None else t.to(DEV) for t in (P, Q, A, h, h_adv)]
+    judge("vbpr", params, lambda: ops.vbpr(*dev[:4], plan, wd1, h_adv=dev[4], lmd=lmd, cold_user=cold_user, want_hsum=True),
+          want, f32, (vbpr.LOSS_BAR, vbpr.GRAD_BAR), over_total=True)
+
+
+KINDS = {"clcrec": case_clcrec, "ccfcrec": case_ccfcrec, "aldi": case_aldi, "infonce": case_infonce, "gar": case_gar,
+         "mtpr": case_mtpr, "vbpr": case_vbpr}
 
 
 def main():

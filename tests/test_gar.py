@@ -9,7 +9,13 @@ Measured:
     float64 run against G24: loss terms 1.65e-7 (item) / 1.24e-7 (user) of the total; tables 1.15e-5 / 3.21e-6 (item: users /
         items) and 5.43e-7 / 1.39e-6 (user) of their scale;
     float32 run against G24: loss terms 8.81e-8 / 8.91e-8; tables 1.51e-5 / 1.46e-6 and 2.35e-7 / 2.34e-7;
-    the float32 restatement's lists: see test_float32_restatement_keeps_the_reference_lists_and_metrics.
+    the float32 restatement's lists: see test_float32_restatement_keeps_the_reference_lists_and_metrics;
+    float32 formula against float64 at the count cases of tests/test_owner_pass_gpu.py (tests/owner_cases.py: reg = B =
+        2746, thirteen widths, both modes): loss terms 1.05e-5 of the total at worst, gradients 2.15e-5 of their maximum
+        (both at d = 256: float32 torch's norm of a 2746 x 256 block); 1.5e-7 .. 2.2e-7 and 9e-7 at d = 4;
+    the mutated float64 restatements at those cases, least distance over the widths and modes, as gradient error over
+        the maximum: counts swapped 0.80, every occurrence counted as a positive 0.24, one occurrence of a three-chunk
+        owner miscounted 1.57e-3, R's part dropped on the user side 0.97 -- against 4 bars = 6.9e-4.
 On the MI355X the kernel measures what tests/test_gar_gpu.py's docstring records.
 """
 import argparse
@@ -20,6 +26,8 @@ import pytest
 import torch
 
 from tests import gar_restate
+from tests import owner_cases as oc
+from tests import test_owner_pass_gpu as op
 from tests.conftest import load_golden
 from tests.test_gar_gpu import (CASES, COEF, EDGE_F32_GRAD_WORST, EDGE_F32_LOSS_WORST, EDGE_GRAD_BAR, EDGE_LOSS_BAR,
                                 F32_GRAD_WORST, F32_LOSS_WORST, F32_RUN_LOSS, F32_RUN_TABLES, GRAD_BAR, IDS, LOSS_BAR,
@@ -210,6 +218,67 @@ def test_edge_inputs_are_the_edges_they_claim():
     for cold_user in MODES:                           # G = 0: no NaN out of the zero-norm block
         got = gar_restate.step(*edges["gen-zero"][0], *edges["gen-zero"][1], cold_user)
         assert all(np.isfinite(x).all() for x in got)
+
+
+# ---- the count cases of tests/test_owner_pass_gpu.py ---------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def count_measured():
+    """At the count cases (tests/owner_cases.py: reg = B, unequal block norms, per-item counts of positives at the window
+    and chunk edges), every width and both modes: {(d, mode): (loss err / total and [gradient err / max] of float32 torch,
+    {mutation: worst gradient err / max of the mutated float64 restatement}, the same of the unmutated written-out
+    form)}, computed once and printed.  On one thread: torch's multi-threaded CPU reductions change their order with the
+    machine, and the block norms here run over up to 2746 x 256 elements."""
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        return _count_measured()
+    finally:
+        torch.set_num_threads(threads)
+
+
+def _count_measured():
+    out = {}
+    for d in oc.WIDTHS:
+        inp, coef = oc.gar_count_inputs(d)
+        for cold_user in MODES:
+            true, mutated, written = oc.gar_mutations(inp, coef, cold_user)
+            assert all(np.isfinite(x).all() for x in true)
+            rel, errs = distances(gar_restate.step(*inp, *coef, cold_user, dtype=torch.float32), true)
+            far = {k: float(max(distances(m, true)[1])) for k, m in mutated.items()}
+            print(f"counts d{d} {'user' if cold_user else 'item'}: float32 torch: loss err / total {rel:.2e}, gradient err / "
+                  f"max {errs[0]:.2e} {errs[1]:.2e} {errs[2]:.2e}; mutated: " + ", ".join(f"{k} {v:.2e}" for k, v in far.items())
+                  + f"; R / total {true[0][2] / true[0][3]:.3f}")
+            out[(d, cold_user)] = (float(rel), [float(e) for e in errs], far, float(max(distances(written, true)[1])))
+    return out
+
+
+def test_count_cases_float32_figures_are_the_recorded_ones(count_measured):
+    """The measurement behind COUNT_LOSS_BAR / COUNT_GRAD_BAR of tests/test_owner_pass_gpu.py, repeated: float32 torch lies
+    within the bars (they are 8x its worst distance) and the recorded worst figures are the measured ones within a factor
+    of 2."""
+    worst = max(v[0] for v in count_measured.values()), max(max(v[1]) for v in count_measured.values())
+    print(f"worst over the count cases, both modes: loss err / total {worst[0]:.2e}, gradient err / max {worst[1]:.2e}")
+    for k, rec in enumerate((op.COUNT_F32_LOSS_WORST, op.COUNT_F32_GRAD_WORST)):
+        assert rec / 2 <= worst[k] <= 2 * rec, (k, worst[k], rec)
+    assert (op.COUNT_LOSS_BAR, op.COUNT_GRAD_BAR) == (8 * op.COUNT_F32_LOSS_WORST, 8 * op.COUNT_F32_GRAD_WORST)
+    assert worst[0] <= op.COUNT_LOSS_BAR and worst[1] <= op.COUNT_GRAD_BAR
+
+
+def test_count_cases_make_every_miscount_visible(count_measured):
+    """The condition of the count cases: the regulariser's part written out (factor x count x row) is the restatement's,
+    and with the counts swapped, every occurrence counted as a positive, one occurrence of a three-chunk owner miscounted,
+    or R's part dropped on the user side, the float64 gradients lie at least 4 bars from the true ones, at every width and
+    in both modes -- a kernel that got a count wrong could not pass tests/test_owner_pass_gpu.py."""
+    least = {}
+    for key, (_, _, far, written) in count_measured.items():
+        assert written <= 1e-12, key
+        assert set(far) == {"counts swapped", "all counted as positives", "one occurrence miscounted", "R dropped on the user side"}
+        for name, v in far.items():
+            assert v >= op.MUTATION_MARGIN * op.COUNT_GRAD_BAR, (key, name, v)
+            least[name] = min(least.get(name, v), v)
+    print("least over the widths and modes: " + ", ".join(f"{k} {v:.2e}" for k, v in least.items())
+          + f"; bar {op.COUNT_GRAD_BAR:.2e}, {op.MUTATION_MARGIN} bars {op.MUTATION_MARGIN * op.COUNT_GRAD_BAR:.2e}")
 
 
 # ---- whole runs against G24 --------------------------------------------------------------------------------------------
