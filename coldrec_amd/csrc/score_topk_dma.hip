@@ -67,12 +67,8 @@ __device__ __forceinline__ void mma_f32_hooked(f32x16 (&acc)[UW], const f32x4& c
 // ONE_TRIP (fp32, and the screen's fp16 pass): the candidate's list rides the first batch of LDS reads (fill, list, filter word: one
 // wait) and the insert works out of those registers -- at fp32 a candidate above its user's threshold does enter (no rounding ties), so the second round trip
 // of the two-step form (fill and list read again by the insert) is paid by nearly every event; on the unseeded public fp16 routes
-// most events end at the "cannot enter" test and the lean first batch wins (the round-5 measurement above).
-#ifdef CRH_DMA_TWO_TRIP                      // (variant build: the two-step form for fp32 too, tools/ab_lib.sh)
-constexpr bool DMA_ONE_TRIP_F32 = false;
-#else
-constexpr bool DMA_ONE_TRIP_F32 = true;
-#endif
+// most events end at the "cannot enter" test and the lean first batch wins (the round-5 measurement above): the fp16 d=256 kernel
+// keeps the two-step form.  (The two-step form at fp32: round 6, profiles/r06_one_trip_event_ab.log.)
 // The screen's MARGIN rule (round 19; ScoreArgs::margin).  A user's threshold is the tail of its list; once that tail
 // is an item (above CRH_MASKED_SCORE) it is max(tail, L[k-1] - M): k = the call's k (ScoreArgs::screen_k <= K'), M one value per call,
 // above twice every user's error bound, so a row below L[k-1] - M has an exact score below the k-th best exact one and need not enter
@@ -201,122 +197,54 @@ __device__ __forceinline__ void dma_candidate(float sc, int gi, bool bm_masked, 
 }
 
 // The event of the 16x16 form (the screen's pass), round 15.  It walks its eight user blocks by the masks the common path has just
-// computed; -DCRH_DMA_EVENT_REBALLOT (variant build, tools/ab_lib.sh) compares every block again, as before.
-#ifdef CRH_DMA_EVENT_REBALLOT
-constexpr bool DMA_EVENT_REBALLOT = true;
-#else
-constexpr bool DMA_EVENT_REBALLOT = false;
-#endif
+// computed (the form that compared every block again: round 15, profiles/r15_event_parts_ab.log, part 2a).
 // Its candidate takes the one-trip form of the fp32 kernels: the screen's lists are seeded and the threshold in the register is the
-// exact K'-th score, so a candidate above it enters unless it is rated, and the two-step form reads fill and list twice for it.
-#ifdef CRH_DMA_SCREEN_TWO_TRIP               // (variant build: the two-step form, as before round 15, tools/ab_lib.sh)
-constexpr bool DMA_SCREEN_ONE_TRIP = false;
-#else
-constexpr bool DMA_SCREEN_ONE_TRIP = true;
-#endif
+// exact K'-th score, so a candidate above it enters unless it is rated, and the two-step form reads fill and list twice for it
+// (the two-step form here: round 15, profiles/r15_event_parts_ab.log, part 2b).
 // MFMA shape of the screen's two launches (fp16 d=128; M16 of the kernel): v_mfma_f32_16x16x32_f16, which holds a higher clock on
-// this power-limited stream than 32x32x16 at the same cycles per flop (round 11).  The approximate scores differ in their last
-// bits (32 products per instruction instead of 16); the screen's certificate covers any fp32 accumulation order.
-#ifdef CRH_DMA_SCREEN_MFMA32                 // (variant build: the 32x32x16 form, tools/ab_lib.sh)
-constexpr bool DMA_SCREEN_M16 = false;
-#else
-constexpr bool DMA_SCREEN_M16 = true;
-#endif
-// The common path of the 16x16 form's tile body is placed by hand (round 16, body16 in the kernel): one explicit slot behind each of a
-// tile's 64 MFMAs.  -DCRH_DMA_M16_BODY_OLD (variant build, tools/ab_lib.sh) keeps the body that left the placement to hipcc's
-// sched_group_barrier pipelines.
-#ifdef CRH_DMA_M16_BODY_OLD
-constexpr bool DMA_M16_HOOKED = false;
-#else
-constexpr bool DMA_M16_HOOKED = true;
-#endif
-// Round 22 went through the listing of body16's common path.  Three steps, each with a switch that builds the form before it (variant
-// build, tools/ab_lib.sh):
-//   -DCRH_DMA_BODY_PADDED      the second pair of a block's maxima as two asm statements, and the counted fragment waits naming the
-//                              fragments they guard: hipcc pads each seam with an s_nop, twelve per tile.  Without it the pair is one
-//                              statement and the wait names nothing (the sched_barriers on both sides keep the MFMAs behind it)
-//   -DCRH_DMA_BODY_RECOMPUTE   the barrier group works out the fetch of tile j + 3 from j: clamped tile index, per-lane 64-bit addresses,
-//                              id slot and ring slot.  Without it the addresses are scalar bases carried from tile to tile plus a 32-bit
-//                              lane offset, the two LDS slots are carried offsets, the DMAs stand in gaps 0 - 2 and the state moves on
-//                              in the free gaps behind them, at most one vector and two scalar instructions each
-//   -DCRH_DMA_BODY_BRANCHY     the event inlined where it is tested and the trip's two bounds tested behind the bodies.  Without it the
-//                              event is marked unlikely and the tests are worked out (and pinned) in gaps of group 3
-#ifdef CRH_DMA_BODY_PADDED
-constexpr bool DMA_BODY_PADDED = true;
-#else
-constexpr bool DMA_BODY_PADDED = false;
-#endif
-#ifdef CRH_DMA_BODY_RECOMPUTE
-constexpr bool DMA_BODY_CARRY = false;
-#else
-constexpr bool DMA_BODY_CARRY = true;
-#endif
-// The second and the third are the COMPACTED kernel's alone (BODY_CARRY / BODY_STRAIGHT in the kernel).  In the uncompacted one each
-// of them measured slower than the form before it (a call without a bitmap: +2.2 and +1.9 ms per step, profiles/r22_body_ab.log):
-// with its events out of line and four more scalars alive across them hipcc reloads six times as many spilled SGPRs inside the loop.
-#ifdef CRH_DMA_BODY_BRANCHY
-constexpr bool DMA_BODY_STRAIGHT = false;
-#else
-constexpr bool DMA_BODY_STRAIGHT = true;
-#endif
+// this power-limited stream than 32x32x16 at the same cycles per flop.  The approximate scores differ in their last bits (32 products
+// per instruction instead of 16); the screen's certificate covers any fp32 accumulation order.  (The 32x32x16 form of these launches:
+// round 11, profiles/r11_mfma16_ab.log.)
+// The common path of the 16x16 form's tile body is placed by hand (body16 in the kernel): one explicit slot behind each of a tile's 64
+// MFMAs.  (The body that left the placement to hipcc's sched_group_barrier pipelines: round 16, profiles/r16_body_ab.log.)
+// Round 22 went through the listing of body16's common path; what ships:
+//   * the second pair of a block's maxima is one asm statement and the counted fragment waits name no register (the sched_barriers
+//     on both sides keep the MFMAs behind them).  As two statements, and with waits that name the fragments they guard, hipcc pads
+//     each seam with an s_nop, twelve per tile (that form: round 22, profiles/r22_body_ab.log, step B)
+//   * BODY_CARRY: the fetch of tile j + 3 is state carried from tile to tile -- scalar bases plus a 32-bit lane offset, the two LDS
+//     slots carried offsets; the DMAs stand in gaps 0 - 2 and the state moves on in the free gaps behind them, at most one vector and
+//     two scalar instructions each.  Without it the barrier group works the fetch out from j: clamped tile index, per-lane 64-bit
+//     addresses, id slot and ring slot
+//   * BODY_STRAIGHT: the event is marked unlikely and the trip's two bounds are worked out (and pinned) in gaps of group 3.  Without it
+//     the event is inlined where it is tested and the bounds are tested behind the bodies
+// The second and the third are the COMPACTED kernel's alone (BODY_CARRY = BODY_STRAIGHT = CM in the kernel), so both forms of that code
+// are live.  In the uncompacted one each of them measured slower than the form before it (a call without a bitmap: +2.2 and +1.9 ms per
+// step, profiles/r22_body_ab.log): with its events out of line and four more scalars alive across them hipcc reloads six times as many
+// spilled SGPRs inside the loop.
 // a test whose branch leaves the common path where `straight` (the kernel's BODY_STRAIGHT) holds
 #define CRH_DMA_BODY_RARE(straight, x) ((straight) ? __builtin_expect(!!(x), 0) : (long)!!(x))
-// What the 16x16 event executes was shortened once more in round 17; the protocol, the inserts and their order are the same.  Each
-// step has a switch that builds the form before it (variant build, tools/ab_lib.sh):
-//   -DCRH_DMA_EVENT_RUNTIME_K    K' read from the launch's arguments.  Without it the 16x16 kernels are compiled for K' = SCREEN_KP (only
-//                                the screen launches them): list addresses, the tail entry's lane and the fill tests are immediates
-//   -DCRH_DMA_EVENT_SLOT_TEST    the per-lane test `slot >= n_users`.  It never fires: a padding column's threshold is +inf from the start
-//                                and a dead wave's are all +inf (where `tau` is set up in the kernel), and an insert moves its own user's only
-//   -DCRH_DMA_EVENT_TAIL64       the per-candidate 64-bit test `item0 + row >= split_end`; without it the rows left in the selected tile
-//                                are one scalar per event
-//   -DCRH_DMA_EVENT_MASK8_SPLIT  gt_mask8 as eight asm statements
-// (Measured and not kept, round 17: the candidate's list reads -- fill, entry `lane` of scores and of ids -- issued by asm statements at
-// the head of its iteration, in flight under the score's select tree, the id and the hash, with the filter word behind them and one
-// wait in front of the first use.  Nothing at the headline, 202.77 against 202.67 ms per step, and +1.4 ms without a bitmap, 249.34
-// against 247.91: HISTORY.md, profiles/r17_event_steps_ab.log.)
-#ifdef CRH_DMA_EVENT_RUNTIME_K
-constexpr int DMA_EVENT_KC = 0;
-#else
-constexpr int DMA_EVENT_KC = SCREEN_KP;
-#endif
-#ifdef CRH_DMA_EVENT_SLOT_TEST
-constexpr bool DMA_EVENT_SLOT_TEST = true;
-#else
-constexpr bool DMA_EVENT_SLOT_TEST = false;
-#endif
-#ifdef CRH_DMA_EVENT_TAIL64
-constexpr bool DMA_EVENT_TAIL64 = true;
-#else
-constexpr bool DMA_EVENT_TAIL64 = false;
-#endif
-#ifdef CRH_DMA_EVENT_MASK8_SPLIT
-[[maybe_unused]] constexpr bool DMA_EVENT_MASK8_SPLIT = true;
-#else
-[[maybe_unused]] constexpr bool DMA_EVENT_MASK8_SPLIT = false;
-#endif
+// What the 16x16 event executes was shortened once more in round 17; the protocol, the inserts and their order are the same:
+//   * the 16x16 kernels are compiled for K' = SCREEN_KP (only the screen launches them; launch_score_dma refuses another k): list
+//     addresses, the tail entry's lane and the fill tests are immediates
+//   * no per-lane test `slot >= n_users`: a padding column's threshold is +inf from the start and a dead wave's are all +inf (where
+//     `tau` is set up in the kernel), and an insert moves its own user's only
+//   * the rows left in the selected tile are one scalar per event, not a 64-bit test `item0 + row >= split_end` per candidate
+//   * gt_mask8 is one asm statement
+// (each of the forms before: round 17, profiles/r17_event_steps_ab.log).
+// (Measured and not kept, round 17: the candidate's list reads issued by asm statements at the head of its iteration, in flight under
+// the score's select tree, the id and the hash, with one wait in front of the first use.  Nothing at the headline, 202.77 against
+// 202.67 ms per step, and +1.4 ms without a bitmap: HISTORY.md, profiles/r17_event_steps_ab.log.)
 // Round 18, the FULL-LIST form of the 16x16 event.  While the kernel's prologue copies the seeds, each wave works out one wave-uniform
 // flag: every live user slot of the wave holds K' entries.  Lists only grow, so the flag holds for the launch; in the screened route
 // it is set by every seeded call (the prefix stage ranks a masked item at -1e9 under its own id, so a seed list is full whenever the
-// prefix holds K' rows: its tail may be masked, its threshold -inf).  With the flag set the event takes dma_candidate_full below;
-// with it clear (an unseeded call, a seed list that is short all the same, K' read at run time) the event of round 17 runs.
-// Two steps, each with a switch that builds the form before it (variant build, tools/ab_lib.sh):
-//   -DCRH_DMA_EVENT_NO_FULL      no flag and no second form at all (the parent's kernels)
-//   -DCRH_DMA_EVENT_NO_STRAIGHT  no straight-line dispatch: a hit block with one hit lane and one row walks the two loops as well
+// prefix holds K' rows: its tail may be masked, its threshold -inf).  With the flag set the event takes dma_candidate_full below, and
+// a hit block with one hit lane and one row runs its candidate with no loop; with it clear (an unseeded call, a seed list that is
+// short all the same) the event of round 17 runs.  (The kernels without the flag, and the full-list form without the straight-line
+// dispatch: round 18, profiles/r18_event_steps_ab.log.)
 // (Measured and not kept, round 18: the full-list form WITHOUT the tail pre-test -- "cannot enter" read off the placing compare as
-// p == K', taken in front of the filter, a second compare only for a masked candidate.  It drops two v_readlane and a scalar
-// crh_better per candidate and ran SLOWER on the same box: +0.96 ms per step at the headline on top of the full-list form alone,
-// +0.22 ms on top of both steps that ship, +0.1 / +0.6 ms without a bitmap (inside the spreads); HISTORY.md,
+// p == K', a second compare only for a masked candidate.  It drops two v_readlane and a scalar crh_better per candidate and ran SLOWER
+// on the same box, +0.96 ms per step at the headline on top of the full-list form alone; HISTORY.md,
 // profiles/r18_event_steps_ab.log.  Why is not measured.)
-#ifdef CRH_DMA_EVENT_NO_FULL
-constexpr bool DMA_EVENT_FULL = false;
-#else
-constexpr bool DMA_EVENT_FULL = DMA_EVENT_KC != 0 && DMA_SCREEN_ONE_TRIP;
-#endif
-#ifdef CRH_DMA_EVENT_NO_STRAIGHT
-constexpr bool DMA_EVENT_STRAIGHT = false;
-#else
-constexpr bool DMA_EVENT_STRAIGHT = true;
-#endif
 // dma_candidate<true, true> for a list that is full (K = the compile-time K'): lane l < K holds entry l, an item; there is no fill to
 // read, test or write, and the user's new K-th entry is the old (K-1)-th or the candidate.  The order -- "cannot enter", filter,
 // insert -- and what each outcome writes are dma_candidate's with n = K.
@@ -408,36 +336,16 @@ __device__ __forceinline__ void tile_slow_path_dma(const f32x16& acc, float& tau
 // The same event for the 16x16x32 form (M16 below): acc = the two 16x16 accumulators of one block of 16 users, element 4 mb + r of
 // lane (c = lane & 15, g = lane >> 4) = tile row 16 mb + 4 g + r for user column c; all four g-lanes of a user hold its threshold.
 typedef float f32x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ float max8(const f32x8& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    float a0, a1, a2, r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(a0) : "v"(v[0]), "v"(v[1]), "v"(v[2]));
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(a1) : "v"(v[3]), "v"(v[4]), "v"(v[5]));
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(a2) : "v"(v[6]), "v"(v[7]), "v"(a0));
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a1), "v"(a2));
-    return r;
-#else
-    return fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
-#endif
-}
-__device__ __forceinline__ float acc_max(const f32x8& v) { return max8(v); }
-__device__ __forceinline__ float acc_max(const f32x16& v) { return max16(v); }
 __device__ __forceinline__ unsigned gt_mask8(const f32x8& v, float t) {   // as gt_mask16
     unsigned m = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (DMA_EVENT_MASK8_SPLIT) {
-#pragma unroll
-        for (int r = 7; r >= 0; --r)
-            asm("v_cmp_gt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m) : "v"(v[r]), "v"(t) : "vcc");
-    } else {
-        // one statement (round 17): behind each of eight separate ones hipcc puts an s_nop, 24 instructions where these 16 do
+    // one statement (round 17): behind each of eight separate ones hipcc puts an s_nop, 24 instructions where these 16 do
 #define CRH_GT8(R) "v_cmp_gt_f32 vcc, %" #R ", %9\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
-        asm(CRH_GT8(8) CRH_GT8(7) CRH_GT8(6) CRH_GT8(5) CRH_GT8(4) CRH_GT8(3) CRH_GT8(2) "v_cmp_gt_f32 vcc, %1, %9\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc"
-            : "+v"(m)
-            : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(t)
-            : "vcc");
+    asm(CRH_GT8(8) CRH_GT8(7) CRH_GT8(6) CRH_GT8(5) CRH_GT8(4) CRH_GT8(3) CRH_GT8(2) "v_cmp_gt_f32 vcc, %1, %9\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc"
+        : "+v"(m)
+        : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(t)
+        : "vcc");
 #undef CRH_GT8
-    }
 #endif
     return m;
 }
@@ -450,16 +358,16 @@ __device__ __forceinline__ float pick8u(const f32x8& v, int r) {
     const float q0 = b1 ? p1 : p0, q1 = b1 ? p3 : p2;
     return b2 ? q1 : q0;
 }
-// KC = the compile-time K' (0: K is the launch's); rows_left = the rows of the selected tile inside the cut, 1 .. 32, and gi0 = the id
-// of its row 0 (stream in id order), both worked out once per event by the caller.
+// Compiled for K' = SCREEN_KP.  rows_left = the rows of the selected tile inside the cut, 1 .. 32 (the clamped last tile of a cut holds
+// fewer), and gi0 = the id of its row 0 (stream in id order), both worked out once per event by the caller.
 // FULL = the wave's lists are all full (round 18): the candidates take dma_candidate_full, and a block with ONE hit lane that holds ONE
 // row -- every event of the sparse part of the stream -- runs its candidate straight, with neither loop's header, back edge and zero test.
-template <bool CM, int KC, bool FULL = false>
-__device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& tau_reg, float* ls, int* li, int* cnt, int Krt, int ucol0,
-                                                     int64_t slot0, const ScoreArgs& a, int64_t item0, int64_t split_end, int rows_left,
-                                                     int gi0, int lane, unsigned tb, const unsigned* rfilter, int idv, float margin, bool rt CRH_TRIP_PARAM) {
-    static_assert(!FULL || KC != 0, "the full-list form is compiled for K'");
-    const int K = KC ? KC : Krt;
+// No lane is tested for `slot0 + column < n_users`: the thresholds of padding columns and dead waves are +inf (see `tau` in the kernel).
+template <bool CM, bool FULL>
+__device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& tau_reg, float* ls, int* li, int* cnt, int ucol0,
+                                                     int64_t slot0, const ScoreArgs& a, int rows_left, int gi0, int lane, unsigned tb,
+                                                     const unsigned* rfilter, int idv, float margin, bool rt CRH_TRIP_PARAM) {
+    constexpr int K = SCREEN_KP;
     unsigned cm = gt_mask8(acc, tau_reg);
     unsigned m8 = 0u;                                             // masked rows of this lane, as in the 32x32 form
     if (tb != 0u && __ballot(tau_reg < 0.0f) != 0ull) {           // wave-uniform
@@ -475,24 +383,17 @@ __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& ta
         const int64_t slot = slot0 + jl;
         const int ul = ucol0 + jl;
         const int row = 16 * (r >> 2) + 4 * g + (r & 3);
-        const int64_t il = item0 + row;
-        // clamped duplicate rows of the tail tile
-        if constexpr (DMA_EVENT_TAIL64) {
-            if (il >= split_end) return;
-        } else {
-            if (row >= rows_left) return;
-        }
+        if (row >= rows_left) return;   // clamped duplicate rows of the tail tile
         const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pick8u(acc, r)), L));
         int gi;
         if constexpr (CM) gi = __builtin_amdgcn_readlane(idv, row);
-        else if constexpr (DMA_EVENT_TAIL64) gi = (int)(a.item_base + il);
         else gi = gi0 + row;
         if constexpr (FULL)
-            dma_candidate_full<KC, CM>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin, rt CRH_TRIP_ARG);
+            dma_candidate_full<K, CM>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin, rt CRH_TRIP_ARG);
         else
-            dma_candidate<DMA_SCREEN_ONE_TRIP, true, true, CM>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin, rt CRH_TRIP_ARG);
+            dma_candidate<true, true, true, CM>(sc, gi, (bmL >> r) & 1u, ul, slot, ls, li, cnt, K, a, lane, rfilter, (lane & 15) == jl, tau_reg, margin, rt CRH_TRIP_ARG);
     };
-    if constexpr (FULL && DMA_EVENT_STRAIGHT && !DMA_EVENT_SLOT_TEST) {
+    if constexpr (FULL) {
         // (one s_bcnt1 and a compare.  Not `lanes & (lanes - 1)`: under a bitmap the masked rows may have left no hit lane at all)
         if (__popcll(lanes) == 1) {
             const int L = __builtin_ctzll(lanes);
@@ -508,9 +409,6 @@ __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& ta
         lanes &= lanes - 1;
         unsigned cmL = __builtin_amdgcn_readlane(cm, L);
         const unsigned bmL = __builtin_amdgcn_readlane(bm, L);
-        if constexpr (DMA_EVENT_SLOT_TEST) {
-            if (slot0 + (L & 15) >= a.n_users) continue;
-        }
         while (cmL) {
             const int r = __builtin_ctz(cmL);
             cmL &= cmL - 1;
@@ -581,11 +479,11 @@ __device__ __forceinline__ void tile_slow_path_dma16(const f32x8& acc, float& ta
 //     the barrier and the DMA issue in group 1, the compares and the events behind group 2.  (An event reads registers, the id
 //     slots and the tile bits of tile j-1, all of which outlive body j: its place inside the body is free.)
 //   * since round 16 the common path of this form is `body16` below, placed by hand: one explicit slot behind each MFMA, body 0
-//     peeled out of the loop, `live` folded into the thresholds, the ring slot taken from the tile counter.  `body` with M16 is what
-//     -DCRH_DMA_M16_BODY_OLD builds: it asks hipcc for the same spread by sched_group_barrier pipelines, which do not count the
-//     inline-asm maxima as VALU -- in its listing four maxima stand in front of group 0's first MFMA, eight gaps carry four each,
-//     the second half of group 2 and all of group 3 are bare, and the loop edge, the ring-slot chain through a spilled SGPR and the
-//     tail's `j > 0` / `live` tests (about 25 instructions per tile) stand between the groups, hidden by no MFMA.
+//     peeled out of the loop, `live` folded into the thresholds, the ring slot taken from the tile counter.  `body` is the 32x32
+//     forms' alone.  (Until round 16 it built this form too and asked hipcc for the same spread by sched_group_barrier pipelines,
+//     which do not count the inline-asm maxima as VALU: four maxima stood in front of group 0's first MFMA, the second half of group 2
+//     and all of group 3 were bare, and about 25 instructions per tile stood between the groups, hidden by no MFMA.  That body is in
+//     history at round 16, profiles/r16_body_ab.log.)
 // The approximate scores differ from the 32x32 form's in their last bits (another accumulation order); the screen's results do not
 // (stage 2 rescores, and its bound covers any fp32 accumulation order).  The public fp16 routes never run this kernel at d=128.
 template <typename T, int D, int R, bool FL, bool CM = false, bool M16 = false>
@@ -608,7 +506,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     constexpr int GR = 2, NG = NCH / GR;               // A fragments are read in groups of GR chunks, one group ahead
     constexpr int BG = NG / 2 - 1;                     // the group in front of which the ring barrier sits
     constexpr int TG = M16 ? 2 : 1;                    // the group behind which tile j-1's threshold test (and its events) sits
-    constexpr bool BODY_CARRY = DMA_BODY_CARRY && CM, BODY_STRAIGHT = DMA_BODY_STRAIGHT && CM;   // round 22, see the switches above
+    constexpr bool BODY_CARRY = CM, BODY_STRAIGHT = CM;   // round 22: both steps measured slower in the uncompacted kernel (see above)
     static_assert(NCH % NW == 0 && NG % 4 == 0 && BG + 2 < NG, "row width not supported by the DMA kernel");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -619,8 +517,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     const int64_t ug_raw = (int64_t)(blockIdx.x / S) * NW + wave;
     const bool live = ug_raw < a.n_ugroups;            // a dead wave still fetches and synchronises
     const int64_t ug = live ? ug_raw : a.n_ugroups - 1;
-    constexpr int KC = M16 ? DMA_EVENT_KC : 0;          // the 16x16 form is compiled for the screen's K' (launch_score_dma checks a.k)
-    const int K = KC ? KC : a.k;
+    const int K = M16 ? SCREEN_KP : a.k;                // the 16x16 form is compiled for the screen's K' (launch_score_dma checks a.k)
     const int i = lane & (M16 ? 15 : 31), h = lane >> (M16 ? 4 : 5);   // user column in its block, k-group (M16: c and g of the 16x16x32 layout)
     // the screen's launches (fp16 d=128, both MFMA shapes; the public fp16 d=128 calls take another kernel): the margin rule of
     // dma_new_tau
@@ -672,8 +569,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     // M16, round 18: every live slot of this wave holds K entries (wave-uniform; lists only grow, so it holds for the launch).  The loop
     // below ends at the first padding slot: padding slots stay empty and do not count -- their thresholds are +inf, no candidate is
     // ever theirs.  (A dead wave copies the lists of the call's last group and takes no event at all.)
-    constexpr bool FULL_FORM = M16 && KC != 0 && DMA_EVENT_FULL;
-    [[maybe_unused]] int lists_full = FULL_FORM && a.seed_score != nullptr ? 1 : 0;
+    [[maybe_unused]] int lists_full = M16 && a.seed_score != nullptr ? 1 : 0;
     if (a.seed_score) {
         // seeded lists: copy each slot's prefix top-k into LDS; its fill = the entries before the padding
         for (int j = 0; j < UPW; ++j) {
@@ -691,7 +587,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 n += __popcll(__ballot(gi != CRH_PAD_IDX));
             }
             if (lane == 0) cnt[j] = n;
-            if constexpr (FULL_FORM) lists_full &= n == K ? 1 : 0;
+            if constexpr (M16) lists_full &= n == K ? 1 : 0;
         }
     }
     // ---- membership filters of the rated lists (192 bits per user, ids of this split's range only)
@@ -742,10 +638,10 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
             if constexpr (Elem<T>::kSwap) chunk_swap(b[q][u]);
         }
     }
-    // the hooked 16x16 body tests no `live` per tile: a dead wave walks, synchronises and fetches like any other, and with +inf for
+    // the 16x16 body tests no `live` per tile: a dead wave walks, synchronises and fetches like any other, and with +inf for
     // every threshold none of its maxima is a hit (it has no list to insert into and stores nothing).  The event relies on it as well:
     // it has no test of its own that would keep a dead wave's lanes out
-    if constexpr (M16 && DMA_M16_HOOKED) {
+    if constexpr (M16) {
         if (!live) {
 #pragma unroll
             for (int u = 0; u < NU; ++u) tau[u] = __builtin_inff();
@@ -941,25 +837,24 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     };
 #endif
     // M16: the event of user block u at tile ts, in the form the wave's flag selects -- one scalar branch per event
-    auto event16 = [&](const AccT& v, float& tau_u, int u, int64_t ts, int rows_left, int gi0, unsigned tb, int idv, bool rt) __attribute__((always_inline)) {
+    // (the other forms never take it, but they parse it)
+    auto event16 = [&](const AccT& v, float& tau_u, int u, int rows_left, int gi0, unsigned tb, int idv, bool rt) __attribute__((always_inline)) {
         if constexpr (M16) {
-            if constexpr (FULL_FORM) {
-                if (lists_full) {
-                    tile_slow_path_dma16<CM, KC, true>(v, tau_u, ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, rows_left, gi0,
-                                                       lane, tb, rfilter, idv, margin, rt CRH_TRIP_ARG);
-                    return;
-                }
-            }
-            tile_slow_path_dma16<CM, KC>(v, tau_u, ls, li, cnt, K, UB * u, slot0w + UB * u, a, ts << 5, split_end, rows_left, gi0, lane, tb,
-                                         rfilter, idv, margin, rt CRH_TRIP_ARG);
+            if (lists_full)
+                tile_slow_path_dma16<CM, true>(v, tau_u, ls, li, cnt, UB * u, slot0w + UB * u, a, rows_left, gi0, lane, tb, rfilter, idv,
+                                               margin, rt CRH_TRIP_ARG);
+            else
+                tile_slow_path_dma16<CM, false>(v, tau_u, ls, li, cnt, UB * u, slot0w + UB * u, a, rows_left, gi0, lane, tb, rfilter, idv,
+                                                margin, rt CRH_TRIP_ARG);
         }
     };
-    // body j: MFMAs of tile j (ring slot s_cur) into accumulator set P, threshold test of tile j-1 out of set 1-P;
+    // body j of the 32x32 forms: MFMAs of tile j (ring slot s_cur) into accumulator set P, threshold test of tile j-1 out of set 1-P;
     // s_nxt = slot of tile j+1, s_fill = slot of tile j + PF (barrier form: the slot tile j-1 left)
     auto body = [&](auto Pc, int j, int s_cur, int s_nxt, int s_fill) __attribute__((always_inline)) {
+        // (the 16x16 kernels never call it, but they parse it: what takes the 32x32 accumulators stands under !M16)
+        static_assert(!M16 || sizeof(Pc) == 0, "the 16x16 kernels run body16");
         constexpr int P = decltype(Pc)::value, Q = 1 - P;
         const uint32_t src = ring_lds + s_cur * TILE_B, srcn = ring_lds + s_nxt * TILE_B;
-        float m[NU];
         // one group of GR chunks; g is a compile-time constant (every register array below is indexed statically)
         auto group = [&](auto Gc) __attribute__((always_inline)) {
             constexpr int g = decltype(Gc)::value;
@@ -988,14 +883,12 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 dma_tile(j + 3, s_fill);
                 // one DMA instruction and a few of its address instructions per MFMA gap instead of all of them in one gap
                 // (+0.9 % on the same box: a single wave per SIMD hides about five issue slots per MFMA, not twenty)
-                // (M16: a 16-cycle MFMA hides two instructions, not six: one scalar and one vector address instruction per gap, the
-                // DMAs wherever their addresses are ready)
 #pragma unroll
-                for (int q = 0; q < (M16 ? 16 : 8); ++q) {
+                for (int q = 0; q < 8; ++q) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x004, M16 ? 1 : 2, 0);   // SALU
+                    __builtin_amdgcn_sched_group_barrier(0x004, 2, 0);   // SALU
                     __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // VALU
-                    if constexpr (!M16) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read (the DMA)
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read (the DMA)
                 }
             }
             if constexpr (FL) {
@@ -1038,28 +931,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                         (mma_f32_hooked<UW, JJ * 4 * UW>(acc[P], c[g & 3][JJ], b[g * GR + JJ], hook), ...);
                     }(std::make_integer_sequence<int, GR>{});
                 }
-            } else if constexpr (M16) {
-                // k-step g: each of the two fragments (item halves) feeds the 8 independent MFMAs over the user blocks -- 16 MFMAs of 16
-                // cycles, the 256 matrix-pipe cycles of a group of the 32x32 form
-                if constexpr (g == 0) {
-#pragma unroll
-                    for (int u = 0; u < NU; ++u)
-#pragma unroll
-                        for (int r = 0; r < NR; ++r) acc[P][u][r] = 0.0f;
-                }
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) {
-                    const f16x8 ca = __builtin_bit_cast(f16x8, c[g & 3][mb]);
-#pragma unroll
-                    for (int u = 0; u < NU; ++u) {
-                        AccT& x = acc[P][u];
-                        f32x4 t = mb ? f32x4{x[4], x[5], x[6], x[7]} : f32x4{x[0], x[1], x[2], x[3]};
-                        t = __builtin_amdgcn_mfma_f32_16x16x32_f16(ca, __builtin_bit_cast(f16x8, b[g][u]), t, 0, 0, 0);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) x[4 * mb + r] = t[r];
-                    }
-                }
-            } else {
+            } else if constexpr (!M16) {
 #pragma unroll
                 for (int jj = 0; jj < GR; ++jj) {
                     if constexpr (g == 0) {
@@ -1073,81 +945,46 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                     Elem<T>::template mma<UW>(acc[P], c[g & 3][jj], b[g * GR + jj]);
                 }
             }
-            // the maxima of tile j-1's accumulators.  M16 (the old body; body16 places them by hand): a 16-cycle MFMA hides two instructions
-            // where a 32-cycle one hides six, so the test is spread over three groups -- the maxima in group 0 (two per MFMA are asked
-            // for; the pipeline below does not see the asm statements as VALU, and hipcc puts up to four into a gap and four in front
-            // of the group), the barrier and the DMA issue in group 1 as ever, the compares and the event in group 2 (TG)
-            if constexpr (M16 && g == 0) {
+            if constexpr (!M16) {
+                // the maxima of tile j-1's accumulators: computed and tested in the same group (NU = UW user blocks in the 32x32 forms)
+                float m[NU];
+                if constexpr (g == TG) {
 #pragma unroll
-                for (int u = 0; u < NU; ++u) m[u] = acc_max(acc[Q][u]);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // VALU
+                    for (int u = 0; u < UW; ++u) m[u] = max16(acc[Q][u]);
                 }
-            }
-            if constexpr (!M16 && g == 1) {
-#pragma unroll
-                for (int u = 0; u < UW; ++u) m[u] = acc_max(acc[Q][u]);
-            }
-            unsigned long long hitm = 0ull;
-            unsigned long long hitb[NU];         // M16: the blocks' own masks, kept for the event (which used to compare again)
-            if constexpr (M16 && g == TG) {      // the compares ride the group's MFMAs too (behind them they are paid in full)
-#pragma unroll
-                for (int u = 0; u < NU; ++u) {
-                    hitb[u] = __ballot(m[u] > tau[u]);
-                    hitm |= hitb[u];
-                }
-#pragma unroll
-                for (int q = 0; q < NU; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // VALU
-                    __builtin_amdgcn_sched_group_barrier(0x004, 1, 0);   // SALU
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (g == TG) {
-                // four compares straight into scalar masks (OR-ed per lane first, the ballot of the result was a select and a second
-                // compare: two VALU instructions per tile beside MFMAs that hide none)
-                if constexpr (!M16) {
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (g == TG) {
+                    // four compares straight into scalar masks (OR-ed per lane first, the ballot of the result was a select and a second
+                    // compare: two VALU instructions per tile beside MFMAs that hide none)
+                    unsigned long long hitm = 0ull;
 #pragma unroll
                     for (int u = 0; u < UW; ++u) hitm |= __ballot(m[u] > tau[u]);
-                }
-                if (hitm != 0ull && live && j > 0 && !(CRH_ABLATE(a.ablate) & 1)) {
+                    if (hitm != 0ull && live && j > 0 && !(CRH_ABLATE(a.ablate) & 1)) {
 #ifdef CRH_PROFILE
-                    const unsigned long long ev_t0 = a.wave_clock != nullptr ? __builtin_amdgcn_s_memtime() : 0ull;
+                        const unsigned long long ev_t0 = a.wave_clock != nullptr ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
-                    const int64_t ts = t0 + j - 1;                                      // the tile being selected
-                    const unsigned tb = has_bits ? tbits[((ts >> 6) & 1) * 64 + (ts & 63)] : 0u;
-                    int idv = 0;                     // CM: the selected tile's ids, one LDS read per event (where tb's was)
-                    if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
-                    // CM: the wave's bit of the tile's rated-tile flags, read with the ids (wave-uniform)
-                    bool rt = false;
-                    if constexpr (CM) rt = (__builtin_amdgcn_readfirstlane(rtiles[(int)((ts >> 9) & 1) * 64 + (int)((ts >> 3) & 63)]) >> (4 * (int)(ts & 7) + wave)) & 1u;
-                    // M16: the rows of the selected tile inside the cut (the clamped last tile of a cut holds fewer than 32) and the id of
-                    // its first row, once per event
-                    const int64_t rl64 = split_end - (ts << 5);
-                    const int rows_left = rl64 < 32 ? (int)rl64 : 32;
-                    const int gi0 = (int)(a.item_base + (ts << 5));
+                        const int64_t ts = t0 + j - 1;                                      // the tile being selected
+                        const unsigned tb = has_bits ? tbits[((ts >> 6) & 1) * 64 + (ts & 63)] : 0u;
+                        int idv = 0;                     // CM: the selected tile's ids, one LDS read per event (where tb's was)
+                        if constexpr (CM) idv = (int)tbits[((j - 1) & (IDS_SLOTS - 1)) * 32 + (lane & 31)];
+                        // CM: the wave's bit of the tile's rated-tile flags, read with the ids (wave-uniform)
+                        bool rt = false;
+                        if constexpr (CM) rt = (__builtin_amdgcn_readfirstlane(rtiles[(int)((ts >> 9) & 1) * 64 + (int)((ts >> 3) & 63)]) >> (4 * (int)(ts & 7) + wave)) & 1u;
 #pragma unroll
-                    for (int u = 0; u < NU; ++u)
-                        // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
-                        if ((M16 && !DMA_EVENT_REBALLOT) ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull) {
-                            if constexpr (M16)
-                                event16(acc[Q][u], tau[u], u, ts, rows_left, gi0, tb, idv, rt);
-                            else
-                                tile_slow_path_dma<sizeof(T) == 4 && DMA_ONE_TRIP_F32, CM, MG>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a,
-                                                                                                ts << 5, split_end, lane, tb, rfilter, idv, margin, rt CRH_TRIP_ARG);
-                        }
-                    // the list stores of the inserts are drained HERE: left pending, the compiler parks an lgkmcnt(0) at a
-                    // later point of the common path, right behind the fragment reads of the barrier group
-                    __builtin_amdgcn_s_waitcnt(0xc07f);
+                        for (int u = 0; u < UW; ++u)
+                            if (__ballot(m[u] > tau[u]) != 0ull)
+                                tile_slow_path_dma<sizeof(T) == 4, CM, MG>(acc[Q][u], tau[u], ls, li, cnt, K, 32 * u, slot0w + 32 * u, a, ts << 5, split_end,
+                                                                           lane, tb, rfilter, idv, margin, rt CRH_TRIP_ARG);
+                        // the list stores of the inserts are drained HERE: left pending, the compiler parks an lgkmcnt(0) at a
+                        // later point of the common path, right behind the fragment reads of the barrier group
+                        __builtin_amdgcn_s_waitcnt(0xc07f);
 #ifdef CRH_PROFILE
-                    if (a.wave_clock != nullptr) {      // CRH_SCORE_TIMING: cycles spent in events and their number, per wave
-                        ev_ticks += __builtin_amdgcn_s_memtime() - ev_t0;
-                        ev_count += 1;
-                    }
+                        if (a.wave_clock != nullptr) {      // CRH_SCORE_TIMING: cycles spent in events and their number, per wave
+                            ev_ticks += __builtin_amdgcn_s_memtime() - ev_t0;
+                            ev_count += 1;
+                        }
 #endif
+                    }
                 }
             }
         };
@@ -1189,11 +1026,11 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
     [[maybe_unused]] int f_jl = 0;          // body j moves the bases on while j < f_jl: tile t0 + j + 3 is not yet the stream's last
     [[maybe_unused]] unsigned tb_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned*)tbits;
     [[maybe_unused]] unsigned lane4 = (unsigned)lane * 4u, lane16 = (unsigned)lane * 16u;
-    // DMA_BODY_STRAIGHT: what the branch behind a body tests, worked out and pinned in a gap of its group 3.  Behind the odd body: the
+    // BODY_STRAIGHT: what the branch behind a body tests, worked out and pinned in a gap of its group 3.  Behind the odd body: the
     // trip head has something to do or the stream has ended; behind the even body: the stream has ended
     [[maybe_unused]] int trip_rare = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (M16 && DMA_M16_HOOKED && BODY_CARRY) {
+    if constexpr (M16 && BODY_CARRY) {
         asm volatile("" : "+v"(lane4));      // (opaque: one register each for the launch, not a shift per use nor a folded 64-bit pointer;
         asm volatile("" : "+v"(lane16));     // tb_lds: one scalar add per M0, where the symbol's address plus an offset is two)
         asm volatile("" : "+s"(tb_lds));
@@ -1220,9 +1057,9 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
         constexpr bool FIRST = decltype(Fc)::value;
         constexpr int LA = P ? 0 : TILE_B;      // tile j+1 from ring_a: the even body's partner slot, the odd body's moved-on base
         static_assert(CPW == 2 || !M16, "two pieces per wave");
-        float m[NU], a0[NU], a1[NU], a2[NU];
+        float m[NU], a0[NU], a1[NU];
         unsigned long long hitm = 0ull;
-        unsigned long long hitb[NU];
+        unsigned long long hitb[NU];         // the blocks' own masks, kept for the event
         [[maybe_unused]] int tc = 0, tf = 0;
         [[maybe_unused]] const unsigned* side = nullptr;
         [[maybe_unused]] const char* gt = nullptr;
@@ -1237,9 +1074,6 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 if constexpr ((n & 1) == 0) {
                     asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(a0[u]) : "v"(v[0]), "v"(v[1]), "v"(v[2]));
                     asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(a1[u]) : "v"(v[3]), "v"(v[4]), "v"(v[5]));
-                } else if constexpr (DMA_BODY_PADDED) {
-                    asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(a2[u]) : "v"(v[6]), "v"(v[7]), "v"(a0[u]));
-                    asm volatile("v_max_f32 %0, %1, %2" : "=v"(m[u]) : "v"(a1[u]), "v"(a2[u]));
                 } else {
                     // one statement with one output (round 22).  Between two statements, the second reading what the first wrote, hipcc
                     // puts an s_nop; and behind a statement with a scratch output it puts one too, because it hands the dead scratch
@@ -1388,12 +1222,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 #endif
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (DMA_BODY_PADDED) {
-                if constexpr (g == 0) lds_wait(c[g], std::integral_constant<int, 4>{});
-                else lds_wait(c[g], std::integral_constant<int, 2>{});
-            } else {
-                lds_wait_bare(std::integral_constant<int, g == 0 ? 4 : 2>{});
-            }
+            lds_wait_bare(std::integral_constant<int, g == 0 ? 4 : 2>{});
             __builtin_amdgcn_sched_barrier(0);
             [&]<int... N>(std::integer_sequence<int, N...>) __attribute__((always_inline)) {
                 (([&]() __attribute__((always_inline)) {
@@ -1432,9 +1261,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
 #pragma unroll
                     for (int u = 0; u < NU; ++u)
                         // (an event of block u moves tau[u] alone, so the masks of the common path are still those of the blocks behind it)
-                        if (!DMA_EVENT_REBALLOT ? hitb[u] != 0ull : __ballot(m[u] > tau[u]) != 0ull)
-                            if constexpr (M16)       // (the other forms never call this body, but they parse it)
-                                event16(acc[Q][u], tau[u], u, ts, rows_left, gi0, tb, idv, rt);
+                        if (hitb[u] != 0ull) event16(acc[Q][u], tau[u], u, rows_left, gi0, tb, idv, rt);
                     // the list stores of the inserts are drained HERE (as in `body`); the fragment reads in flight land with them
                     __builtin_amdgcn_s_waitcnt(0xc07f);
 #ifdef CRH_PROFILE
@@ -1545,7 +1372,7 @@ __global__ __launch_bounds__(256, 1) void score_topk_dma_kernel(ScoreArgs a) {
                 }
             }
         };
-        if constexpr (M16 && DMA_M16_HOOKED) {
+        if constexpr (M16) {
             // body 0 peeled; a trip is then the odd body and the even one behind it, with the trip's head (an even j, as ever) between them
             lds_group(c[2], ring_lds, std::integral_constant<int, 2>{});
             if constexpr (BODY_CARRY) {
@@ -1660,16 +1487,16 @@ int score_dma_ring_slots(int esz, int d, int k, int mode) {
 // half the B registers, the same loop.  mode: 2 = the flag form (fp32 d=128 only), anything else the barrier form.
 int launch_score_dma(int esz, int d, int mode, const ScoreArgs& a, hipStream_t stream) {
     // both fp16 d=128 launches are the screen's: their 16x16 form is compiled for its K' and takes no other list length
-    if (esz == 2 && d == 128 && DMA_SCREEN_M16 && DMA_EVENT_KC != 0 && a.k != DMA_EVENT_KC) return CRH_ERR_ARG;
+    if (esz == 2 && d == 128 && a.k != SCREEN_KP) return CRH_ERR_ARG;
     // ... and they carry the margin rule (dma_new_tau): its word and the call's k come with the launch
     if (esz == 2 && d == 128 && (a.margin == nullptr || a.screen_k < 1 || a.screen_k > a.k)) return CRH_ERR_ARG;
     if (esz == 2 && d == 128 && a.idmap != nullptr) {     // the compacted stream of the screened route
         if (score_dma_lds_bytes(d * esz, a.k, 4, false, true) > 160 * 1024) return CRH_ERR_ARG;
-        return launch_score_dma_t<_Float16, 128, 4, false, true, DMA_SCREEN_M16>(a, stream);
+        return launch_score_dma_t<_Float16, 128, 4, false, true, true>(a, stream);
     }
     // (fp16 d=128 reaches this kernel from the screen only -- the public fp16 d=128 calls take the ring kernel, score_topk.hip
     // dma_rows -- so both of its launches share one definition of the approximate score)
-    if (esz == 2) return d == 128 ? launch_score_dma_t<_Float16, 128, 4, false, false, DMA_SCREEN_M16>(a, stream) : launch_score_dma_t<_Float16, 256, 4, false>(a, stream);
+    if (esz == 2) return d == 128 ? launch_score_dma_t<_Float16, 128, 4, false, false, true>(a, stream) : launch_score_dma_t<_Float16, 256, 4, false>(a, stream);
     if (d == 64) return launch_score_dma_t<float, 64, 4, false>(a, stream);
     return mode == 2 ? launch_score_dma_t<float, 128, 4, true>(a, stream) : launch_score_dma_t<float, 128, 4, false>(a, stream);
 }
