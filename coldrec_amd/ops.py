@@ -374,8 +374,8 @@ def warm_up(device) -> None:
         mask_topk(torch.zeros((4, 64), **f32), 4, write_back=False)
         idx = torch.zeros(4, dtype=torch.int32, device=device)
         g, gv = torch.zeros_like(u), torch.zeros_like(v)
-        bpr_fwd_bwd(u, v, v, idx, idx, idx, 0.0, g, gv, gv, plan=build_plans_device(idx, idx, idx, 4)[0])   # bpr_adam.hip
-        adam_dense(u.clone(), g, torch.zeros_like(u), torch.zeros_like(u), 1)
+        bpr_fwd_bwd(u, v, v, idx, idx, idx, 0.0, g, gv, gv, plan=build_plans_device(idx, idx, idx, 4)[0])   # bpr_plan.hip, bpr.hip
+        adam_dense(u.clone(), g, torch.zeros_like(u), torch.zeros_like(u), 1)  # optim.hip
         l2_norm(u)                                                           # l2_reg.hip
         rp = torch.arange(0, 65, dtype=torch.int64, device=device).clamp_(max=1)
         spmm_csr(rp, torch.zeros(1, dtype=torch.int32, device=device), torch.ones(1, **f32), u, y=torch.empty_like(u))

@@ -1,4 +1,4 @@
-"""Edges of the training kernels (coldrec_amd/csrc/bpr_adam.hip, l2_reg.hip, spmm.hip's SGD epilogue -- the SpMM's own
+"""Edges of the training kernels (coldrec_amd/csrc/bpr.hip, bpr_plan.hip, optim.hip, mf_step.hip, l2_reg.hip, spmm.hip's SGD epilogue -- the SpMM's own
 widths, cuts and heavy-row sum tree are tests/test_spmm_edges_gpu.py): the shapes, widths,
 grid caps, heavy-row thresholds and row-ownership splits where a change of lane mapping, ownership or reduction order would
 otherwise go unnoticed.  Every kernel is driven through coldrec_amd.ops or the C ABI and compared with either
@@ -206,13 +206,13 @@ def test_l2_zero_tensor_gives_zero_gradient(n, off):
 
 
 # ================================================================================================ 2. lane-group widths
-WIDTHS = [4, 12, 20, 36, 68, 132, 196, 252, 256]      # pick_group (bpr_adam.hip:1060): idle lanes just past a power of two
+WIDTHS = [4, 12, 20, 36, 68, 132, 196, 252, 256]      # pick_group (train_common.h): idle lanes just past a power of two
 WIDE = [260, 384, 512]                                # a 64-lane group walks each row twice (c += G loops)
 
 
 @pytest.mark.parametrize("d", WIDTHS + WIDE)
 def test_widths_bpr_atomics_vs_fp64(d):
-    """Atomics forward / backward (bpr_adam.hip:82 bpr_fwd_kernel, :164 bpr_bwd_kernel) at every lane-group width, d > 256
+    """Atomics forward / backward (bpr.hip: bpr_fwd_kernel, bpr_bwd_kernel) at every lane-group width, d > 256
     included, against fp64 with test_bpr_fwd_bwd_vs_oracle's tolerances; the gradient tables sit between guard rows and
     untouched rows stay exactly 0 (no idle lane, no lane past the row, writes anything)."""
     from coldrec_amd import ops
@@ -233,7 +233,7 @@ def test_widths_bpr_atomics_vs_fp64(d):
 
 @pytest.mark.parametrize("d", WIDTHS)
 def test_widths_plan_backward_vs_fp64_and_repeat(d):
-    """Plan backward (bpr_adam.hip:368 bpr_bwd_rows_kernel, light rows :383 and heavy rows :400 -- three hot items put rows
+    """Plan backward (bpr.hip: bpr_bwd_rows_kernel, its light-row and its heavy-row loop -- three hot items put rows
     on the heavy list) at every width up to 256: fp64 with the tolerances above, two runs bit-identical, guard rows intact,
     untouched rows exactly 0."""
     from coldrec_amd import ops
@@ -261,9 +261,9 @@ def test_widths_plan_backward_vs_fp64_and_repeat(d):
 
 @pytest.mark.parametrize("d", WIDE)
 def test_widths_beyond_256_refused_where_unsupported(d):
-    """The plan backward holds one 16-B slice per lane (d <= 256) and refuses wider tables loudly (bpr_adam.hip:1660), as
-    does the row exchange of the ownership split (:1824, :1841); MFEngine does not offer the one-launch step (whose entry
-    point refuses d > 256 at :2027) for such tables."""
+    """The plan backward holds one 16-B slice per lane (d <= 256) and refuses wider tables loudly (bpr.hip: bpr_launch), as
+    does the row exchange of the ownership split (crh_rows_pack_f32, crh_rows_unpack_f32); MFEngine does not offer the one-launch step (whose entry
+    point, mf_step.hip's mf_step_run, refuses d > 256) for such tables."""
     from coldrec_amd import ops
     rng = np.random.default_rng(d)
     U, V = rand_tables(rng, 10, 12, d)
@@ -284,7 +284,7 @@ def test_widths_beyond_256_refused_where_unsupported(d):
 
 @pytest.mark.parametrize("d", WIDTHS + WIDE)
 def test_widths_optimisers_bitwise_vs_oracle_order(d):
-    """sgd_dense (bpr_adam.hip:958), sgd_rows (:1041), adam_dense (:917) and adam_rows (:996) at every width: bit for bit the
+    """optim.hip's sgd_dense_kernel, sgd_rows_kernel, adam_dense_kernel and adam_rows_kernel at every width: bit for bit the
     oracle's op order (oracle_np.sgd_dense: one fma; oracle_np.adam_dense: torch's separate rounded ops), as
     test_sgd_dense_is_one_fma_per_element.  The rows kernels touch exactly the plan's rows (guard rows and untouched rows
     unchanged, bitwise) and clear the gradient rows they consumed."""
@@ -351,8 +351,8 @@ def test_widths_optimisers_bitwise_vs_oracle_order(d):
 @pytest.mark.parametrize("d,B,use_plan", [(256, 4096, True), (256, 4097, True), (256, 8192, True),
                                           (128, 8193, False), (128, 20_000, False)])
 def test_forward_grid_cap(d, B, use_plan):
-    """The forward grid is capped at BPR_MAX_BLOCKS = 1 024 (bpr_adam.hip:1685) and grid-strides beyond it (:89); the
-    backward's batch_totals (:124) then reduces 1 024 partials.  d = 256 (4 triples per block) reaches the cap at B = 4 096,
+    """The forward grid is capped at BPR_MAX_BLOCKS = 1 024 (bpr.hip: bpr_launch) and grid-strides beyond it (bpr_fwd_kernel); the
+    backward's batch_totals then reduces 1 024 partials.  d = 256 (4 triples per block) reaches the cap at B = 4 096,
     d = 128 (8 per block) at 8 192.  Losses 1e-5 against fp64, gradients as test_bpr_fwd_bwd_vs_oracle."""
     from coldrec_amd import ops
     assert ops.bpr_fwd_parts(B, d) == min(1024, -(-B // (256 // (64 if d == 256 else 32))))
@@ -417,8 +417,8 @@ def heavy_epoch(kind, seed):
 def test_heavy_threshold_plan_backward_and_sgd_rows(kind, d):
     """Rows at exactly T - 1, T and T + 1 entries (T = crh_bpr_heavy_threshold(), as positive, as negative, and mixed) and
     one user row holding all 8 192 entries of a batch: the plan's heavy list is exactly the rows above T, the plan backward
-    (light rows bpr_adam.hip:388, heavy rows :400) equals fp64 within test_bpr_fwd_bwd_vs_oracle's tolerances, repeats
-    bit for bit, and agrees with the atomics backward within the same bounds; sgd_rows (:1041) on the result is bit for bit
+    (bpr.hip: bpr_bwd_rows_kernel, light rows and heavy rows) equals fp64 within test_bpr_fwd_bwd_vs_oracle's tolerances, repeats
+    bit for bit, and agrees with the atomics backward within the same bounds; sgd_rows on the result is bit for bit
     oracle_np.sgd_dense over the whole table."""
     from coldrec_amd import ops
     T = heavy_T()
@@ -473,7 +473,7 @@ def _fp64_sgd_replay(U0, V0, batches, reg, lr):
 @pytest.mark.parametrize("opt", ["adam", "sgd"])
 @pytest.mark.parametrize("kind", ["edges", "one_user"])
 def test_heavy_threshold_one_launch_step(kind, opt):
-    """The one-launch step (bpr_adam.hip:1266 mf_step_kernel; light rows skip heavy ones at :1357, heavy blocks :1365) with
+    """The one-launch step (mf_step.hip: mf_step_kernel; its light loop skips heavy rows, its heavy blocks take them) with
     Adam and with SGD, on the batches above, through EpochRunner(fused=True) against the three-kernel step
     (fused=False: plan backward + adam_dense / sgd_rows): the tolerances of test_fused_mf_step_matches_three_kernel_step
     (losses 2e-6, tables 2e-4 + 1e-5 of the largest entry: the two differ in the summation order of the norms only); two
@@ -531,8 +531,8 @@ def _owned_case(seed, d, kind):
 
 
 def check_owned_partition(U, V, tri, plan, B, own_mod):
-    """The row-ownership split (bpr_adam.hip:389 light rows / :402 heavy rows; crh_rows_pack_f32 :1787, crh_rows_unpack_f32
-    :1802) against the plain plan backward, all bitwise: for every own_rem, bpr_bwd_owned STORES exactly the rows of plan
+    """The row-ownership split (bpr.hip: the own_mod tests of bpr_bwd_rows_kernel's light and heavy loops; rows_pack_kernel,
+    rows_unpack_kernel) against the plain plan backward, all bitwise: for every own_rem, bpr_bwd_owned STORES exactly the rows of plan
     slots w % own_mod == own_rem with the plain backward's bits and leaves every other row (sentinel-filled) untouched, and
     reports the same loss; the owned slots partition the plan; rows_pack writes the owned slots' rows in slot order (-1
     past the plan, whose rows it leaves alone) as bitwise copies; packing every rank, concatenating (the all-gather) and
@@ -610,7 +610,7 @@ def test_row_ownership_partition(d, kind, own_mod):
 # ================================================================================================ 6. lazy Adam through adam_rows
 @pytest.mark.parametrize("d", [4, 68, 256, 260])
 def test_adam_rows_replay_equals_dense_adam(d):
-    """crh_adam_rows_f32 driven directly (bpr_adam.hip:996: catch-up mode 0, step mode 1, flush mode 2 at :1011) over 12
+    """crh_adam_rows_f32 driven directly (optim.hip: adam_rows_kernel -- catch-up mode 0, step mode 1, flush mode 2) over 12
     steps with random touched subsets against crh_adam_dense_f32 applied 12 times to the same gradients: p, m, v bit for
     bit.  Two lazy replicas: A flushes at three random steps (each compared whole with the dense tables, then flushed again
     with nothing stale: a no-op, bitwise); B never flushes before the end, so its final flush replays every stale row --
