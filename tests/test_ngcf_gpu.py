@@ -7,8 +7,8 @@ Bars.  Every output is measured as its largest error over the largest magnitude 
 same distance of the float32 torch formula, run on the same device at the same shape (measured in the test, printed with
 the kernel's).  The backward takes x_k as an input, so all three (kernel, float32 formula, float64) take the slope from the
 same signs.  Measured on the MI355X: the kernel's worst ratio to the torch formula's own distance is 2.74 over the layer
-cases (N17-d12 bwd, ds: 1.4e-7 against 5.0e-8) and 2.15 in the engine step; its largest distance 8.8e-7 (x_k, N1003-d256,
-torch 5.9e-7).  The G17 run ends 1.0e-7 (bpr), 3.5e-7 (l2), 2.6e-8 (epoch norms), 2.2e-8 (parameter norms) and 4.7e-7
+cases (N17-d12 bwd, ds: 1.4e-7 against 5.0e-8) and 0.94 in the engine step; its largest distance 8.8e-7 (x_k, N1003-d256,
+torch 5.9e-7).  The G17 run ends 1.0e-7 (bpr), 3.5e-7 (l2), 1.5e-8 (epoch norms), 1.7e-8 (parameter norms) and 2.4e-7
 (sampled rows) from the reference's, every test metric equal (the NGCF section)."""
 import argparse
 import json
@@ -27,7 +27,10 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 # (N, d): every N in {1, 15, 16, 17, 63, 65, 257, 1003} and every d in {4, 12, 16, 60, 64, 100, 128, 256} at least once;
-# d <= 64 takes the one-kernel backward (weights in LDS), wider ones the two-launch form with 3 .. 16 column slabs
+# d <= 64 takes the one-kernel backward (weights in LDS), wider ones the two-launch form.  These widths reach the
+# instantiations DP = 32, 64, 128, 256 (1, 1, 4, 16 slabs), at most 32 partials (one chunk) and one tile per wave.
+# tests/test_ngcf_edges_gpu.py adds DP = 96, 160, 192, 224 (3, 10, 12, 14 slabs; 160 and 224 with an odd tile count), 2 .. 64
+# chunks of partials and 2 and 3 tiles per wave.
 PAIRS = [(1, 4), (15, 12), (16, 16), (17, 12), (63, 60), (65, 64), (257, 100), (1003, 64), (257, 128), (1003, 256), (17, 256),
          (65, 4), (1003, 100), (63, 128)]
 IDS = lambda p: "N%d-d%d" % p
@@ -144,9 +147,10 @@ def test_exact_zeros_take_torchs_rule(pair):
         assert _dist(got, want) <= 2e-6, (name, _dist(got, want))
 
 
-def test_two_identical_backward_calls_give_identical_bits():
+@pytest.mark.parametrize("pair", [(1003, 64), (2049, 132)], ids=IDS)
+def test_two_identical_backward_calls_give_identical_bits(pair):
     from coldrec_amd import ops
-    n, d = 1003, 64
+    n, d = pair
     inp = _inputs(n, d, seed=3)
     x, s, w, g, dout, xk = (inp[k].to(DEV) for k in ("x", "s", "w", "g", "dout", "acc"))
     a = ops.ngcf_layer_bwd(x, s, xk, g, dout, C, w)
@@ -171,7 +175,7 @@ def _intact(buf, rows, pad=8):
     return bool((buf[:pad] == CANARY).all() and (buf[pad + rows:] == CANARY).all())
 
 
-@pytest.mark.parametrize("pair", [(17, 12), (1003, 256)], ids=IDS)
+@pytest.mark.parametrize("pair", [(17, 12), (1003, 256), (2049, 132)], ids=IDS)
 def test_nothing_is_written_outside_the_outputs_and_the_workspace(pair):
     from coldrec_amd import ops
     n, d = pair
@@ -213,7 +217,7 @@ def test_a_workspace_one_byte_short_is_refused():
     ops.ngcf_layer_bwd(x, s, xk, g, dout, C, w, ds=ds, local=local, dw=dw, db=db, workspace=ws)
 
 
-@pytest.mark.parametrize("pair", [(1003, 64), (257, 128), (17, 256), (63, 60)], ids=IDS)
+@pytest.mark.parametrize("pair", [(1003, 64), (257, 128), (17, 256), (63, 60), (2049, 132)], ids=IDS)
 def test_permitted_aliasing_gives_the_same_bits(pair):
     """local over g and ds over s (include/coldrec_hip.h), in the one-kernel form (d <= 64) and the two-launch form."""
     from coldrec_amd import ops
