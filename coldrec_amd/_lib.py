@@ -132,6 +132,11 @@ SIGNATURES = {
     "crh_vbpr_f32": (_i32, [_vp, _i64, _vp, _i64] + [_vp] * 6 + [_i32] * 4 + [_vp] * 5 + [_i64, _i64] + [_vp] * 5 +
                             [_i64, _i64, _i64, _i32, _i32, _f32, _f32, _f32] + [_vp] * 8 + [_sz, _vp]),
     "crh_adagrad_rows_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _vp]),
+    "crh_metaemb_workspace_bytes": (_sz, [_i64, _i32]),
+    "crh_metaemb_f32": (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp,
+                               _sz, _vp]),
+    "crh_deepmusic_workspace_bytes": (_sz, [_i64, _i32]),
+    "crh_deepmusic_f32": (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _sz, _vp]),
     "crh_ngcf_workspace_bytes": (_sz, [_i64, _i32]),
     "crh_ngcf_layer_fwd_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _f32, _vp, _f32, _vp]),
     "crh_ngcf_layer_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

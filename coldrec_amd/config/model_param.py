@@ -100,4 +100,7 @@ def model_specific_param(model_name, parser, available_models):
     if model_name == 'AMR':
         parser.add_argument('--eps', type=float, default=0.1, help='Length of the adversarial shift of a content row')
         parser.add_argument('--lmd', type=float, default=1, help='Weight of the adversarial term')
+    if model_name == 'MetaEmbedding':      # config/model_param.py:266-267 (DeepMusic takes no flags of its own)
+        parser.add_argument('--alpha', type=float, default=0.5,
+                            help='Weight of the cold-start loss; 1 - alpha weighs the warm-up loss')
     return parser

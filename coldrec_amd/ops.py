@@ -954,7 +954,7 @@ def _check_ids_in_tables(op: str, what: str, user_range, item_range, user_table,
         raise RuntimeError(f"{op}: {what} lie outside the tables")
 
 
-_AT_LEAST = {1: "one element", 4: "four elements", 5: "five elements", 6: "six elements"}
+_AT_LEAST = {1: "one element", 3: "three elements", 4: "four elements", 5: "five elements", 6: "six elements"}
 
 
 def _loss_buffer(op: str, loss, n: int, device) -> torch.Tensor:
@@ -1617,6 +1617,88 @@ def adagrad_rows(p: torch.Tensor, g: torch.Tensor, state_sum: torch.Tensor, ids:
     _lib.check(_lib.lib().crh_adagrad_rows_f32(_lib.ptr(p), _lib.ptr(g), _lib.ptr(state_sum), _lib.ptr(ids),
                                                int(ids.shape[0]), int(p.shape[0]), int(d), float(lr), float(eps),
                                                int(bool(zero_grad)), _lib.current_stream()), "crh_adagrad_rows_f32")
+
+
+# ---- the two frozen-table generator losses: MetaEmbedding's (metaemb.hip) and DeepMusic's (deepmusic.hip) ------------
+
+def metaemb_workspace_bytes(n: int, d: int) -> int:
+    return int(_lib.lib().crh_metaemb_workspace_bytes(int(n), int(d)))
+
+
+def metaemb_workspace(n: int, d: int, device) -> torch.Tensor:
+    return _new_workspace(metaemb_workspace_bytes(n, d), device)
+
+
+def deepmusic_workspace_bytes(batch: int, d: int) -> int:
+    return int(_lib.lib().crh_deepmusic_workspace_bytes(int(batch), int(d)))
+
+
+def deepmusic_workspace(batch: int, d: int, device) -> torch.Tensor:
+    return _new_workspace(deepmusic_workspace_bytes(batch, d), device)
+
+
+def _frozen_table_checks(op: str, table, ids, gen, id_range, *others):
+    """What ``metaemb`` and ``deepmusic`` check alike: one frozen table, (N,) ids into it and (N, d) generated rows on one
+    device.  Returns (N, d, (id min, id max), the ids as int32)."""
+    _need_cuda(table, ids, gen, *others)
+    _check_2d_f32(op, "the table and the generated rows", table, gen)
+    d = table.shape[1]
+    _check_width(op, d)
+    N = ids.shape[0] if ids.dim() == 1 else 0
+    if N < 1 or ids.dtype.is_floating_point:
+        raise RuntimeError(f"{op}: ids must be an (N,) integer tensor with N >= 1")
+    if gen.shape != (N, d):
+        raise RuntimeError(f"{op}: the generated rows must be (N, d) of the table's width, one row per id")
+    _check_one_device(op, "the table's", table.device, ids, gen, *others)
+    if id_range is None:
+        id_range = (int(ids.min()), int(ids.max()))
+    lo, hi = (int(x) for x in id_range)
+    if lo < 0 or hi >= table.shape[0]:
+        raise RuntimeError(f"{op}: ids lie outside the table")
+    return N, d, (lo, hi), ids.to(torch.int32).contiguous()
+
+
+def metaemb(table: torch.Tensor, ids: torch.Tensor, emb: torch.Tensor, n_pos: int, alpha: float, cold_lr: float,
+            scale: float = 1.0, want_grad: bool = True, want_scores: bool = False, grad_emb=None, loss=None, scores=None,
+            workspace=None, id_range=None):
+    """MetaEmbedding's loss and its gradient in one call (crh_metaemb_f32).  table (rows, d): the frozen table; ids (N,)
+    integer ids into it; emb (N, d): the generated rows, one per occurrence; occurrences below n_pos have the target 1,
+    the rest 0; fp32 contiguous, d % 4 == 0 <= 256.  Returns (loss3 = [L_a, L_b, ME], grad_emb, scores): grad_emb is
+    d ME / d emb * scale, scores the (2, N) scores y_a, y_b; one that is neither given nor wanted is not computed (None).
+    id_range = (id min, id max) when the caller knows them; measured here otherwise, which waits for the device."""
+    N, d, (lo, hi), ids = _frozen_table_checks("metaemb", table, ids, emb, id_range, grad_emb, loss, scores, workspace)
+    dev = table.device
+    if not 0 <= int(n_pos) <= N:
+        raise RuntimeError(f"metaemb: n_pos = {n_pos} out of [0, {N}]")
+    grad_emb = _grad_buffer("metaemb", "the generated rows' shape", grad_emb, emb, want_grad, True)
+    if scores is None:
+        scores = torch.empty((2, N), dtype=torch.float32, device=dev) if want_scores else None
+    elif scores.dtype != torch.float32 or not scores.is_contiguous() or scores.shape != (2, N):
+        raise RuntimeError("metaemb: scores must be a contiguous float32 tensor of (2, N)")
+    loss = _loss_buffer("metaemb", loss, 3, dev)
+    workspace = _workspace_arg("metaemb", workspace, metaemb_workspace, N, d, dev)
+    _lib.check(_lib.lib().crh_metaemb_f32(
+        _lib.ptr(table), int(table.shape[0]), _lib.ptr(ids), lo, hi, _lib.ptr(emb), int(N), int(n_pos), int(d),
+        float(alpha), float(cold_lr), float(scale), _lib.ptr(grad_emb), _lib.ptr(loss), _lib.ptr(scores),
+        _lib.ptr(workspace), workspace.numel(), _lib.current_stream()), "crh_metaemb_f32")
+    return loss, grad_emb, scores
+
+
+def deepmusic(table: torch.Tensor, ids: torch.Tensor, gen: torch.Tensor, reg: float, scale: float = 1.0,
+              want_grad: bool = True, grad_gen=None, loss=None, workspace=None, id_range=None):
+    """DeepMusic's loss and its gradient in one call (crh_deepmusic_f32).  table (rows, d): the frozen table; ids (B,)
+    integer ids into it; gen (B, d): the generated rows; fp32 contiguous, d % 4 == 0 <= 256.  Returns (loss3 = [L_mse, R,
+    total], grad_gen = d total / d gen * scale, or None when neither given nor wanted).  id_range as ``metaemb``'s."""
+    B, d, (lo, hi), ids = _frozen_table_checks("deepmusic", table, ids, gen, id_range, grad_gen, loss, workspace)
+    dev = table.device
+    grad_gen = _grad_buffer("deepmusic", "the generated rows' shape", grad_gen, gen, want_grad, True)
+    loss = _loss_buffer("deepmusic", loss, 3, dev)
+    workspace = _workspace_arg("deepmusic", workspace, deepmusic_workspace, B, d, dev)
+    _lib.check(_lib.lib().crh_deepmusic_f32(
+        _lib.ptr(table), int(table.shape[0]), _lib.ptr(ids), lo, hi, _lib.ptr(gen), int(B), int(d), float(reg),
+        float(scale), _lib.ptr(grad_gen), _lib.ptr(loss), _lib.ptr(workspace), workspace.numel(), _lib.current_stream()),
+        "crh_deepmusic_f32")
+    return loss, grad_gen
 
 
 # ---- NGCF's propagation layer (ngcf.hip) -----------------------------------------------------------------------------

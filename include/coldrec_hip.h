@@ -845,6 +845,49 @@ int crh_adagrad_rows_f32(float* p, float* g, float* state_sum, const int32_t* id
                          double lr, double eps, int zero_grad, void* stream);
 
 /*
+ * The loss of MetaEmbedding (reference model/MetaEmbedding.py:28-44, 168-203), forward and backward in one call
+ * (csrc/metaemb.hip): a cold-start step and a warm-up step after one inner gradient step, as first-order MAML has them.
+ * table (rows, d) is frozen; ids (n) point into it; emb (n, d) = the generated rows, one per occurrence; occurrence
+ * i < n_pos has the target t = 1, the rest t = 0.  With o = table[ids[i]], bce(y, t) = max(y, 0) - t y +
+ * log1p(exp(-|y|)), s = sigmoid and every mean over the n occurrences:
+ *     y_a = <o, emb_i>                          L_a = mean bce(y_a, t)
+ *     g   = (s(y_a) - t) o / n                  (a constant: the inner gradient is not differentiated)
+ *     y_b = <o, emb_i - cold_lr g>              L_b = mean bce(y_b, t)
+ *     ME  = alpha L_a + (1 - alpha) L_b
+ *   id_min, id_max the smallest and largest id, as the caller states them: a range that leaves the table is an argument
+ *                  error (an occurrence whose id leaves the table all the same contributes nothing, zero gradient row)
+ *   grad_emb       (n, d): d ME / d emb * scale = scale [alpha (s(y_a) - t) + (1 - alpha) (s(y_b) - t)] o / n, every row
+ *   loss_out       3 device floats: L_a, L_b, ME (not scaled)
+ *   scores_out     2 n device floats: y_a of every occurrence, then y_b
+ *                  Any output may be NULL: it is not written and the others keep their bits; all NULL is an error
+ *   workspace      crh_metaemb_workspace_bytes(n, d) bytes (0 = a refused shape), 256-byte aligned
+ * d % 4 == 0, 4 <= d <= 256; 1 <= n < 2^31; 0 <= n_pos <= n; table, emb and grad_emb 16-byte aligned.  Sigmoid and bce
+ * are formed from exp(-|y|): a saturated score neither overflows nor loses the slope's sign.  No atomics, every sum in an
+ * order fixed by n and d: two identical calls give identical bits.  Two launches on the stream: one lane group per
+ * occurrence, then one workgroup that adds the occurrences' two terms in index order.
+ */
+size_t crh_metaemb_workspace_bytes(int64_t n, int d);
+int crh_metaemb_f32(const float* table, int64_t rows, const int32_t* ids, int id_min, int id_max, const float* emb,
+                    int64_t n, int64_t n_pos, int d, float alpha, float cold_lr, float scale, float* grad_emb,
+                    float* loss_out, float* scores_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The loss of DeepMusic (reference model/DeepMusic.py:19-29, util/utils.py:32-48), forward and backward in one call
+ * (csrc/deepmusic.hip).  table (rows, d) is frozen; ids (batch) point into it; gen (batch, d) = the generated rows:
+ *     L_mse = sum |table[ids[b]] - gen_b|^2 / (batch d)      R = reg |gen|_F / batch      total = L_mse + R
+ *   grad_gen       (batch, d): d total / d gen * scale = scale (2 (gen_b - table[ids[b]]) / (batch d) + reg gen_b /
+ *                  (batch |gen|_F)), every row; the second part is zero when |gen|_F = 0.  NULL = not computed
+ *   loss_out       3 device floats: L_mse, R, total (not scaled); NULL = not written; both NULL is an error
+ *   id_min, id_max, workspace (crh_deepmusic_workspace_bytes(batch, d)), widths, alignment and the determinism contract
+ *                  as crh_metaemb_f32's; 1 <= batch < 2^31.  Three launches: one lane group per record, one workgroup
+ *                  for the loss and the norm's factor, and that factor times gen added to every row of grad_gen.
+ */
+size_t crh_deepmusic_workspace_bytes(int64_t batch, int d);
+int crh_deepmusic_f32(const float* table, int64_t rows, const int32_t* ids, int id_min, int id_max, const float* gen,
+                      int64_t batch, int d, float reg, float scale, float* grad_gen, float* loss_out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/*
  * The layer perturbation of SimGCL / XSimGCL (model/SimGCL.py:106-108), in place on one (n_rows, d) fp32 layer output
  * of the propagation, d % 4 == 0, 4 <= d <= 256, every pointer 16-byte aligned.  Per row, r = the row's d uniforms:
  *     nrm = max(sqrt(sum r^2), 1e-12)                       (F.normalize's clamp)
