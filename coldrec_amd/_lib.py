@@ -131,6 +131,12 @@ SIGNATURES = {
     "crh_vbpr_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64, _i64]),
     "crh_vbpr_f32": (_i32, [_vp, _i64, _vp, _i64] + [_vp] * 6 + [_i32] * 4 + [_vp] * 5 + [_i64, _i64] + [_vp] * 5 +
                             [_i64, _i64, _i64, _i32, _i32, _f32, _f32, _f32] + [_vp] * 8 + [_sz, _vp]),
+    "crh_duif_chunk_rows": (_i32, []),
+    "crh_duif_part_chunk": (_i32, []),
+    "crh_duif_parts": (_i64, [_i64, _i32, _i32]),
+    "crh_duif_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i64]),
+    "crh_duif_f32": (_i32, [_vp, _i64, _vp, _i64, _i32] + [_vp] * 4 + [_i32] * 4 + [_vp] * 5 + [_i64, _i64, _i64, _i32, _i32,
+                            _f32, _f32] + [_vp] * 5 + [_sz, _vp]),
     "crh_adagrad_rows_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _vp]),
     "crh_metaemb_workspace_bytes": (_sz, [_i64, _i32]),
     "crh_metaemb_f32": (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp,

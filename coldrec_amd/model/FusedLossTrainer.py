@@ -1,4 +1,4 @@
-"""What the trainers around a fused HIP loss (CLCRec, CCFCRec, ALDI, GAR, MTPR, VBPR, AMR, MetaEmbedding, DeepMusic) share: the epoch loop, the checkpoint of
+"""What the trainers around a fused HIP loss (CLCRec, CCFCRec, ALDI, GAR, MTPR, VBPR, AMR, MetaEmbedding, DeepMusic, DUIF) share: the epoch loop, the checkpoint of
 the published tables, ``--save_emb``, the stock ``predict`` pair, and the loading of a backbone's saved tables.
 
 A trainer states the names of its loss terms and of the tables it publishes, and supplies ``_optimizers``,

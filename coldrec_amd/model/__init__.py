@@ -14,7 +14,7 @@ import importlib
 _BUILTIN = {'MF': ('.MF', 'MF'), 'LightGCN': ('.LightGCN', 'LightGCN'), 'DropoutNet': ('.DropoutNet', 'DropoutNet')}
 _CONTRASTIVE = ('SimGCL', 'XSimGCL')
 _LAZY = {name: ('.' + name, name) for name in _CONTRASTIVE + ('CLCRec', 'CCFCRec', 'ALDI', 'GAR', 'NCL', 'NGCF', 'MTPR', 'VBPR',
-                                                                   'AMR', 'MetaEmbedding', 'DeepMusic')}
+                                                                   'AMR', 'MetaEmbedding', 'DeepMusic', 'DUIF')}
 _lazy_cache = {}
 
 

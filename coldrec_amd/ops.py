@@ -1600,6 +1600,100 @@ def vbpr(user_table: torch.Tensor, item_table: torch.Tensor, aux_table: torch.Te
     return loss, grad_user, grad_item, grad_aux, grad_h, grad_h_adv, grad_hsum
 
 
+# ---- DUIF's projected BPR step (duif.hip) ----------------------------------------------------------------------------
+
+def duif_chunk_rows() -> int:
+    return int(_lib.lib().crh_duif_chunk_rows())
+
+
+def duif_part_chunk() -> int:
+    """How many weight-gradient partials one first-stage sum adds."""
+    return int(_lib.lib().crh_duif_part_chunk())
+
+
+def duif_parts(rows: int, d: int, c: int) -> int:
+    """The weight-gradient partials of ``rows`` projected rows (2 B in item mode, B in user mode): a function of the shape."""
+    return int(_lib.lib().crh_duif_parts(int(rows), int(d), int(c)))
+
+
+def duif_workspace_bytes(batch: int, d: int, c: int, cold_user: bool, n_own: int) -> int:
+    return int(_lib.lib().crh_duif_workspace_bytes(int(batch), int(d), int(c), int(bool(cold_user)), int(n_own)))
+
+
+def duif_workspace(batch: int, d: int, c: int, cold_user: bool, n_own: int, device) -> torch.Tensor:
+    return _new_workspace(duif_workspace_bytes(batch, d, c, cold_user, n_own), device)
+
+
+def duif_plan(users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, cold_user: bool, n_users: Optional[int] = None,
+              n_items: Optional[int] = None, id_range=None, chunk: Optional[int] = None) -> dict:
+    """The index side of one crh_duif_f32 step.  users, pos, neg (B,): integer tensors on one device.  Only the FREE side's
+    occurrences are grouped -- the B users in item mode, the 2 B items (pos, then neg) in user mode --: own_ids (the
+    distinct ids, ascending), own_ptr, own_occ (a stable sort, so ascending inside an id), cut into chunks of
+    crh_duif_chunk_rows() (own_chunk_ptr, own_chunk_own).  The projected side's ids are converted to int32 and nothing
+    more: projection is per occurrence.  id_range, n_users, n_items and ``chunk``: as ``gar_plan``'s."""
+    B = users.shape[0] if users.dim() == 1 else 0
+    if B < 1 or pos.shape != (B,) or neg.shape != (B,):
+        raise RuntimeError("duif_plan: users, pos, neg must be (B,) with B >= 1")
+    if any(t.dtype.is_floating_point or t.device != users.device for t in (users, pos, neg)):
+        raise RuntimeError("duif_plan: users, pos, neg must be integer tensors on one device")
+    cold_user = bool(cold_user)
+    ulong = users.long()
+    both = torch.cat([pos.long(), neg.long()])
+    if id_range is None:
+        id_range = ((int(ulong.min()), int(ulong.max())), (int(both.min()), int(both.max())))
+    user_range, item_range = (tuple(int(x) for x in r) for r in id_range)
+    _check_ids_in_plan("duif_plan", user_range, item_range, n_users, n_items)
+    c = lambda t: t.to(torch.int32).contiguous()
+    chunk = duif_chunk_rows() if chunk is None else chunk
+    own_ids, occ, ptr, chunk_ptr, chunk_own = (c(t) for t in _owner_chunks(both if cold_user else ulong, chunk)[:5])
+    return dict(batch=B, cold_user=cold_user, user_range=user_range, item_range=item_range, users=c(ulong), pos=c(both[:B]),
+                neg=c(both[B:]), n_own=int(own_ids.shape[0]), n_own_chunks=int(chunk_own.shape[0]), own_ids=own_ids,
+                own_ptr=ptr, own_occ=occ, own_chunk_ptr=chunk_ptr, own_chunk_own=chunk_own)
+
+
+def duif(table: torch.Tensor, content: torch.Tensor, w: torch.Tensor, plan: dict, reg: float, cold_user: bool = False,
+         scale: float = 1.0, want_table: bool = True, want_w: bool = True, want_h: bool = False, grad_table=None,
+         grad_w=None, loss=None, workspace=None):
+    """One DUIF step, forward and backward, in one call (crh_duif_f32).  table (n_free, d): the trained table of the side
+    without content (the users in item mode, the items when cold_user); content (n_content, c): the other side's content
+    rows; w (d, c) = nn.Linear(c, d, bias=False).weight; fp32 contiguous, d % 4 == 0, 4 <= d <= 256, 1 <= c <= 4096;
+    plan: ``duif_plan`` of the same cold_user.  Returns (loss3 = [L_bpr, R, total], grad_table, grad_w, H): gradients are
+    d total / d . * scale, grad_table zero at rows the batch does not touch (a caller's buffer keeps those rows as they
+    were); H = content[ids] @ w.T, one row per projected occurrence (item mode: the B positives, then the B negatives;
+    user mode: the B users).  An output that is neither given nor wanted is not computed (None)."""
+    _need_cuda(table, content, w, plan["users"], grad_table, grad_w, loss, workspace)
+    dev = table.device
+    _check_2d_f32("duif", "the table, the content and the projection", table, content, w)
+    cold_user = bool(cold_user)
+    if cold_user != plan["cold_user"]:
+        raise RuntimeError("duif: the plan was made for the other cold object")
+    d, c = table.shape[1], content.shape[1]
+    _check_width("duif", d)
+    if c < 1 or c > 4096:
+        raise RuntimeError(f"duif: content width {c} must lie in [1, 4096]")
+    if w.shape != (d, c):
+        raise RuntimeError("duif: the projection must be (d, c): the table's width by the content's, nn.Linear's layout")
+    _check_one_device("duif", "the table's", dev, content, w, plan["users"], grad_table, grad_w, loss, workspace)
+    free, proj = (plan["item_range"], plan["user_range"]) if cold_user else (plan["user_range"], plan["item_range"])
+    if free[0] < 0 or free[1] >= table.shape[0] or proj[0] < 0 or proj[1] >= content.shape[0]:
+        raise RuntimeError("duif: ids lie outside the tables")
+    B = plan["batch"]
+    what = "the table's and the projection's shapes"
+    grad_table = _grad_buffer("duif", what, grad_table, table, want_table, False)
+    grad_w = _grad_buffer("duif", what, grad_w, w, want_w, True)
+    h = torch.empty((B if cold_user else 2 * B, d), dtype=torch.float32, device=dev) if want_h else None
+    loss = _loss_buffer("duif", loss, 3, dev)
+    workspace = _workspace_arg("duif", workspace, duif_workspace, B, d, c, cold_user, plan["n_own"], dev)
+    p, ptr = plan, _lib.ptr
+    _lib.check(_lib.lib().crh_duif_f32(
+        ptr(table), int(table.shape[0]), ptr(content), int(content.shape[0]), int(c), ptr(w), ptr(p["users"]), ptr(p["pos"]),
+        ptr(p["neg"]), int(free[0]), int(free[1]), int(proj[0]), int(proj[1]), ptr(p["own_ids"]), ptr(p["own_ptr"]),
+        ptr(p["own_occ"]), ptr(p["own_chunk_ptr"]), ptr(p["own_chunk_own"]), int(p["n_own"]), int(p["n_own_chunks"]), int(B),
+        int(d), int(cold_user), float(reg), float(scale), ptr(grad_table), ptr(grad_w), ptr(h), ptr(loss), ptr(workspace),
+        workspace.numel(), _lib.current_stream()), "crh_duif_f32")
+    return loss, grad_table, grad_w, h
+
+
 def adagrad_rows(p: torch.Tensor, g: torch.Tensor, state_sum: torch.Tensor, ids: torch.Tensor, lr: float,
                  eps: float = 1e-10, zero_grad: bool = True) -> None:
     """One step of torch.optim.Adagrad's defaults over the rows ``ids`` (int32, distinct) of p, in place:

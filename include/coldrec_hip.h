@@ -835,6 +835,47 @@ int crh_vbpr_f32(const float* user_table, int64_t user_rows, const float* item_t
                  void* stream);
 
 /*
+ * One step of DUIF (reference model/DUIF.py:19-23, util/utils.py:25-29, 44-48), forward and backward in one call
+ * (csrc/duif.hip).  table T (table_rows, d): the trained table of the side without content; content C (content_rows, c)
+ * fp32 row-major, 4-byte aligned only (a row starts wherever c puts it); w (d, c) = nn.Linear(c, d, bias=False).weight.
+ * 4 <= d <= 256, d % 4 == 0; 1 <= c <= 4096; 1 <= batch < 2^31.  Per record b a user, a positive and a negative:
+ *   cold_user == 0  u_b = T[users_b],  p_b = C[pos_b] w^T,  n_b = C[neg_b] w^T;  R = 2 batch projected rows: row o < batch
+ *                   belongs to the positive of record o, row batch + o to its negative
+ *   cold_user != 0  u_b = C[users_b] w^T,  p_b = T[pos_b],  n_b = T[neg_b];  R = batch projected rows
+ *   x_b = <u_b, p_b - n_b>;  L_bpr = mean_b -log(1e-5 + sigmoid(x_b));  R_reg = reg (|U|_F + |P|_F + |N|_F) / batch, the
+ *   Frobenius norms of the three (batch, d) blocks, duplicates counted; a norm of 0 has the gradient 0.
+ *   loss_out       3 device floats: L_bpr, R_reg, their sum (not scaled); NULL = not written
+ *   grad_table     d sum / d T * scale, written at the touched rows ONLY (every other row of the caller's buffer keeps what
+ *                  it held); duplicate ids are summed in the plan's order
+ *   grad_w         d sum / d w * scale, (d, c), every element written
+ *   h_out          the projected rows H (R, d), every row written
+ *                  Any output may be NULL: it is not computed and the others keep their bits; all NULL is an error
+ *   free_min .. content_max: the smallest and largest id of the free side (into T) and of the projected side (into C); a
+ *                  range that leaves its table is an argument error
+ *   own_*          the inverse index of the FREE side's occurrences only (cold_user == 0: the batch users; else the
+ *                  2 batch items, positives then negatives), as crh_gar_f32's, with chunks of crh_duif_chunk_rows()
+ *                  (ops.duif_plan builds it)
+ *   workspace      crh_duif_workspace_bytes(batch, d, c, cold_user, n_own) bytes (0 = a refused shape), 256-byte aligned:
+ *                  H and its gradient, the free side's per-occurrence rows, the records' terms, the owner chunks' partials,
+ *                  one (d, c) partial of grad_w per wave of the weight-gradient launch -- crh_duif_parts(R, d, c) of them
+ *                  (0 = a refused shape), a function of the shape alone -- and the sums of crh_duif_part_chunk()
+ *                  consecutive partials
+ * T, w, the gradients and h_out 16-byte aligned.  fp32 throughout on the fp32 MFMAs (exact fp32 fma chains); no atomics,
+ * every sum in an order fixed by (batch, d, c) and the plan: two identical calls give identical bits.  An argument error
+ * returns before anything is launched.
+ */
+int crh_duif_chunk_rows(void);
+int crh_duif_part_chunk(void);
+int64_t crh_duif_parts(int64_t rows, int d, int c);
+size_t crh_duif_workspace_bytes(int64_t batch, int d, int c, int cold_user, int64_t n_own);
+int crh_duif_f32(const float* table, int64_t table_rows, const float* content, int64_t content_rows, int c, const float* w,
+                 const int32_t* users, const int32_t* pos, const int32_t* neg, int free_min, int free_max, int content_min,
+                 int content_max, const int32_t* own_ids, const int32_t* own_ptr, const int32_t* own_occ,
+                 const int32_t* own_chunk_ptr, const int32_t* own_chunk_own, int64_t n_own, int64_t n_own_chunks,
+                 int64_t batch, int d, int cold_user, float reg, float scale, float* grad_table, float* grad_w, float* h_out,
+                 float* loss_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * torch.optim.Adagrad's defaults (lr_decay = 0, weight_decay = 0, accumulator 0) over n_ids DISTINCT rows of a (n_rows, d)
  * table, d % 4 == 0, 4 <= d <= 256 (csrc/adagrad.hip).  Per element, every operation rounded on its own:
  *     s <- s + g * g ;  p <- p + (-lr) * (g / (sqrt(s) + eps))          (lr and eps rounded to fp32)

@@ -1,5 +1,5 @@
-"""The output bits of the four fused losses that take a plan's inverse index (ops.ccfcrec, ops.gar, ops.mtpr, ops.vbpr) at
-the kernel tests' cases: every CASES entry, both cold modes, VBPR with and without h_adv.  Prints one JSON object, a
+"""The output bits of the five fused losses that take a plan's inverse index (ops.ccfcrec, ops.gar, ops.mtpr, ops.vbpr,
+ops.duif) at the kernel tests' cases: every CASES entry, both cold modes, VBPR with and without h_adv.  Prints one JSON object, a
 sha256 per output tensor.  Two libraries with the same ABI compute the same bits exactly when two runs print the same:
 
     python tools/loss_bits.py > a.json;  CRH_LIB=/path/to/other/libcoldrec_hip.so python tools/loss_bits.py > b.json
@@ -14,7 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from coldrec_amd import ops  # noqa: E402
-from tests import mtpr_restate, test_ccfcrec_gpu, test_gar_gpu, vbpr_restate  # noqa: E402  (the cases and their inputs)
+from tests import duif_restate, mtpr_restate, test_ccfcrec_gpu, test_gar_gpu, vbpr_restate  # noqa: E402  (the cases and their inputs)
 
 DEV = torch.device("cuda:0")
 
@@ -63,6 +63,12 @@ def main():
                            lmd=vbpr_restate.CASE_LMD, cold_user=cold_user, want_hsum=True)
             record(out, f"vbpr/{vbpr_restate.CASE_IDS(case)}/{vbpr_restate.VARIANT_IDS(variant)}",
                    ("loss", "grad_user", "grad_item", "grad_aux", "grad_h", "grad_h_adv", "grad_hsum"), got)
+    for case in duif_restate.CASES:
+        for cold_user in duif_restate.MODES:
+            T, C, W, users, pos, neg = (t.to(dev) for t in duif_restate.inputs(case, cold_user, ops.duif_chunk_rows()))
+            got = ops.duif(T, C, W, ops.duif_plan(users, pos, neg, cold_user), duif_restate.CASE_REG, cold_user=cold_user, want_h=True)
+            record(out, f"duif/{duif_restate.CASE_IDS(case)}/{duif_restate.MODE_IDS(cold_user)}",
+                   ("loss", "grad_table", "grad_w", "h"), got)
     print(json.dumps(out, indent=0, sort_keys=True))
 
 
